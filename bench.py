@@ -2,11 +2,17 @@
 on MI355X (BASELINE.json metric), 64x64x3 CarRacing-shaped synthetic replay.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --seq S --horizon H --precision fp32|bf16]
+                  [--dump-outputs DIR] [--full]
 
 Headline: K calls of Dreamer.train_Agent() with AC_epochs=1 at the north-star
 batch (B=256 per GPU, S=64, H=15), window draws inside the timed region.
-Secondaries: AC_epochs=2 (pipelined epochs), BASELINE configs[1] (B=64), the
-world-model step and the full iteration.
+A plain run sets up, warms up, times the K calls, writes what the last call
+computed when --dump-outputs is given, and prints the result line.
+--full adds everything else after the timed region: the live encoder roofline
+(and the figures derived from it), the secondaries (AC_epochs=2 pipelined
+epochs, BASELINE configs[1] (B=64), bf16 mode, configs[3], configs[4], acting),
+the world-model step with the full iteration, and the CPU baseline;
+--no-secondary, --wm-steps 0 and --no-cpu-baseline narrow a --full run.
 Multi-GPU: launched by torch.distributed.run, one process per GPU; weak
 scaling (B rows per GPU), RCCL all-gather of lambda returns + one all-reduce
 of the flat [actor|critic|loss] gradient buffer per epoch.  Rank 0 prints ONE
@@ -393,6 +399,37 @@ def make_dreamer(cfg, dev, B, S, H, res, ac_epochs, world, rank, group, precisio
     return c, d
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much (float32 payload)
+
+
+def dump_outputs(path, d, losses):
+    """What the last timed Dreamer.train_Agent() call computed, as
+    path/<name>.npy (float32): the two losses it returns, the actor / critic /
+    target-critic parameters it leaves behind, and the imagined trajectories
+    and lambda returns of its epoch.  Whole arrays while they fit in
+    DUMP_BUDGET_BYTES together (they do at the default shapes); otherwise the
+    budget is shared smallest array first, and an array over its share is
+    written as a fixed sample of its flattened elements (sorted indices drawn
+    from default_rng(0))."""
+    eng, ag = d._engine, d.agent
+    arrays = {
+        "losses": torch.tensor(losses, dtype=torch.float32),
+        "actor_params": ag.fa.flat, "critic_params": ag.fc.flat, "target_critic_params": ag.ft.flat,
+        "latents": eng.latents, "hiddens": eng.hiddens, "actions": eng.actions,
+        "rewards": eng.rewards, "continues": eng.continues, "lambda_returns": eng.R,
+    }
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        a = t.detach().to(torch.float32).cpu().numpy()
+        cap = left // (len(arrays) - i)
+        left -= min(a.size, cap)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 VEC_OBS_DIM = 24  # configs[4] proprioceptive vector observations (a walker-like state size)
 
 
@@ -432,11 +469,22 @@ def main():
                     help="frame side (64: CarRacing; 128: configs[3]'s frames with the reference's 4-conv encoder)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
                     help="fp32: parity mode (bit-exact indices vs the reference); bf16: perf mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the live encoder roofline, the secondaries, the "
+                         "world-model step and the CPU baseline (the options below narrow it)")
     ap.add_argument("--cpu-budget", type=float, default=24.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only")
-    ap.add_argument("--wm-steps", type=int, default=10, help="world-model training steps timed (0: skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondaries")
+    ap.add_argument("--wm-steps", type=int, default=10,
+                    help="with --full: world-model training steps timed (0: skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_cpu_baseline, args.no_secondary, args.wm_steps = True, True, 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -485,6 +533,8 @@ def main():
     cfg, d = make_dreamer(CAR_RACER, dev, B, S, H, res, 1, world, rank, group, args.precision)
     el, (la, lc) = time_train_agent(d, args.steps, args.warmup)
     value = world * B * H * args.steps / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d, (la, lc))  # before anything below trains d further
     eng = d._engine
     frames = B * (S // 2)
     enc_flops = encoder_flops_per_frame(cfg) * frames
@@ -630,11 +680,10 @@ def main():
         return
     # the dominant kernel group (conv encoder + feature projection) timed live
     # with HIP events on the engine's stream, back to back, after the timed region
-    enc_s = eng.time_encoder(reps=5) / 1e3
+    # (--full only: the encodes are runs of their own)
+    enc_s = eng.time_encoder(reps=5) / 1e3 if args.full else None
     peak = BF16_MFMA_PEAK_TFLOPS if args.precision == "bf16" else SPLIT3_PEAK_TFLOPS
     path_peak = BF16_MFMA_PEAK_TFLOPS if args.precision == "bf16" else FP32_MFMA_PEAK_TFLOPS
-    achieved = enc_flops / enc_s / 1e12
-    traffic, traffic_src = traffic_for(B, res, args.precision)
     dtype = "bf16" if args.precision == "bf16" else "f32"
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "imagined latent-steps/s", "n_gpus": world,
@@ -648,24 +697,28 @@ def main():
                                + (" (north-star batch per GPU)" if (B, S, H, res) == (256, 64, 15, 64) else ""),
                    "global_batch": B * world, "seq_len": S, "horizon": H, "parallelism": f"dp{world}",
                    "precision": args.precision},
-        "roofline": {"bound": "mfma", "kernel": "encoder conv stack + feature projection (one train_Agent epoch's "
-                                                 f"{frames} warm-start frames)",
-                     "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic,
-                     "traffic_unit": "HBM-side bytes per launch group (per epoch)", "traffic_source": traffic_src,
-                     "algorithmic_flops_per_launch": enc_flops,
-                     "algorithmic_unit": "55.77 MFLOP per 64x64 frame (SURVEY §8d) x B*S/2 frames",
-                     "encoder_ms": round(enc_s * 1e3, 4),
-                     "peak_note": ("bf16 MFMA dense peak" if args.precision == "bf16" else
-                                   "f32 work on the bf16 MFMA, 6 split products per f32 product (2500/6); "
-                                   "the f32-input MFMA peak is 157.3 (frac_vs_f32_mfma_peak), the bf16 pipe the "
-                                   "split products occupy 2500 (frac_vs_bf16_pipe)")},
-        "losses": {"actor": la, "critic": lc},
     }
-    if args.precision != "bf16":
+    if enc_s is not None:
+        achieved = enc_flops / enc_s / 1e12
+        traffic, traffic_src = traffic_for(B, res, args.precision)
+        out["roofline"] = {
+            "bound": "mfma", "kernel": "encoder conv stack + feature projection (one train_Agent epoch's "
+                                       f"{frames} warm-start frames)",
+            "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4), "traffic": traffic,
+            "traffic_unit": "HBM-side bytes per launch group (per epoch)", "traffic_source": traffic_src,
+            "algorithmic_flops_per_launch": enc_flops,
+            "algorithmic_unit": "55.77 MFLOP per 64x64 frame (SURVEY §8d) x B*S/2 frames",
+            "encoder_ms": round(enc_s * 1e3, 4),
+            "peak_note": ("bf16 MFMA dense peak" if args.precision == "bf16" else
+                          "f32 work on the bf16 MFMA, 6 split products per f32 product (2500/6); "
+                          "the f32-input MFMA peak is 157.3 (frac_vs_f32_mfma_peak), the bf16 pipe the "
+                          "split products occupy 2500 (frac_vs_bf16_pipe)")}
+    out["losses"] = {"actor": la, "critic": lc}
+    if enc_s is not None and args.precision != "bf16":
         out["roofline"]["frac_vs_f32_mfma_peak"] = round(achieved / FP32_MFMA_PEAK_TFLOPS, 4)
         out["roofline"]["frac_vs_bf16_pipe"] = round(6 * achieved / BF16_MFMA_PEAK_TFLOPS, 4)
-    if (B, S, H, res) == (256, 64, 15, 64):
+    if enc_s is not None and (B, S, H, res) == (256, 64, 15, 64):
         # the same group from the committed kernel trace (per-kernel averages under the profiler)
         pms, pk, psrc, phash = profile_encoder_ms(args.precision)
         if pms:
@@ -686,7 +739,7 @@ def main():
                                 "note": "whole train_Agent epoch, SURVEY §8d necessary FLOPs x imagined steps/s"}
         # the chain: everything but the encoder group (warm-start scan, dream, update) per epoch
         chain_fl = mf * 1e6 * B * H - enc_flops
-        chain_s = el / args.steps - enc_s
+        chain_s = el / args.steps - enc_s if enc_s is not None else 0.0
         if chain_s > 0:
             ctf = chain_fl / chain_s / 1e12
             out["chain_roofline"] = {"bound": "mfma", "achieved": round(ctf, 2), "peak": path_peak, "unit": "TFLOP/s",

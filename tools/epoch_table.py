@@ -2,7 +2,7 @@
 
   python tools/epoch_table.py prof_results.db EPOCHS ENCODES [top]
 
-The profiled command is `bench.py --steps S --warmup W --no-cpu-baseline
+The profiled command is `bench.py --full --steps S --warmup W --no-cpu-baseline
 --no-secondary --wm-steps 0`: EPOCHS = S + W train_Agent epochs, and the
 encoder kernels run ENCODES = EPOCHS + 6 times (bench.py's live roofline timing
 adds one warm-up and five timed encodes).  A kernel whose call count divides by

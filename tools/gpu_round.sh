@@ -1,11 +1,14 @@
 #!/bin/bash
-# tests + bench + kernel-trace profile, each step under its own time limit
+# tests + full bench + kernel-trace profile, each step under its own time limit
+# (bench and profile logs under $OUT_DIR, default bench_out/ in the repository root)
 cd "$(dirname "$0")/.." || exit 1
 export PYTHONUNBUFFERED=1
 TAG=${1:-r02}
+R=$(pwd)
+OUT=$(mkdir -p "${OUT_DIR:-bench_out}" && cd "${OUT_DIR:-bench_out}" && pwd) || exit 1
 bash tools/gpu_tests.sh || exit 1
-timeout -k 10 400 python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -30 gpurun_out/bench_$TAG.err; exit 1; }
-cat gpurun_out/bench_$TAG.json
+timeout -k 10 400 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -30 $OUT/bench_$TAG.err; exit 1; }
+cat $OUT/bench_$TAG.json
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o p -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --wm-steps 0 > $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG.log 2>&1 || { tail -20 $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG.log; exit 1; }
-tail -2 $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG.log
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o p -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary --wm-steps 0 > $OUT/prof_$TAG.log 2>&1 || { tail -20 $OUT/prof_$TAG.log; exit 1; }
+tail -2 $OUT/prof_$TAG.log
