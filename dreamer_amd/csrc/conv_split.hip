@@ -392,6 +392,32 @@ static constexpr size_t e12_lds_bytes(int terms = 3) {
   return (size_t)terms * 4 * E12_PS * 16 + (size_t)E12_RI * E12_LWI * 8;
 }
 
+// Phase timestamps (tools/build_e12_ts.sh, tools/enc12_probe.py): compiled in
+// only with -DDR_E12_TS.  Thread 0 of waves 0 and 4 of the first workgroups
+// stamps the 100 MHz clock at the phase boundaries of its first tiles.
+// DR_E12_TS=2 also sends the three-term launch back to the one-schedule form
+// (k_enc12_split3<8>), for a phase table of both on one box.
+#define E12_TS_WGS 4
+#define E12_TS_TILES 4
+#define E12_TS_MARKS 8
+#ifdef DR_E12_TS
+__device__ long long dr_e12_ts_buf[E12_TS_WGS * E12_TS_TILES * 2 * E12_TS_MARKS];
+#define E12_TS(tile, k)                                                                                        \
+  do {                                                                                                         \
+    const int it_ = ((tile) - (int)blockIdx.x) / (int)gridDim.x;                                               \
+    if ((threadIdx.x & 255) == 0 && blockIdx.x < E12_TS_WGS && it_ < E12_TS_TILES)                             \
+      dr_e12_ts_buf[((blockIdx.x * E12_TS_TILES + it_) * 2 + (threadIdx.x >> 8)) * E12_TS_MARKS + (k)] =       \
+          (long long)wall_clock64();                                                                           \
+  } while (0)
+extern "C" int dr_e12_ts_read(long long* host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(dr_e12_ts_buf), sizeof(dr_e12_ts_buf)) == hipSuccess ? 0 : -1;
+}
+#else
+#define E12_TS(tile, k) \
+  do {                  \
+  } while (0)
+#endif
+
 // NW = 8: two waves per SIMD -- waves 0-3 run conv2's taps 0-7 and waves 4-7
 // taps 8-15 over the same 64 x 32 output blocks, the two partial sums meet in
 // LDS (fixed order: taps 0-7 + taps 8-15) before the epilogue
@@ -486,6 +512,7 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
   for (;;) {
     const int f = tile >> 1, y2_0 = (tile & 1) * R2, y1_0 = 2 * y2_0 - 1;
     const int next = tile + (int)gridDim.x;
+    E12_TS(tile, 0);
     // conv1 weights (A operand: lane -> channel 16 j + r, k = 32 s + 8 q .. + 7), three
     // planes: re-read per tile (L2) so that they hold no registers during conv2
     u32x4 wa1[NTM][2][2];
@@ -559,7 +586,9 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
         }
       }
     }
+    E12_TS(tile, 1);
     __syncthreads();
+    E12_TS(tile, 2);
     // the next tile's input rows: loads in flight under conv2 (xin is free now)
     if (next < ntiles) in_load(next);
 
@@ -608,6 +637,7 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) wfa[pl][jj] = wfb[pl][jj];
     }
+    E12_TS(tile, 3);
     if (NW == 8) {
       // taps 8-15 partials through LDS (c1o is free once every wave is past conv2)
       f32x4* red = reinterpret_cast<f32x4*>(e12_smem);  // [4 waves][8 blocks][64 lanes]
@@ -626,6 +656,7 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
           for (int jj = 0; jj < 2; ++jj) acc[i][jj] += red[(w4 * 8 + i * 2 + jj) * 64 + lane];
       }
     }
+    E12_TS(tile, 4);
     // lane (r, q) of acc[i][jj]: channels 32 ch + 16 jj + 4 q .. + 3 of conv2 pixel (row 4 ph + i, column r)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -647,9 +678,305 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
         if (pre1) *reinterpret_cast<f32x4*>(pre1 + (o - out) + co) = pv;
       }
     }
+    E12_TS(tile, 5);
     if (next >= ntiles) break;  // uniform over the workgroup: every wave leaves here
     in_store(next);
     __syncthreads();  // next input staged; every wave is past its conv2 reads of c1o
+    E12_TS(tile, 6);
+    tile = next;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The three-term form at 8 waves (the fp32 encoder and, with the saves, the
+// fp32 world-model step): the tile, the wave roles in conv2 and every sum of
+// k_enc12_split3<8> above, bit for bit, on a schedule that keeps less work
+// beside an idle matrix pipe:
+//  - the conv1 planes carry the two out-of-frame columns as zeros (row stride
+//    34, written once), so a conv2 tap reads its fragments without selects;
+//  - conv2 names a tap's fragments and weights one tap ahead of its MFMAs (two
+//    register sets, no copies); the compiler still sinks most of those loads
+//    to their use, and pinning them with scheduling fences measured slower
+//    (profiles/r07a_ab_enc12_x8.txt);
+//  - the two tap halves are exchanged, not reduced one way: waves 0-3 finish
+//    rows 0-1 of their four, waves 4-7 rows 2-3 (a + b = b + a), so all eight
+//    waves run the epilogue; the exchange buffer lies over the input rows,
+//    not over the planes, which drops the barrier in front of it;
+//  - the input rows are staged as whole pixels (one 8-byte LDS store each);
+//  - conv1's 36 blocks go 4.5 to a wave (the last four split by channel
+//    half), and its weights and bias are read once, not per tile;
+//  - the barriers wait on LDS only (dr_lds_barrier), so the next tile's input
+//    loads and the epilogue's stores stay in flight across them.
+// LDS: planes [3][4 c8][PS] 117.7 KB + 32 KB (input rows 20 KB / exchange).
+// ---------------------------------------------------------------------------
+#define E12X_OW 34
+#define E12X_PS (E12_R1 * E12X_OW + 1)
+#define E12X_XCH (8 * 4 * 64 * 16)  // [8 waves][4 blocks][64 lanes] f32x4
+static constexpr size_t e12x_lds_bytes() { return (size_t)3 * 4 * E12X_PS * 16 + E12X_XCH; }
+static_assert(E12X_XCH >= E12_RI * E12_LWI * 8 && e12x_lds_bytes() <= 160 * 1024, "enc12 LDS");
+
+__global__ __launch_bounds__(512, 1) void k_enc12_split3_x8(int n, int nb, dr_frames src, const u16* __restrict__ wr1,
+                                                            const float* __restrict__ b1, const u16* __restrict__ wr2,
+                                                            const float* __restrict__ b2, float* __restrict__ out,
+                                                            float* __restrict__ pre0, float* __restrict__ a0,
+                                                            float* __restrict__ pre1) {
+  constexpr int NTH = 512, TAPS = 8;
+  constexpr int R2 = E12_R2, R1 = E12_R1, RI = E12_RI, PS = E12X_PS, OWP = E12X_OW, LWI = E12_LWI;
+  constexpr int OW1 = 32, OW2 = 16, W = 64, H = 64, C1 = 32, C2 = 64;
+  extern __shared__ __attribute__((aligned(16))) u32x4 e12_smem[];
+  u32x4* c1o = e12_smem;                                            // [3][4][PS]
+  uint2* xin = reinterpret_cast<uint2*>(e12_smem + 3 * 4 * PS);    // [RI][LWI]
+  f32x4* xch = reinterpret_cast<f32x4*>(e12_smem + 3 * 4 * PS);    // over xin: free between conv1 and the staging
+  u16* c1h = reinterpret_cast<u16*>(c1o);
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 15,
+            q = lane >> 4;
+  const int ntiles = 2 * n;
+  int tile = blockIdx.x;
+  if (tile >= ntiles) return;
+
+  // ---- written once: the planes' zero columns 0 / OWP - 1 ----
+  for (int i = tid; i < 3 * 4 * R1 * 2; i += NTH) {
+    const int pc = i / (2 * R1), rem = i - pc * 2 * R1;
+    c1o[pc * PS + (rem >> 1) * OWP + (rem & 1) * (OWP - 1)] = (u32x4){0u, 0u, 0u, 0u};
+  }
+  // input rows: bf16 of the centred pixel values, [row][x + 1][4 ch]; a thread
+  // takes 4 pixels x 3 channels (three dwords of the planar u8 frame).  Every
+  // tile writes every entry, the zero padding (columns 0 / LWI - 1, channel
+  // slot 3, rows outside the frame) included: the exchange overwrites the rows
+  constexpr int NIT = RI * (W / 4), MAXI = (NIT + NTH - 1) / NTH;
+  const unsigned hw = (unsigned)(H * W);
+  const float centre = src.raw255 ? 127.5f : 0.0f, scale = src.raw255 ? 1.0f / 255.0f : 1.0f;
+  unsigned uv[MAXI][3];
+  auto in_load = [&](int tl) __attribute__((always_inline)) {
+    const int f = tl >> 1, iy0 = 2 * (2 * (tl & 1) * R2 - 1) - 1;
+    const int b = f % nb, t = f / nb + src.t0;
+    const unsigned char* fr8 = src.ring + ((src.starts[b] + t) % src.ring_cap) * 3 * (long long)hw;
+#pragma unroll
+    for (int k = 0; k < MAXI; ++k) {
+      const int i = tid + NTH * k, rr = i >> 4, x4 = i & 15, y = iy0 + rr;
+      const bool ok = i < NIT && y >= 0 && y < H;
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        uv[k][c] = *reinterpret_cast<const unsigned*>(fr8 + (ok ? (unsigned)c * hw + (unsigned)(y * W + 4 * x4) : 0u));
+    }
+  };
+  auto in_store = [&](int tl) __attribute__((always_inline)) {
+    const int iy0 = 2 * (2 * (tl & 1) * R2 - 1) - 1;
+#pragma unroll
+    for (int k = 0; k < MAXI; ++k) {
+      const int i = tid + NTH * k, rr = i >> 4, x4 = i & 15, y = iy0 + rr;
+      if (i >= NIT) continue;
+      const bool ok = y >= 0 && y < H;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        unsigned bb[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bb[c] = b16bits((__bf16)((float)((uv[k][c] >> (8 * e)) & 255u) - centre));
+        xin[rr * LWI + 4 * x4 + e + 1] = ok ? make_uint2(bb[0] | (bb[1] << 16), bb[2]) : make_uint2(0u, 0u);
+      }
+      if (x4 == 0) xin[rr * LWI] = make_uint2(0u, 0u);
+      if (x4 == W / 4 - 1) xin[rr * LWI + LWI - 1] = make_uint2(0u, 0u);
+    }
+  };
+  in_load(tile);
+  // conv1 weights (A operand: lane -> channel 16 j + r, k = 32 s + 8 q .. + 7), three
+  // planes, and bias: read once and kept (56 registers; conv2 leaves them room)
+  u32x4 wa1[3][2][2];
+  float bb1[2][4];
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        wa1[pl][s][j] = *reinterpret_cast<const u32x4*>(wr1 + ((long long)pl * C1 + 16 * j + r) * 64 + 32 * s + 8 * q);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bb1[j][e] = b1[16 * j + 4 * q + e];
+  in_store(tile);
+  __syncthreads();
+
+  const int w4 = wave & 3, kh = wave >> 2, ph = w4 & 1, ch = w4 >> 1;
+  // conv2 weight fragments straight from L2 (the 196 KB of split planes stay
+  // resident): lane (r, q) of wf[pl][jj] = row 32 ch + 16 jj + r, k 8 q .. + 7
+  const u16* wbase = wr2 + ((long long)(32 * ch + r)) * 32 + 8 * q;
+  auto wld = [&](u32x4 (&wf)[3][2], int tap) __attribute__((always_inline)) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+        wf[pl][jj] = *reinterpret_cast<const u32x4*>(wbase + ((long long)(tap * 3 + pl) * C2 + 16 * jj) * 32);
+  };
+  // a tap's pixel fragments: conv1 column x1 = 2 r - 1 + kx sits at x1 + 1
+  auto pld = [&](u32x4 (&pf)[3][4], int tap) __attribute__((always_inline)) {
+    const int ky = tap >> 2, kx = tap & 3;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int u = q * PS + (2 * (4 * ph + i) + ky) * OWP + 2 * r + kx;
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) pf[pl][i] = c1o[pl * 4 * PS + u];
+    }
+  };
+
+  for (;;) {
+    const int f = tile >> 1, y2_0 = (tile & 1) * R2, y1_0 = 2 * y2_0 - 1;
+    const int next = tile + (int)gridDim.x;
+    E12_TS(tile, 0);
+    u32x4 wfa[3][2], wfb[3][2];
+    wld(wfa, TAPS * kh);
+    // ---- conv1 over the R1 tile rows; rows outside the frame are conv2's zero padding.
+    // JM: the channel halves (bit j = channels 16 j .. + 15) this wave computes of block i ----
+    auto c1_block = [&](int i, auto JM) __attribute__((always_inline)) {
+      constexpr int jm = decltype(JM)::value;
+      const int yl = i >> 1, x1 = 16 * (i & 1) + r, y1 = y1_0 + yl;
+      uint2 hv[2], mv[2], lv[2];
+      if (y1 < 0 || y1 >= H / 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) hv[j] = mv[j] = lv[j] = make_uint2(0u, 0u);
+      } else {
+        f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int t0 = 8 * s + 2 * q, ky = t0 >> 2, kx = t0 & 3;
+          const u32x4 pb = *reinterpret_cast<const u32x4*>(&xin[(2 * yl + ky) * LWI + 2 * x1 + kx]);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            if (!((jm >> j) & 1)) continue;
+#pragma unroll
+            for (int pl = 2; pl >= 0; --pl) acc[j] = mfma_b16(wa1[pl][s][j], pb, acc[j]);
+          }
+        }
+        // lane: pixel (yl, x1), channels 16 j + 4 q .. + 3
+        const bool own = pre0 && yl >= 1 && yl <= 2 * R2;  // this tile's own conv1 rows
+        const long long o1 = (((long long)f * (H / 2) + y1) * OW1 + x1) * C1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (!((jm >> j) & 1)) continue;
+          float v[4], pv[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            pv[e] = acc[j][e] * scale + bb1[j][e];
+            v[e] = dr_silu_fast(pv[e]);
+          }
+          if (own) {
+            *reinterpret_cast<f32x4*>(pre0 + o1 + 16 * j + 4 * q) = (f32x4){pv[0], pv[1], pv[2], pv[3]};
+            *reinterpret_cast<f32x4*>(a0 + o1 + 16 * j + 4 * q) = (f32x4){v[0], v[1], v[2], v[3]};
+          }
+          split3_pair(v[0], v[1], hv[j].x, mv[j].x, lv[j].x);
+          split3_pair(v[2], v[3], hv[j].y, mv[j].y, lv[j].y);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (!((jm >> j) & 1)) continue;
+        const int c8 = 2 * j + (q >> 1);
+        const int o = (c8 * PS + yl * OWP + x1 + 1) * 8 + (q & 1) * 4;  // u16 offset inside a plane
+        *reinterpret_cast<uint2*>(c1h + o) = hv[j];
+        *reinterpret_cast<uint2*>(c1h + 4 * PS * 8 + o) = mv[j];
+        *reinterpret_cast<uint2*>(c1h + 2 * 4 * PS * 8 + o) = lv[j];
+      }
+    };
+    constexpr int F1 = R1 * OW1 / 16;  // 36 blocks: four whole ones and a half per wave
+    static_assert(F1 == 36, "conv1 block split");
+    for (int i = wave; i < 32; i += 8) c1_block(i, std::integral_constant<int, 3>());
+    if (wave & 1)
+      c1_block(32 + (wave >> 1), std::integral_constant<int, 2>());
+    else
+      c1_block(32 + (wave >> 1), std::integral_constant<int, 1>());
+    E12_TS(tile, 1);
+    dr_lds_barrier();
+    E12_TS(tile, 2);
+    // the next tile's input rows: loads in flight under conv2
+    if (next < ntiles) in_load(next);
+
+    // ---- conv2: this wave's 8 taps x 32 channels, one MFMA k-step per tap; c1o is
+    // read-only here and the weights come from L2, so no barrier in the loop ----
+    f32x4 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) acc[i][jj] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // smallest terms first (weight plane x activation plane)
+    auto tap_mm = [&](u32x4 (&wf)[3][2], u32x4 (&pf)[3][4]) __attribute__((always_inline)) {
+#define E12_S3(PW, PA)                       \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) acc[i][jj] = \
+      mfma_b16(wf[PW][jj], pf[PA][i], acc[i][jj]);
+      E12_S3(2, 0)
+      E12_S3(1, 1)
+      E12_S3(0, 2)
+      E12_S3(1, 0)
+      E12_S3(0, 1)
+      E12_S3(0, 0)
+#undef E12_S3
+    };
+    {
+      const int tap0 = TAPS * kh, last = tap0 + TAPS - 1;
+      u32x4 pfa[3][4], pfb[3][4];
+      pld(pfa, tap0);
+#pragma unroll 1
+      for (int tap = tap0; tap < last; tap += 2) {
+        wld(wfb, tap + 1);
+        pld(pfb, tap + 1);
+        tap_mm(wfa, pfa);
+        const int tn = tap + 2 < last ? tap + 2 : last;  // (the last reload is unused)
+        wld(wfa, tn);
+        pld(pfa, tn);
+        tap_mm(wfb, pfb);
+      }
+    }
+    E12_TS(tile, 3);
+    // ---- the two tap halves meet: each side sends the rows the other finishes ----
+    // lane (r, q) of acc[i][jj]: channels 32 ch + 16 jj + 4 q .. + 3 of conv2 pixel (row 4 ph + i, column r)
+    f32x4 fin[2][2];
+    if (kh) {
+#pragma unroll
+      for (int il = 0; il < 2; ++il)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) xch[(wave * 4 + il * 2 + jj) * 64 + lane] = acc[il][jj];
+    } else {
+#pragma unroll
+      for (int il = 0; il < 2; ++il)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) xch[(wave * 4 + il * 2 + jj) * 64 + lane] = acc[2 + il][jj];
+    }
+    dr_lds_barrier();
+    if (kh) {  // taps 0-7 + taps 8-15, as the one-way sum
+#pragma unroll
+      for (int il = 0; il < 2; ++il)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) fin[il][jj] = xch[((wave - 4) * 4 + il * 2 + jj) * 64 + lane] + acc[2 + il][jj];
+    } else {
+#pragma unroll
+      for (int il = 0; il < 2; ++il)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) fin[il][jj] = acc[il][jj] + xch[((wave + 4) * 4 + il * 2 + jj) * 64 + lane];
+    }
+    E12_TS(tile, 4);
+    if (next < ntiles) {  // uniform over the workgroup
+      dr_lds_barrier();   // the exchange is read: the input rows may be written
+      in_store(next);
+      dr_lds_barrier();   // next input staged; every wave is past its conv2 reads of c1o
+    }
+    E12_TS(tile, 5);
+    // ---- epilogue: rows 4 ph + 2 kh + il; it shares its barrier interval with the next conv1 ----
+#pragma unroll
+    for (int il = 0; il < 2; ++il) {
+      float* o = out + (((long long)f * OW2 + y2_0 + 4 * ph + 2 * kh + il) * OW2 + r) * C2;
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int co = 32 * ch + 16 * jj + 4 * q;
+        const f32x4 bv = *reinterpret_cast<const f32x4*>(b2 + co);
+        f32x4 v;
+        const f32x4 pv = fin[il][jj] + bv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = dr_silu_fast(pv[e]);
+        *reinterpret_cast<f32x4*>(o + co) = v;
+        if (pre1) *reinterpret_cast<f32x4*>(pre1 + (o - out) + co) = pv;
+      }
+    }
+    E12_TS(tile, 6);
+    if (next >= ntiles) break;
     tile = next;
   }
 }
@@ -692,8 +1019,12 @@ int op_enc12_split3_ex(int n, int nb, int h, int w, int c1, int c2, const dr_fra
   static const bool raised = [] {
     (void)hipFuncSetAttribute((const void*)k_enc12_split3<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)e12_lds_bytes());
+    (void)hipFuncSetAttribute((const void*)k_enc12_split3_x8, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)e12x_lds_bytes());
+#if defined(DR_E12_TS) && DR_E12_TS == 2
     (void)hipFuncSetAttribute((const void*)k_enc12_split3<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)e12_lds_bytes());
+#endif
     return true;
   }();
   (void)raised;
@@ -730,8 +1061,13 @@ int op_enc12_split3_ex(int n, int nb, int h, int w, int c1, int c2, const dr_fra
   if (cus[dev] == 0) DR_TRY_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
   const int grid = std::min(n * 2, std::max(1, cus[dev]));
   // 8 waves (two per SIMD); one wave per SIMD measured 517.0 k against 532.9 k (r03o)
+#if defined(DR_E12_TS) && DR_E12_TS == 2
   hipLaunchKernelGGL(k_enc12_split3<8>, dim3((unsigned)grid), dim3(512), e12_lds_bytes(), s, n, nb, *src,
                      (const u16*)wr1, b1, (const u16*)wr2, b2, out, pre0, a0, pre1);
+#else
+  hipLaunchKernelGGL(k_enc12_split3_x8, dim3((unsigned)grid), dim3(512), e12x_lds_bytes(), s, n, nb, *src,
+                     (const u16*)wr1, b1, (const u16*)wr2, b2, out, pre0, a0, pre1);
+#endif
   return dr_check_launch("enc12_split3");
 }
 
