@@ -179,6 +179,138 @@ __device__ __forceinline__ void act_conv(int ih, int iw, int cin, int cout, cons
   }
 }
 
+// The batched conv stage: the same (pixel block, channel) task for every frame
+// of a batch with the channel's weights held in registers.  Per frame the
+// one-row path above costs 10-20 us, nearly all of it index arithmetic (about
+// ten VALU instructions per FMA) and one-at-a-time reductions, so here the map
+// shape is a compile-time constant (IW x IW x CIN; act_dims_ok pins it):
+//  - the slab has a zero pad column on either side of a row, so no gather
+//    needs a bounds test, and k = lane + 64 j moves the address by 4 j floats,
+//    so every gather is one LDS read at lane base + immediate and one FMA;
+//    the strides spread a pixel's 64 gather addresses over all 32 banks;
+//  - the pixel loop is unrolled, which lets the 2 x OW independent reduction
+//    chains overlap; lane p keeps pixel p and the SiLU + store happen once;
+//  - two slabs: frame e + 1 is fetched into registers before frame e's pixels
+//    are computed and written to the other slab after them.
+// Each output is still sum over k = lane + 64 j (j ascending) then wave_sum of
+// the same products as act_conv's, so the bits are the same.
+template <int IW, int CIN, bool FRAME>
+struct ActSlab {
+  // channel stride CS = 4 (mod 32) and row stride SR = 16 (mod 32): the 64 gather addresses of a pixel,
+  // ky SR + kx CS + (lane >> 4), then fall on 32 distinct banks, two lanes each
+  static constexpr int CS = CIN % 4 == 0 ? CIN + 4 : CIN + 1, RW = IW + 2;
+  static constexpr int SR = RW * CS + (48 - (RW * CS) % 32) % 32, SIZE = 6 * SR, STRIDE = SIZE;
+  static_assert(CS % 32 == 4 && SR % 32 == 16, "bank spread");
+  static constexpr int N4 = 6 * IW * CIN / 4, NV = (N4 + ACT_NT - 1) / ACT_NT;
+  float4 v[NV];  // this thread's share of the 6 input rows, 4 consecutive elements each
+  // in: the f32 NHWC map, or frame: the u8 HWC frame (x / 255 - 0.5, Dreamer.py:251); rows outside the map are zero
+  __device__ __forceinline__ void load(int pb, const float* in, const unsigned char* frame) {
+    const int y0 = 4 * pb - 1;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int i4 = threadIdx.x + u * ACT_NT, e = i4 < N4 ? 4 * i4 : 0;
+      const int r = e / (IW * CIN), rem = e - r * (IW * CIN), y = y0 + r;
+      const bool ok = i4 < N4 && y >= 0 && y < IW;
+      const int src = min(max(y, 0), IW - 1) * (IW * CIN) + rem;  // always inside the map: the load is unconditional
+      if constexpr (FRAME) {
+        const unsigned wd = *reinterpret_cast<const unsigned*>(frame + src);
+        const float4 f = make_float4((float)(wd & 255u) / 255.0f - 0.5f, (float)((wd >> 8) & 255u) / 255.0f - 0.5f,
+                                     (float)((wd >> 16) & 255u) / 255.0f - 0.5f, (float)(wd >> 24) / 255.0f - 0.5f);
+        v[u] = ok ? f : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        const float4 f = *reinterpret_cast<const float4*>(in + src);
+        v[u] = ok ? f : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+  }
+  __device__ __forceinline__ void store(float* xs) const {
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+      const int i4 = threadIdx.x + u * ACT_NT;
+      if (i4 >= N4) break;
+      if constexpr (CIN % 4 == 0) {  // the 4 elements are channels of one pixel, 16-byte aligned in the slab
+        const int e = 4 * i4, r = e / (IW * CIN), rem = e - r * (IW * CIN), px = rem / CIN, ch = rem - px * CIN;
+        *reinterpret_cast<float4*>(xs + r * SR + (px + 1) * CS + ch) = v[u];
+      } else {
+        const float c[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int e = 4 * i4 + q, r = e / (IW * CIN), rem = e - r * (IW * CIN), px = rem / CIN, ch = rem - px * CIN;
+          xs[r * SR + (px + 1) * CS + ch] = c[q];
+        }
+      }
+    }
+  }
+  // the pad columns: cells 0 and IW + 1 of the 6 rows
+  static __device__ __forceinline__ void pads(float* xs) {
+    for (int i = threadIdx.x; i < 12 * CS; i += ACT_NT) {
+      const int r = i / (2 * CS), c = i - r * 2 * CS;
+      xs[r * SR + (c < CS ? c : (IW + 1) * CS + c - CS)] = 0.f;
+    }
+  }
+};
+// dynamic LDS the batched conv stages need: two slabs of the largest map (conv4's, 8 x 8 x 128)
+#define ACT_BATCH_CONV_LDS (2 * ActSlab<8, 128, false>::STRIDE)
+
+template <int KJ, bool NCHW, int IW, int CIN>
+__device__ __forceinline__ void act_conv_pixels_t(int cout, int pb, int co, const float (&wv)[KJ], float bias,
+                                                  const float* xs, float* out) {
+  constexpr int CS = ActSlab<IW, CIN, false>::CS, SR = ActSlab<IW, CIN, false>::SR, OW = IW / 2, K = CIN * 16;
+  static_assert(K % 64 == 0 || KJ == 1, "a partial k batch only where it is the only one");
+  static_assert(2 * OW <= 64, "one pixel per lane");
+  const int lane = threadIdx.x & 63;
+  // k = lane + 64 j -> (ci, ky, kx) = ((lane >> 4) + 4 j, (lane >> 2) & 3, lane & 3); lanes past K hold a zero
+  // weight and read cell 0 of the pixel's window
+  const float* xb = xs + (lane < K ? ((lane >> 2) & 3) * SR + (lane & 3) * CS + (lane >> 4) : 0);
+  float mine = 0.f;
+#pragma unroll
+  for (int pl = 0; pl < 2 * OW; ++pl) {
+    const int po = 2 * (pl / OW) * SR + 2 * (pl % OW) * CS;  // (a constant after unrolling)
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < KJ; ++j) acc = fmaf(wv[j], xb[po + 4 * j], acc);
+    acc = wave_sum(acc);
+    if (lane == pl) mine = acc + bias;
+  }
+  if (lane < 2 * OW) {
+    const int p = (2 * pb + lane / OW) * OW + lane % OW;
+    out[NCHW ? co * OW * OW + p : p * cout + co] = mine / (1.0f + expf(-mine));
+  }
+}
+
+// frame e's input at in + e * in_ld (or frames + e * IW * IW * CIN), its output at out + e * out_ld
+template <int KJ, bool FRAME, bool NCHW, int IW, int CIN>
+__device__ __forceinline__ void act_conv_rows(int n_env, int cout, const float* in, long long in_ld,
+                                              const unsigned char* frames, const float* __restrict__ w,
+                                              const float* __restrict__ b, float* out, long long out_ld, float* xs) {
+  using Slab = ActSlab<IW, CIN, FRAME>;
+  static_assert(2 * Slab::STRIDE <= ACT_BATCH_CONV_LDS, "slab pair");
+  constexpr int NPB = IW / 4;
+  const int pb = blockIdx.x % NPB, co = (blockIdx.x / NPB) * 4 + (threadIdx.x >> 6);
+  float wv[KJ];  // the channel's weight row [ci][ky][kx], k = lane + 64 j, as act_conv
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int k = (threadIdx.x & 63) + 64 * j;
+    wv[j] = (k < CIN * 16 && co < cout) ? w[(long long)co * (CIN * 16) + k] : 0.f;
+  }
+  const float bias = co < cout ? b[co] : 0.f;
+  __syncthreads();  // the previous readers of xs are done
+  Slab::pads(xs);
+  Slab::pads(xs + Slab::STRIDE);
+  Slab s;
+  s.load(pb, in, frames);
+  s.store(xs);
+  for (int e = 0; e < n_env; ++e) {
+    __syncthreads();  // slab e is whole, and the other slab's readers (frame e - 1) are done
+    const bool more = e + 1 < n_env;
+    if (more)
+      s.load(pb, FRAME ? nullptr : in + (e + 1) * in_ld, FRAME ? frames + (long long)(e + 1) * IW * IW * CIN : nullptr);
+    if (co < cout)
+      act_conv_pixels_t<KJ, NCHW, IW, CIN>(cout, pb, co, wv, bias, xs + (e & 1) * Slab::STRIDE, out + e * out_ld);
+    if (more) s.store(xs + ((e + 1) & 1) * Slab::STRIDE);
+  }
+}
+
 // y[o] = b[o] + W[o][0:K] . x for x in LDS: one wave task per output row,
 // k = lane + 64 j (coalesced row reads, KJ loads in flight per batch)
 template <int KJ>
@@ -203,6 +335,48 @@ __device__ __forceinline__ void act_dense(int nout, int K, const float* __restri
     }
     acc = wave_sum(acc);
     if (lane == 0) y[o] = acc + (b ? b[o] : 0.f);
+  }
+}
+
+// act_dense for up to NE input rows at once (xs + r * xld, outputs y + r * yld;
+// bit r of `rows` set = row r is live): the output row's weights are loaded
+// once and stay in registers while every live input row accumulates against
+// them -- per input row the same k order and reduction as act_dense, so the
+// same bits.
+template <int KJ, int NE>
+__device__ __forceinline__ void act_dense_rows(int nout, int K, const float* __restrict__ W, long long ldw,
+                                               const float* __restrict__ b, const float* xs, int xld, float* y,
+                                               long long yld, unsigned rows, int gw, int nw) {
+  const int lane = threadIdx.x & 63;
+  for (int o = gw; o < nout; o += nw) {
+    const float* wr = W + (long long)o * ldw;
+    float acc[NE];
+#pragma unroll
+    for (int r = 0; r < NE; ++r) acc[r] = 0.f;
+    for (int k0 = 0; k0 < K; k0 += 64 * KJ) {
+      float wv[KJ];
+#pragma unroll
+      for (int j = 0; j < KJ; ++j) {
+        const int k = k0 + lane + 64 * j;
+        wv[j] = k < K ? wr[k] : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < NE; ++r) {
+        if (!((rows >> r) & 1u)) continue;
+#pragma unroll
+        for (int j = 0; j < KJ; ++j) {
+          const int k = k0 + lane + 64 * j;
+          acc[r] = fmaf(wv[j], k < K ? xs[r * xld + k] : 0.f, acc[r]);
+        }
+      }
+    }
+    const float bias = b ? b[o] : 0.f;
+#pragma unroll
+    for (int r = 0; r < NE; ++r) {
+      if (!((rows >> r) & 1u)) continue;
+      const float v = wave_sum(acc[r]);
+      if (lane == 0) y[r * yld + o] = v + bias;
+    }
   }
 }
 
@@ -281,6 +455,133 @@ __device__ __forceinline__ void act_rows(int n, int K, const float* __restrict__
   y[t] = acc + b[t];
 }
 
+// element j of h' from the GRU pre-activations (torch gru_cell order r, z, n)
+__device__ __forceinline__ float act_gru_gates(const float* gi, const float* gh, int Hd, int j, float hv) {
+  const float rr = 1.0f / (1.0f + expf(-(gh[j] + gi[j])));
+  const float uu = 1.0f / (1.0f + expf(-(gh[Hd + j] + gi[Hd + j])));
+  const float nn = tanhf(gi[2 * Hd + j] + gh[2 * Hd + j] * rr);
+  return (hv - nn) * uu + nn;
+}
+
+// One wave, one latent group of one row: SiLU(LN(pre1)), the group's C
+// latent_mapper.3 logits and the categorical sampler.  q: the row's explicit
+// Exp(1) variates [R][C] or NULL (Philox keyed by `row`); z_out / logits_out:
+// the row's [R][C].  Uses xs[0, 1280).
+__device__ __forceinline__ void act_latent_group(const dr_dims& d, const dr_world_model& wm, const float* pre1, int grp,
+                                                 const float* q, const unsigned long long* rng, int stream, int row,
+                                                 float* z_out, float* logits_out, float* xs) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int C = d.cols;
+  float* x1 = xs + wave * 256;
+  float* lgs = xs + 1024 + wave * 64;
+  act_ln_silu(pre1, d.enc_hidden, wm.map1.w, wm.map1.b, x1);
+  // the group's C logits: the weights (k = lane + 64 j) of 16 rows per batch
+  float xv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) xv[j] = lane + 64 * j < d.enc_hidden ? x1[lane + 64 * j] : 0.f;
+  float mylg = 0.f;
+  for (int u0 = 0; u0 < C; u0 += 16) {
+    float wv[16][4];
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = lane + 64 * j;
+        wv[u][j] = (u0 + u < C && k < d.enc_hidden) ? wm.map3.w[(long long)(grp * C + u0 + u) * d.enc_hidden + k] : 0.f;
+      }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc = fmaf(wv[u][j], xv[j], acc);
+      acc = wave_sum(acc);
+      if (lane == u0 + u) mylg = acc;
+    }
+  }
+  if (lane < C) lgs[lane] = mylg + wm.map3.b[grp * C + lane];
+  const bool act = lane < C;
+  const float lg = act ? lgs[lane] : -INFINITY;
+  if (act && logits_out) logits_out[grp * C + lane] = lg;
+  // softmax, 1% unimix, argmax(p_hat / Exp(1)), straight-through one-hot (VAE.py:88-98)
+  const float mx = wave_max(lg);
+  const float ex = act ? expf(lg - mx) : 0.f;
+  const float se = wave_sum(ex);
+  const float p = ex / se;
+  const float pu = act ? 0.99f * p + (float)(0.01 * (1.0 / C)) : 0.f;
+  const float sp = wave_sum(pu);
+  const float ph = pu / sp;
+  float qv = 1.0f;
+  if (act) {
+    if (q) qv = q[(long long)grp * C + lane];
+    else qv = dr_exp1(rng, (uint32_t)stream, (uint32_t)row, (uint32_t)(grp * C + lane));
+  }
+  float best = act ? ph / qv : -INFINITY;
+  int bi = act ? lane : 0x7fffffff;
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) {
+      best = ob;
+      bi = oi;
+    }
+  }
+  if (act) z_out[grp * C + lane] = (lane == bi) ? ((1.0f + pu) - pu) : 0.0f;
+}
+
+// One workgroup, one row's actor tail: LN-SiLU, base_net.3, LN-SiLU, the mu /
+// log_sigma heads, tanh(mu + eps sigma) (Agent.py:191-210).  eps: the row's
+// explicit N(0,1) variates [A] or NULL (Philox stream `stream`, keyed by
+// `row`).  Uses xs[0, 3072 + 2 A).
+__device__ __forceinline__ void act_actor_tail(const dr_dims& d, const dr_actor& ac, const float* prea, int det,
+                                               const float* eps, const unsigned long long* rng, int stream, int row,
+                                               float* a_out, float* mu_out, float* sig_out, float* xs) {
+  const int wave = threadIdx.x >> 6;
+  const int a1 = d.actor_h1, a2 = d.actor_h2, A = d.action;
+  float* x1 = xs;          // SiLU(LN(pre1))
+  float* p2 = xs + 1024;   // base_net.3 output
+  float* x2 = xs + 2048;   // SiLU(LN(p2))
+  if (wave == 0) act_ln_silu(prea, a1, ac.n1.w, ac.n1.b, x1);
+  __syncthreads();
+  act_rows<25>(a2, a1, ac.l3.w, ac.l3.b, x1, p2);
+  __syncthreads();
+  if (wave == 0) act_ln_silu(p2, a2, ac.n4.w, ac.n4.b, x2);
+  __syncthreads();
+  float* hd = xs + 3072;  // [mu (A) | log_sigma (A)]
+  for (int o = wave; o < 2 * A; o += ACT_NT / 64) {
+    const int lane = threadIdx.x & 63;
+    const float* hw = o < A ? ac.mu.w : ac.ls.w;
+    const float* hb = o < A ? ac.mu.b : ac.ls.b;
+    const int oo = o < A ? o : o - A;
+    float wv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wv[j] = lane + 64 * j < a2 ? hw[(long long)oo * a2 + lane + 64 * j] : 0.f;
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = fmaf(wv[j], lane + 64 * j < a2 ? x2[lane + 64 * j] : 0.f, acc);
+    acc = wave_sum(acc);
+    if (lane == 0) hd[o] = acc + hb[oo];
+  }
+  __syncthreads();
+  if (threadIdx.x < A) {
+    const int i = threadIdx.x;
+    const float muv = hd[i];
+    const float ls = fminf(fmaxf(hd[A + i], -5.0f), 2.0f);
+    const float sg = dr_softplus(ls) + 1e-3f;
+    float av;
+    if (det) {
+      av = tanhf(muv);
+    } else {
+      float e;
+      if (eps) e = eps[i];
+      else e = dr_normal(rng, (uint32_t)stream, (uint32_t)row, (uint32_t)i);
+      av = tanhf(muv + e * sg);
+    }
+    a_out[i] = av;
+    mu_out[i] = muv;
+    sig_out[i] = sg;
+  }
+}
+
 __global__ __launch_bounds__(ACT_NT) void k_act_step(ActArgs ga) {
   __shared__ ActArgs a;
   __shared__ int s_ok;
@@ -316,13 +617,7 @@ __global__ __launch_bounds__(ACT_NT) void k_act_step(ActArgs ga) {
     const int gt = blockIdx.x * ACT_NT + threadIdx.x;
     for (int j = gt; j < Hd; j += ACT_NB * ACT_NT) {
       const float hv = a.h[j];
-      float hn = hv;
-      if (a.has_prev) {
-        const float rr = 1.0f / (1.0f + expf(-(a.gh[j] + a.gi[j])));
-        const float uu = 1.0f / (1.0f + expf(-(a.gh[Hd + j] + a.gi[Hd + j])));
-        const float nn = tanhf(a.gi[2 * Hd + j] + a.gh[2 * Hd + j] * rr);
-        hn = (hv - nn) * uu + nn;
-      }
+      const float hn = a.has_prev ? act_gru_gates(a.gi, a.gh, Hd, j, hv) : hv;
       a.hn[j] = hn;
       a.h_out[j] = hn;
     }
@@ -345,65 +640,9 @@ __global__ __launch_bounds__(ACT_NT) void k_act_step(ActArgs ga) {
   if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
   ACT_TS(a, 5);
   // ---- stage 6: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per latent group ----
-  if (ok && gw < R) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float* x1 = xs + wave * 256;
-    float* lgs = xs + 1024 + wave * 64;
-    act_ln_silu(a.pre1, d.enc_hidden, a.wm.map1.w, a.wm.map1.b, x1);
-    const int grp = gw;
-    // the group's C logits: the weights (k = lane + 64 j) of 16 rows per batch
-    float xv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xv[j] = lane + 64 * j < d.enc_hidden ? x1[lane + 64 * j] : 0.f;
-    float mylg = 0.f;
-    for (int u0 = 0; u0 < C; u0 += 16) {
-      float wv[16][4];
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int k = lane + 64 * j;
-          wv[u][j] = (u0 + u < C && k < d.enc_hidden)
-                         ? a.wm.map3.w[(long long)(grp * C + u0 + u) * d.enc_hidden + k] : 0.f;
-        }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = fmaf(wv[u][j], xv[j], acc);
-        acc = wave_sum(acc);
-        if (lane == u0 + u) mylg = acc;
-      }
-    }
-    if (lane < C) lgs[lane] = mylg + a.wm.map3.b[grp * C + lane];
-    const bool act = lane < C;
-    const float lg = act ? lgs[lane] : -INFINITY;
-    if (act && a.logits_out) a.logits_out[grp * C + lane] = lg;
-    // softmax, 1% unimix, argmax(p_hat / Exp(1)), straight-through one-hot (VAE.py:88-98)
-    const float mx = wave_max(lg);
-    const float ex = act ? expf(lg - mx) : 0.f;
-    const float se = wave_sum(ex);
-    const float p = ex / se;
-    const float pu = act ? 0.99f * p + (float)(0.01 * (1.0 / C)) : 0.f;
-    const float sp = wave_sum(pu);
-    const float ph = pu / sp;
-    float qv = 1.0f;
-    if (act) {
-      if (a.noise.q) qv = a.noise.q[(long long)grp * C + lane];
-      else qv = dr_exp1(a.noise.rng, (uint32_t)a.noise.stream, (uint32_t)a.noise.row0, (uint32_t)(grp * C + lane));
-    }
-    float best = act ? ph / qv : -INFINITY;
-    int bi = act ? lane : 0x7fffffff;
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ob > best || (ob == best && oi < bi)) {
-        best = ob;
-        bi = oi;
-      }
-    }
-    if (act) a.z_out[grp * C + lane] = (lane == bi) ? ((1.0f + pu) - pu) : 0.0f;
-  }
+  if (ok && gw < R)
+    act_latent_group(d, a.wm, a.pre1, gw, a.noise.q, a.noise.rng, a.noise.stream, a.noise.row0, a.z_out,
+                     a.logits_out, xs);
   if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
   ACT_TS(a, 6);
   // ---- stage 7: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
@@ -447,51 +686,8 @@ __global__ __launch_bounds__(ACT_NT) void k_act_step(ActArgs ga) {
   }
   // ---- stage 8 (workgroup 0): LN-SiLU, base_net.3, LN-SiLU, mu / log_sigma heads, tanh(mu + eps sigma) ----
   if (blockIdx.x != 0) return;
-  const int wave = threadIdx.x >> 6;
-  const int a1 = d.actor_h1, a2 = d.actor_h2;
-  float* x1 = xs;          // SiLU(LN(pre1))
-  float* p2 = xs + 1024;   // base_net.3 output
-  float* x2 = xs + 2048;   // SiLU(LN(p2))
-  if (wave == 0) act_ln_silu(a.prea, a1, a.ac.n1.w, a.ac.n1.b, x1);
-  __syncthreads();
-  act_rows<25>(a2, a1, a.ac.l3.w, a.ac.l3.b, x1, p2);
-  __syncthreads();
-  if (wave == 0) act_ln_silu(p2, a2, a.ac.n4.w, a.ac.n4.b, x2);
-  __syncthreads();
-  float* hd = xs + 3072;  // [mu (A) | log_sigma (A)]
-  for (int o = wave; o < 2 * A; o += ACT_NT / 64) {
-    const int lane = threadIdx.x & 63;
-    const float* hw = o < A ? a.ac.mu.w : a.ac.ls.w;
-    const float* hb = o < A ? a.ac.mu.b : a.ac.ls.b;
-    const int oo = o < A ? o : o - A;
-    float wv[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wv[j] = lane + 64 * j < a2 ? hw[(long long)oo * a2 + lane + 64 * j] : 0.f;
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = fmaf(wv[j], lane + 64 * j < a2 ? x2[lane + 64 * j] : 0.f, acc);
-    acc = wave_sum(acc);
-    if (lane == 0) hd[o] = acc + hb[oo];
-  }
-  __syncthreads();
-  if (threadIdx.x < A) {
-    const int i = threadIdx.x;
-    const float muv = hd[i];
-    const float ls = fminf(fmaxf(hd[A + i], -5.0f), 2.0f);
-    const float sg = dr_softplus(ls) + 1e-3f;
-    float av;
-    if (a.det) {
-      av = tanhf(muv);
-    } else {
-      float e;
-      if (a.noise.eps) e = a.noise.eps[i];
-      else e = dr_normal(a.noise.rng, (uint32_t)(a.noise.stream + 1), (uint32_t)a.noise.row0, (uint32_t)i);
-      av = tanhf(muv + e * sg);
-    }
-    a.a_out[i] = av;
-    a.mu_out[i] = muv;
-    a.sig_out[i] = sg;
-  }
+  act_actor_tail(d, a.ac, a.prea, a.det, a.noise.eps, a.noise.rng, a.noise.stream + 1, a.noise.row0, a.a_out,
+                 a.mu_out, a.sig_out, xs);
   ACT_TS(a, 15);
 }
 
@@ -517,6 +713,16 @@ static void act_carve(char* base, const dr_dims* d, ActArgs& a, size_t& off) {
   a.prea = (float*)take(4 * d->actor_h1);
 }
 
+// the stage helpers' register batches (KJ) and the LDS staging are sized for the
+// CarRacing encoder (Dreamer.py:20-64 config); other shapes use the unfused calls
+static bool act_dims_ok(const dr_dims* d) {
+  const int F = 4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = d->rows * d->cols;
+  return (d->enc_depth == 0 || d->enc_depth == 4) && d->img_h == 64 && d->img_w == 64 && d->enc_f1 == 32 &&
+         d->enc_f2 == 64 && F + d->hidden <= 64 * 74 && L + d->action <= 64 * 17 && d->hidden <= 64 * 10 &&
+         d->hidden + L <= 64 * 26 && d->cols <= 64 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden <= 256 &&
+         d->actor_h1 <= 256 && d->actor_h2 <= 1024 && d->action <= 64;
+}
+
 extern "C" size_t dr_act_step_workspace_bytes(const dr_dims* d) {
   ActArgs a;
   size_t off = 0;
@@ -532,13 +738,7 @@ extern "C" int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_
   DR_REQUIRE(d && wm && ac && frame && h && z_out && h_out && a_out && mu_out && sigma_out && ws, "null argument");
   DR_REQUIRE(!has_prev || (z_prev && a_prev), "has_prev needs z_prev and a_prev");
   DR_REQUIRE(d->obs_dim == 0, "dr_act_step: pixel observations only (vector observations use the unfused path)");
-  const int F = 4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = d->rows * d->cols;
-  // the stage helpers' register batches (KJ) and the LDS staging are sized for the
-  // CarRacing encoder (Dreamer.py:20-64 config); other shapes use the unfused calls
-  if (!((d->enc_depth == 0 || d->enc_depth == 4) && d->img_h == 64 && d->img_w == 64 && d->enc_f1 == 32 &&
-        d->enc_f2 == 64 && F + d->hidden <= 64 * 74 && L + d->action <= 64 * 17 && d->hidden <= 64 * 10 &&
-        d->hidden + L <= 64 * 26 && d->cols <= 64 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden <= 256 &&
-        d->actor_h1 <= 256 && d->actor_h2 <= 1024 && d->action <= 64)) {
+  if (!act_dims_ok(d)) {
     dr_set_error("dr_act_step: dims outside the batch-1 acting kernel (64x64 frames, encoder 32/64 filters, widths "
                  "<= the staging)");
     return DR_E_UNSUPPORTED;
@@ -597,4 +797,317 @@ extern "C" int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_
   a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
   hipLaunchKernelGGL(k_act_step, dim3(ACT_NB), dim3(ACT_NT), ACT_LDS * 4, s, a);
   return dr_check_launch("act_step");
+}
+
+// ---------------------------------------------------------------------------
+// Batched acting: the same step for n_env <= DR_ACT_MAX_ENVS environments in
+// one launch (vectorised rollout_policy / evaluate_agent).  Same grid, same
+// barrier and the same stage helpers as k_act_step; what changes is that a
+// wave keeps its weight row in registers while the rows of the batch pass
+// through it:
+//   conv stages   the workgroup's (pixel block, 4 channels) of every frame in
+//                 turn, slab restaged per frame (act_conv_rows)
+//   dense stages  up to NE rows' inputs side by side in LDS, NE accumulators
+//                 per wave (act_dense_rows); where a stage has at most half as
+//                 many output rows as the grid has waves (latent_mapper.0,
+//                 actor base_net.0) the batch is split over the two halves of
+//                 the grid
+//   sampler       one wave per (row, latent group)
+//   actor tail    row e in workgroup e
+// Every row keeps the one-row kernel's summation order, so its outputs are
+// the bits dr_act_step gives on that row's inputs, whatever n_env is.
+struct alignas(16) ActBatchArgs {
+  dr_dims d;
+  dr_world_model wm;
+  dr_actor ac;
+  const unsigned char* frames;  // [n_env][H][W][3] u8
+  const unsigned char* first;   // [n_env]: 1 = episode start (h' = 0)
+  int n_env, det;
+  const float *z_prev, *h, *a_prev;  // [n_env][L], [n_env][hidden], [n_env][A]
+  dr_noise noise;
+  float *z_out, *h_out, *a_out, *mu_out, *sig_out, *logits_out;
+  int* status;
+  // workspace (c1 ... prea: one copy per row)
+  unsigned* bar;
+  float *c1, *c2, *c3, *c4, *gi, *gh, *hn, *pre1, *prea;
+  int* fail;
+  int spin_limit;
+  long long* ts;
+};
+
+#define ACT_NW (ACT_NB * (ACT_NT / 64))
+// a dense stage with at most ACT_NW / 2 output rows runs as two halves of the grid, each on half the batch
+__host__ __device__ inline int act_dense_splits(int nout) { return 2 * nout <= ACT_NW ? 2 : 1; }
+
+// y[e][o] = b[o] + W[o] . x_e for the rows e of the batch not in `skip`, in
+// chunks of NE rows: stage_row(dst, e) puts x_e (K floats) into LDS
+template <int KJ, int NE, typename StageRow>
+__device__ __forceinline__ void act_dense_batch(int n_env, unsigned skip, int nout, int K, const float* __restrict__ W,
+                                                const float* __restrict__ b, float* xs, float* y, long long yld,
+                                                StageRow stage_row) {
+  const int nsp = act_dense_splits(nout), bps = ACT_NB / nsp, sp = blockIdx.x / bps;
+  const int per = (n_env + nsp - 1) / nsp, lo = sp * per, hi = min(n_env, lo + per);
+  const int gw = (blockIdx.x - sp * bps) * (ACT_NT / 64) + (threadIdx.x >> 6), nw = bps * (ACT_NT / 64);
+  for (int e0 = lo; e0 < hi; e0 += NE) {
+    unsigned rows = 0;
+    for (int r = 0; r < NE && e0 + r < hi; ++r)
+      if (!((skip >> (e0 + r)) & 1u)) rows |= 1u << r;
+    if (!rows) continue;  // (uniform over the workgroup)
+    __syncthreads();      // the previous readers of xs are done
+#pragma unroll
+    for (int r = 0; r < NE; ++r)
+      if ((rows >> r) & 1u) stage_row(xs + r * K, e0 + r);
+    __syncthreads();
+    act_dense_rows<KJ, NE>(nout, K, W, K, b, xs, K, y + e0 * yld, yld, rows, gw, nw);
+  }
+}
+
+template <int NE>
+__global__ __launch_bounds__(ACT_NT) void k_act_batch(ActBatchArgs ga) {
+  __shared__ ActBatchArgs a;
+  __shared__ int s_ok;
+  __shared__ unsigned s_first;  // bit e: row e starts an episode
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  static_assert(sizeof(ActBatchArgs) / 16 <= ACT_NT, "argument copy");
+  if (threadIdx.x < sizeof(ActBatchArgs) / 16)
+    reinterpret_cast<int4*>(&a)[threadIdx.x] = reinterpret_cast<const int4*>(&ga)[threadIdx.x];
+  if (threadIdx.x == 0) {
+    unsigned m = 0;
+    for (int e = 0; e < ga.n_env; ++e)
+      if (ga.first[e]) m |= 1u << e;
+    s_first = m;
+  }
+  __syncthreads();
+  const dr_dims& d = a.d;
+  const int N = a.n_env;
+  const unsigned first = s_first;
+  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6);
+  const int Hd = d.hidden, R = d.rows, C = d.cols, L = R * C, A = d.action;
+  const int c1 = d.enc_f1, c2 = d.enc_f2, c3 = 2 * c2, c4 = 4 * c2;
+  const int H0 = d.img_h, W0 = d.img_w, F = c4 * (H0 / 16) * (W0 / 16);
+  const long long p1 = (long long)(H0 / 2) * (W0 / 2);
+  const long long n1 = p1 * c1, n2 = p1 / 4 * c2, n3 = p1 / 16 * c3, n4 = p1 / 64 * c4;  // == F
+  unsigned round = 0;
+  bool ok = true;
+  ACT_TS(a, 0);
+
+  // ---- stage 1: GRU pre-activations of the continuing rows  ||  conv1 from the frames ----
+  act_dense_batch<17, NE>(N, first, 3 * Hd, L + A, a.wm.w_ih, a.wm.b_ih, xs, a.gi, 3 * Hd, [&](float* dst, int e) {
+    act_stage<5>(dst, L + A, [&](int i) { return i < L ? a.z_prev[(long long)e * L + i] : a.a_prev[e * A + i - L]; });
+  });
+  act_dense_batch<10, NE>(N, first, 3 * Hd, Hd, a.wm.w_hh, a.wm.b_hh, xs, a.gh, 3 * Hd, [&](float* dst, int e) {
+    act_stage<3>(dst, Hd, [&](int i) { return a.h[e * Hd + i]; });
+  });
+  // (map shapes as template arguments: act_dims_ok admits only 64 x 64 frames and 32 / 64 filters)
+  act_conv_rows<1, true, false, 64, 3>(N, c1, nullptr, 0, a.frames, a.wm.conv[0].w, a.wm.conv[0].b, a.c1, n1, xs);
+  ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 1);
+  // ---- stage 2: conv2  ||  GRU gates; h' = 0 at an episode start ----
+  if (ok) {
+    const int gt = blockIdx.x * ACT_NT + threadIdx.x;
+    for (int i = gt; i < N * Hd; i += ACT_NB * ACT_NT) {
+      const int e = i / Hd, j = i - e * Hd;
+      const float hn = ((first >> e) & 1u) ? 0.f : act_gru_gates(a.gi + e * 3 * Hd, a.gh + e * 3 * Hd, Hd, j, a.h[i]);
+      a.hn[i] = hn;
+      a.h_out[i] = hn;
+    }
+    act_conv_rows<8, false, false, 32, 32>(N, c2, a.c1, n1, nullptr, a.wm.conv[1].w, a.wm.conv[1].b, a.c2, n2, xs);
+  }
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 2);
+  if (ok)
+    act_conv_rows<16, false, false, 16, 64>(N, c3, a.c2, n2, nullptr, a.wm.conv[2].w, a.wm.conv[2].b, a.c3, n3, xs);
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 3);
+  if (ok)
+    act_conv_rows<32, false, true, 8, 128>(N, c4, a.c3, n3, nullptr, a.wm.conv[3].w, a.wm.conv[3].b, a.c4, n4, xs);
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 4);
+  // ---- stage 5: latent_mapper.0 on cat(features, h') (VAE.py:73) ----
+  if (ok)
+    act_dense_batch<25, NE>(N, 0u, d.enc_hidden, F + Hd, a.wm.map0.w, a.wm.map0.b, xs, a.pre1, d.enc_hidden,
+                            [&](float* dst, int e) {
+                              act_stage<19>(dst, F + Hd,
+                                            [&](int i) { return i < F ? a.c4[e * n4 + i] : a.hn[e * Hd + i - F]; });
+                            });
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 5);
+  // ---- stage 6: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per (row, latent group) ----
+  if (ok)
+    for (int t = gw; t < N * R; t += ACT_NW) {
+      const int e = t / R, grp = t - e * R;
+      act_latent_group(d, a.wm, a.pre1 + e * d.enc_hidden, grp, a.noise.q ? a.noise.q + (long long)e * L : nullptr,
+                       a.noise.rng, a.noise.stream, a.noise.row0 + e, a.z_out + (long long)e * L,
+                       a.logits_out ? a.logits_out + (long long)e * L : nullptr, xs);
+    }
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 6);
+  // ---- stage 7: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
+  if (ok)
+    act_dense_batch<26, NE>(N, 0u, d.actor_h1, Hd + L, a.ac.l0.w, a.ac.l0.b, xs, a.prea, d.actor_h1,
+                            [&](float* dst, int e) {
+                              act_stage<7>(dst, Hd + L, [&](int i) {
+                                return i < Hd ? a.hn[e * Hd + i] : a.z_out[(long long)e * L + i - Hd];
+                              });
+                            });
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 7);
+  // Failure path as k_act_step: a timed-out barrier raises the status word and
+  // every failing workgroup writes NaN to all five outputs of every row after
+  // its own writes; the workgroups that run a tail re-read the shared flag.
+  if (blockIdx.x < N) {  // (uniform over the workgroup)
+    __shared__ int s_fail;
+    if (threadIdx.x == 0) s_fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_fail) ok = false;
+  }
+  if (!ok) {
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int i = threadIdx.x; i < N * A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * L; i += ACT_NT) a.z_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * Hd; i += ACT_NT) a.h_out[i] = qnan;
+    return;
+  }
+  // ---- stage 8: row e's actor tail in workgroup e ----
+  if (blockIdx.x >= N) return;
+  const int e = blockIdx.x;
+  act_actor_tail(d, a.ac, a.prea + e * d.actor_h1, a.det, a.noise.eps ? a.noise.eps + e * A : nullptr, a.noise.rng,
+                 a.noise.stream + 1, a.noise.row0 + e, a.a_out + e * A, a.mu_out + e * A, a.sig_out + e * A, xs);
+  ACT_TS(a, 15);
+}
+
+static void act_batch_carve(char* base, const dr_dims* d, int n_env, ActBatchArgs& a, size_t& off) {
+  auto take = [&](size_t bytes) {
+    const size_t o = (off + 255) & ~(size_t)255;
+    off = o + bytes;
+    return base ? base + o : nullptr;
+  };
+  const size_t n = (size_t)n_env;
+  const int c1 = d->enc_f1, c2 = d->enc_f2;
+  const size_t p1 = (size_t)(d->img_h / 2) * (d->img_w / 2);
+  a.ts = (long long*)take(16 * sizeof(long long));  // first, as in dr_act_step's workspace
+  a.bar = (unsigned*)take(ACT_BAR_BYTES);
+  a.fail = (int*)take(256);
+  a.c1 = (float*)take(4 * n * p1 * c1);
+  a.c2 = (float*)take(4 * n * (p1 / 4) * c2);
+  a.c3 = (float*)take(4 * n * (p1 / 16) * 2 * c2);
+  a.c4 = (float*)take(4 * n * (p1 / 64) * 4 * c2);
+  a.gi = (float*)take(4 * n * 3 * d->hidden);
+  a.gh = (float*)take(4 * n * 3 * d->hidden);
+  a.hn = (float*)take(4 * n * d->hidden);
+  a.pre1 = (float*)take(4 * n * d->enc_hidden);
+  a.prea = (float*)take(4 * n * d->actor_h1);
+}
+
+extern "C" size_t dr_act_batch_workspace_bytes(const dr_dims* d, int n_env) {
+  if (!d || n_env < 1) return 0;
+  ActBatchArgs a;
+  size_t off = 0;
+  act_batch_carve(nullptr, d, n_env, a, off);
+  return off;
+}
+
+// rows a wave accumulates at once (the instantiation): the batch rounded up to a power of two, at most 8
+static int act_batch_ne(int n_env) { return n_env <= 1 ? 1 : n_env <= 2 ? 2 : n_env <= 4 ? 4 : 8; }
+
+// floats of dynamic LDS: the conv slab, or the widest dense stage's chunk of input rows
+static size_t act_batch_lds(const dr_dims* d, int n_env) {
+  const int ne = act_batch_ne(n_env);
+  const size_t F = (size_t)4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = (size_t)d->rows * d->cols;
+  auto chunk = [&](int nout) {
+    const int nsp = act_dense_splits(nout), per = (n_env + nsp - 1) / nsp;
+    return (size_t)(per < ne ? per : ne);
+  };
+  size_t n = ACT_BATCH_CONV_LDS;
+  auto need = [&](size_t v) { n = v > n ? v : n; };
+  need(chunk(3 * d->hidden) * (L + d->action));
+  need(chunk(3 * d->hidden) * d->hidden);
+  need(chunk(d->enc_hidden) * (F + d->hidden));
+  need(chunk(d->actor_h1) * (d->hidden + L));
+  return n;
+}
+// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_dims_ok admits
+#define ACT_BATCH_LDS_MAX (8 * 64 * 74 * 4)
+
+extern "C" int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int n_env,
+                            const unsigned char* frames, const unsigned char* first, const float* z_prev,
+                            const float* h, const float* a_prev, dr_noise noise, int deterministic, float* z_out,
+                            float* h_out, float* a_out, float* mu_out, float* sigma_out, float* logits_out,
+                            int* status, void* ws, size_t ws_bytes, hipStream_t s) {
+  DR_REQUIRE(n_env >= 1, "n_env < 1");
+  DR_REQUIRE(d && wm && ac && frames && first && z_prev && h && a_prev && z_out && h_out && a_out && mu_out &&
+                 sigma_out && ws,
+             "null argument");
+  if (n_env > DR_ACT_MAX_ENVS) {
+    dr_set_error("dr_act_batch: n_env above DR_ACT_MAX_ENVS");
+    return DR_E_UNSUPPORTED;
+  }
+  if (d->obs_dim != 0 || !act_dims_ok(d)) {
+    dr_set_error("dr_act_batch: dims outside the acting kernel (pixel observations, 64x64 frames, encoder 32/64 "
+                 "filters, widths <= the staging)");
+    return DR_E_UNSUPPORTED;
+  }
+  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
+  const bool force_timeout = force && strcmp(force, "timeout") == 0;
+  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
+  ActBatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.d = *d;
+  a.wm = *wm;
+  a.ac = *ac;
+  a.frames = frames;
+  a.first = first;
+  a.n_env = n_env;
+  a.det = deterministic;
+  a.z_prev = z_prev;
+  a.h = h;
+  a.a_prev = a_prev;
+  a.noise = noise;
+  a.z_out = z_out;
+  a.h_out = h_out;
+  a.a_out = a_out;
+  a.mu_out = mu_out;
+  a.sig_out = sigma_out;
+  a.logits_out = logits_out;
+  a.status = status;
+  size_t off = 0;
+  act_batch_carve((char*)ws, d, n_env, a, off);
+  DR_REQUIRE(off <= ws_bytes, "workspace too small");
+  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(a.bar), 0.f, s));
+  const int ne = act_batch_ne(n_env);
+  const void* fn = ne == 1   ? (const void*)k_act_batch<1>
+                   : ne == 2 ? (const void*)k_act_batch<2>
+                   : ne == 4 ? (const void*)k_act_batch<4>
+                             : (const void*)k_act_batch<8>;
+  const size_t lds = act_batch_lds(d, n_env) * 4;
+  DR_REQUIRE(lds <= ACT_BATCH_LDS_MAX, "stage input beyond the LDS budget");
+  // co-residency as dr_act_step, per batch size: the occupancy query is made
+  // with the dynamic LDS this n_env launches (up to 147 KiB: one workgroup per CU)
+  static int resident_ok[DR_ACT_MAX_ENVS + 1][64];  // 0 unknown, 1 ok, -1 too small (idempotent, benign race)
+  int dev = 0;
+  DR_TRY_HIP(hipGetDevice(&dev));
+  DR_REQUIRE(dev >= 0 && dev < 64, "device index");
+  if (resident_ok[n_env][dev] == 0) {
+    DR_TRY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ACT_BATCH_LDS_MAX));
+    int per_cu = 0, cus = 0;
+    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ACT_NT, lds));
+    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    resident_ok[n_env][dev] = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
+  }
+  if (resident_ok[n_env][dev] != 1 || force_nonres) {
+    dr_set_error("dr_act_batch: the device cannot hold the acting grid co-resident");
+    return DR_E_UNSUPPORTED;
+  }
+  a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
+  switch (ne) {
+    case 1: hipLaunchKernelGGL(k_act_batch<1>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    case 2: hipLaunchKernelGGL(k_act_batch<2>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    case 4: hipLaunchKernelGGL(k_act_batch<4>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    default: hipLaunchKernelGGL(k_act_batch<8>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+  }
+  return dr_check_launch("act_batch");
 }

@@ -107,6 +107,7 @@ class Dreamer(nn.Module):
         self.agent_obs = None
         self.agent_hidden = None
         self.agent_latent = None
+        self.vec_obs = self.vec_hidden = self.vec_latent = None  # rollout_policy_vec's per-env state
         self._engine = None
         self.world = None  # (rank, size, group) for data-parallel train_Agent
 
@@ -357,14 +358,158 @@ class Dreamer(nn.Module):
         # the status word travels back with the step (4 bytes behind the kernel);
         # _act_sync / act_check raise on a timed-out grid barrier
         st["status_host"].copy_(st["status"], non_blocking=True)
+        self._act_last = st
         self._act_ev = torch.cuda.Event()
         self._act_ev.record()
         return a2, mu, sg, z2, h2
 
     def act_check(self):
-        """Wait for the last act_step and raise if its one-launch kernel hit a
-        grid-barrier timeout (its outputs are then NaN, never a state)."""
+        """Wait for the last act_step / act_step_batch and raise if its
+        one-launch kernel hit a grid-barrier timeout (its outputs are then NaN,
+        never a state)."""
         self._act_sync()
+
+    # ------------------------------------------- acting (N environments, HIP)
+    # Batch sizes at which act_step_batch runs the one-launch dr_act_batch:
+    # those where it beat both the batched unfused launches and N sequential
+    # act_step calls by more than the run-to-run spread
+    # (profiles/act_batch_timing.txt, DESIGN.md section 5b): measured at N =
+    # 1, 2, 4 and 8; at N = 16 the unfused launches are faster, and 9 ... 15
+    # were not measured, so they go with 16.  At the other sizes the faster of
+    # the other two runs (ACT_BATCH_SEQUENTIAL_N: the sizes where that is the
+    # sequential one -- none: the unfused launches cost about the same at
+    # every N, below two act_step calls).
+    ACT_BATCH_FUSED_N = frozenset(range(1, 9))
+    ACT_BATCH_SEQUENTIAL_N = frozenset()
+    # None: dispatch by the table; "fused" / "unfused" / "sequential": that path (tests, timing)
+    act_batch_path = None
+
+    def _act_batch_route(self, N):
+        fusable = not (self.world_model.vector_obs or N > L.DR_ACT_MAX_ENVS
+                       or getattr(self, "_act_batch_unsupported", False))
+        want = self.act_batch_path
+        if want is None:
+            want = "fused" if N in self.ACT_BATCH_FUSED_N else (
+                "sequential" if N in self.ACT_BATCH_SEQUENTIAL_N else "unfused")
+        if want == "fused" and not fusable:
+            want = "unfused"
+        if want == "sequential" and self.world_model.vector_obs:
+            want = "unfused"
+        return want
+
+    def act_step_batch(self, observations, state=None, first=None, deterministic=False):
+        """One env step of N environments at once.  observations: (N, H, W, 3)
+        uint8; state: the (z, h, a) this method returned for the previous step
+        (None: every row starts an episode); first: bool [N], True = that row
+        starts an episode (h' = 0, its state row is ignored and may be stale);
+        default all True without state, all False with it.  Per row the
+        semantics (and, on the one-launch path, the bits) of act_step.
+        Returns (a', mu, sigma, z', h') shaped (N, 1, ...).
+
+        Runs dr_act_batch (one launch) at the batch sizes in ACT_BATCH_FUSED_N;
+        otherwise, for vector observations, the deeper VAE, N >
+        DR_ACT_MAX_ENVS or a device that cannot hold the grid, the batched
+        unfused launches (_act_step_batch_unfused) or N act_step calls."""
+        dev = self.device
+        L.require_gpu(torch.empty(0, device=dev))
+        observations = np.asarray(observations)
+        N = observations.shape[0]
+        if N < 1:
+            raise ValueError("act_step_batch needs at least one environment")
+        if first is None:
+            first = np.ones(N, dtype=bool) if state is None else np.zeros(N, dtype=bool)
+        first = np.asarray(first, dtype=bool).reshape(N)
+        if state is None and not first.all():
+            raise ValueError("act_step_batch: a row that continues an episode needs the previous state")
+        route = self._act_batch_route(N)
+        if route == "unfused":
+            return self._act_step_batch_unfused(observations, state, first, deterministic)
+        if route == "sequential":
+            return self._act_step_batch_sequential(observations, state, first, deterministic)
+        d = self.world_model.dims(self.agent)
+        self.agent._ensure_flat()
+        R, C = self.latent_state_dims
+        A, Hd = self.action_dims, self.hidden_state_dims
+        bufs = self.__dict__.setdefault("_act_batch_bufs", {})
+        st = bufs.get(N)
+        if st is None:
+            H_, W_ = self.observation_dims
+            nf = N * H_ * W_ * 3
+            st = bufs[N] = dict(
+                nf=nf,
+                pin=torch.empty(nf + N, dtype=torch.uint8).pin_memory(),  # the frames, then the first flags
+                dev=torch.empty(nf + N, dtype=torch.uint8, device=dev),
+                z0=torch.zeros(N, R * C, device=dev), h0=torch.zeros(N, Hd, device=dev),
+                a0=torch.zeros(N, A, device=dev),
+                status=torch.zeros(1, dtype=torch.int32, device=dev),
+                status_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                ws=torch.empty(L.query("dr_act_batch_workspace_bytes", d, N), dtype=torch.uint8, device=dev))
+        self._act_sync()  # the previous step's copy out of the pinned staging buffer has run (and it was ok)
+        nf = st["nf"]
+        pin = st["pin"].numpy()
+        pin[:nf] = observations.reshape(-1)
+        pin[nf:] = first
+        st["dev"].copy_(st["pin"], non_blocking=True)
+        if state is None:
+            zp, hp, ap = st["z0"], st["h0"], st["a0"]
+        else:
+            zp, hp, ap = (t.reshape(N, -1).float().contiguous() for t in state)
+        z2 = torch.empty(N, 1, R, C, device=dev)
+        h2 = torch.empty(N, 1, Hd, device=dev)
+        a2, mu, sg = (torch.empty(N, 1, A, device=dev) for _ in range(3))
+        try:
+            L.call("dr_act_batch", d, self.world_model.packed(), self.agent.actor_struct(), N, L.ptr(st["dev"]),
+                   L.ptr(st["dev"]) + nf, L.ptr(zp), L.ptr(hp), L.ptr(ap), hip.adhoc(dev).noise(),
+                   int(deterministic), L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu), L.ptr(sg), None,
+                   L.ptr(st["status"]), L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
+        except L.HipError as e:
+            if e.code != L.DR_E_UNSUPPORTED:
+                raise
+            # the device cannot hold the grid, or the widths are not the kernel's (e.g. the 5-layer VAE)
+            self._act_batch_unsupported = True
+            return self._act_step_batch_unfused(observations, state, first, deterministic)
+        st["status_host"].copy_(st["status"], non_blocking=True)
+        self._act_last = st
+        self._act_ev = torch.cuda.Event()
+        self._act_ev.record()
+        return a2, mu, sg, z2, h2
+
+    def _act_step_batch_unfused(self, observations, state, first, deterministic):
+        """act_step_batch through the batched launches that exist: dr_gru_cell,
+        dr_encoder_features + dr_observe_scan (Encoder.encode) and dr_actor_act
+        on N rows, h' = where(first, 0, GRU(...))."""
+        dev = self.device
+        wm = self.world_model
+        N = observations.shape[0]
+        if wm.vector_obs:
+            obs = torch.as_tensor(np.asarray(observations, dtype=np.float32), device=dev).view(N, 1, -1)
+        else:
+            u8 = torch.from_numpy(np.ascontiguousarray(observations, dtype=np.uint8)).to(dev)
+            obs = (u8.permute(0, 3, 1, 2).float() / 255.0 - 0.5).unsqueeze(1).contiguous()
+        h2 = torch.zeros(N, 1, self.hidden_state_dims, device=dev)
+        if state is not None and not first.all():
+            z, h, a = state
+            hg = wm.sequence_model(z.reshape(N, 1, -1), h.reshape(N, 1, -1), a.reshape(N, 1, -1))
+            h2 = torch.where(torch.from_numpy(first).to(dev).view(N, 1, 1), h2, hg.reshape(N, 1, -1))
+        z2, _ = wm.encoder.encode(h2, obs)
+        a2, mu, sg = self.agent.actor.act(h2, z2, deterministic=deterministic)
+        return a2, mu, sg, z2, h2
+
+    def _act_step_batch_sequential(self, observations, state, first, deterministic):
+        """act_step_batch as N act_step calls (explicit noise is handed on row by row)."""
+        R, C = self.latent_state_dims
+        ov = hip._override[-1] if hip._override else None
+        rows = []
+        for e in range(observations.shape[0]):
+            s = (None, None, None) if first[e] else tuple(t[e] for t in state)
+            if ov is None:
+                rows.append(self.act_step(observations[e], *s, deterministic=deterministic))
+                continue
+            q, eps = ov
+            with hip.noise_override(q=None if q is None else q.reshape(-1, R, C)[e].contiguous(),
+                                    eps=None if eps is None else eps.reshape(-1, self.action_dims)[e].contiguous()):
+                rows.append(self.act_step(observations[e], *s, deterministic=deterministic))
+        return tuple(torch.cat(ts, dim=0) for ts in zip(*rows))
 
     def _act_step_unfused(self, observation, z, h, a, deterministic):
         """The same step through the unfused HIP launches -- dr_gru_cell,
@@ -402,12 +547,13 @@ class Dreamer(nn.Module):
         if ev is None:
             return
         ev.synchronize()
-        st = self._act_bufs
+        st = self._act_last  # the buffers of the step the event follows (act_step's, or act_step_batch's for its N)
         if int(st["status_host"][0]) != 0:
             st["status"].zero_()
             st["status_host"].zero_()
             self._act_ev = None
-            raise RuntimeError("dr_act_step: a grid barrier timed out (the acting grid was not co-resident, e.g. "
+            name = "dr_act_batch" if "nf" in st else "dr_act_step"
+            raise RuntimeError(f"{name}: a grid barrier timed out (the acting grid was not co-resident, e.g. "
                                "beside a long-running kernel); that step's outputs are NaN")
 
     def rollout_policy(self, env, random_policy=False):  # Dreamer.py:177-226
@@ -462,17 +608,113 @@ class Dreamer(nn.Module):
                 rewards.append(total)
         return torch.tensor(rewards, dtype=torch.float32, device=self.device).mean()
 
+    def rollout_policy_vec(self, envs, random_policy=False):
+        """rollout_policy over a list of environments stepped in lockstep for
+        sequence_length steps, the device work of each step one act_step_batch.
+        Per-env state (agent observation, latent, hidden) is kept between
+        calls.  First call: env e is reset with seed self.seed + e, then
+        self.seed += N - 1.  On done, in env-index order: self.seed += 1, reset
+        with it, and that row starts an episode on the next step.
+
+        After the S steps the transitions go into the ring through
+        add_to_buffer as N consecutive blocks of S -- env 0's steps, then env
+        1's, ... -- so every block is one env's contiguous stream.  A sampled
+        window that crosses a block boundary joins two envs' streams, the same
+        way the reference's windows already join two episodes across a done."""
+        N = len(envs)
+        with torch.no_grad():
+            if self.vec_obs is None or len(self.vec_obs) != N:
+                frames = [env.reset(seed=self.seed + e)[0] for e, env in enumerate(envs)]
+                self.seed += N - 1
+                self.vec_obs = [self._agent_obs(o) for o in frames]
+                _, _, _, self.vec_latent, self.vec_hidden = self.act_step_batch(np.stack(frames))
+            action = None
+            if not random_policy:  # the current actor's actions for the current states
+                action, _, _ = self.agent.actor.act(self.vec_hidden, self.vec_latent, deterministic=False)
+            blocks = [[] for _ in range(N)]
+            for _ in range(self.sequence_length):
+                if random_policy:
+                    action_np = np.stack([np.asarray(env.action_space.sample(), dtype=np.float32) for env in envs])
+                    action = torch.tensor(action_np, dtype=torch.float32, device=self.device).view(N, 1, -1)
+                else:
+                    action_np = action.detach().cpu().numpy().reshape(N, -1)
+                    self.act_check()
+                frames, first = [], np.zeros(N, dtype=bool)
+                for e, env in enumerate(envs):
+                    observation_, reward, terminated, truncated, _ = env.step(action_np[e])
+                    done = terminated or truncated
+                    blocks[e].append((self._buffer_obs(self.vec_obs[e]), action_np[e], reward, 1 - done))
+                    if done:
+                        self.seed += 1
+                        observation_, _ = env.reset(seed=self.seed)
+                        first[e] = True
+                    frames.append(observation_)
+                    self.vec_obs[e] = self._agent_obs(observation_)
+                action, _, _, self.vec_latent, self.vec_hidden = self.act_step_batch(
+                    np.stack(frames), (self.vec_latent, self.vec_hidden, action), first)
+            for block in blocks:
+                for transition in block:
+                    self.buffer.add_to_buffer(*transition)
+
+    def evaluate_agent_vec(self, envs, eval_episodes):
+        """evaluate_agent with len(envs) episodes in flight: eval_episodes
+        deterministic episodes seeded self.seed + 1 ... self.seed +
+        eval_episodes in the order they start (the first len(envs) together; an
+        env that finishes takes the next seed and its row starts an episode).
+        An env with no episode left drops out of the batch.  Returns the mean
+        total reward (taken in episode order) as a device scalar."""
+        totals = [0] * eval_episodes
+        with torch.no_grad():
+            slots = []  # [env, episode index] in flight
+            for env in envs[:eval_episodes]:
+                self.seed += 1
+                slots.append([env, len(slots)])
+            started = len(slots)
+            frames = [env.reset(seed=self.seed - started + 1 + ep)[0] for env, ep in slots]
+            state, first = None, np.ones(len(slots), dtype=bool)
+            while slots:
+                action, _, _, latent, hidden = self.act_step_batch(np.stack(frames), state, first, deterministic=True)
+                action_np = action.detach().cpu().numpy().reshape(len(slots), -1)
+                self.act_check()
+                keep, frames, first = [], [], []
+                for i, slot in enumerate(slots):
+                    env, ep = slot
+                    observation_, reward, terminated, truncated, _ = env.step(action_np[i])
+                    totals[ep] += reward
+                    if not (terminated or truncated):
+                        first.append(False)
+                    elif started < eval_episodes:
+                        self.seed += 1
+                        observation_, _ = env.reset(seed=self.seed)
+                        slot[1] = started
+                        started += 1
+                        first.append(True)
+                    else:
+                        continue
+                    keep.append(i)
+                    frames.append(observation_)
+                slots = [slots[i] for i in keep]
+                first = np.asarray(first, dtype=bool)
+                if slots:
+                    idx = torch.tensor(keep, device=self.device)
+                    state = tuple(t.index_select(0, idx) for t in (latent, hidden, action))
+        return torch.tensor(totals, dtype=torch.float32, device=self.device).mean()
+
     def train_dreamer(self, env, eval_env):  # Dreamer.py:324-372
+        """A list or tuple of environments in either position selects the
+        vectorised methods (rollout_policy_vec / evaluate_agent_vec) for it."""
+        rollout = self.rollout_policy_vec if isinstance(env, (list, tuple)) else self.rollout_policy
+        evaluate = self.evaluate_agent_vec if isinstance(eval_env, (list, tuple)) else self.evaluate_agent
         WM_loss_list, actor_loss_list, critic_loss_list, evaluation_list = [], [], [], []
         print("Starting Training...")
         print("Starting Random Kickstart.")
         for _ in tqdm(range(self.random_iterations), desc="Kickstarting Dreamer Agent.", leave=True):
-            self.rollout_policy(env, random_policy=True)
+            rollout(env, random_policy=True)
             WM_loss_list.append([x.detach().cpu().item() for x in self.train_world_model()])
         print("Starting Training Loop...")
-        evaluation_list.append(self.evaluate_agent(eval_env, eval_episodes=3).detach().cpu().item())
+        evaluation_list.append(evaluate(eval_env, eval_episodes=3).detach().cpu().item())
         for it in tqdm(range(self.training_iterations), desc="Training Dreamer Agent.", leave=True):
-            self.rollout_policy(env, random_policy=False)
+            rollout(env, random_policy=False)
             wm_loss = self.train_world_model()
             actor_loss, critic_loss = self.train_Agent()
             WM_loss_list.append([x.detach().cpu().item() for x in wm_loss])
@@ -488,9 +730,9 @@ class Dreamer(nn.Module):
                          critic_loss=_sanitize_for_save(critic_loss_list),
                          rewards=_sanitize_for_save(evaluation_list))
             if it % 500 == 0:
-                evaluation_list.append(self.evaluate_agent(eval_env, eval_episodes=3).detach().cpu().item())
+                evaluation_list.append(evaluate(eval_env, eval_episodes=3).detach().cpu().item())
         print("Training Complete.")
-        evaluation_list.append(self.evaluate_agent(eval_env, eval_episodes=10).detach().cpu().item())
+        evaluation_list.append(evaluate(eval_env, eval_episodes=10).detach().cpu().item())
         return WM_loss_list, actor_loss_list, critic_loss_list, evaluation_list
 
     def Run(self, env, env_seed, render=True):  # Dreamer.py:374-401

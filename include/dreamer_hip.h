@@ -247,6 +247,32 @@ int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_actor* acto
                 int has_prev, const float* z_prev, const float* h, const float* a_prev, dr_noise noise,
                 int deterministic, float* z_out, float* h_out, float* a_out, float* mu_out, float* sigma_out,
                 float* logits_out, int* status, void* ws, size_t ws_bytes, hipStream_t stream);
+/* The same step for n_env <= DR_ACT_MAX_ENVS environments in ONE launch
+ * (vectorised rollout_policy / evaluate_agent; the reference drives one env,
+ * Dreamer.py:177-226, 295-322).  Per row e, dr_act_step's semantics: if
+ * first[e], h'_e = 0 (episode start, Dreamer.py:186-187, 222) and row e of
+ * z_prev / h / a_prev is not read (it may be stale); otherwise h'_e =
+ * GRU(z_prev_e, h_e, a_prev_e) (observe_step, WorldModel.py:79-82).  Then
+ * z'_e = Encoder.encode(h'_e, frame_e) (VAE.py:57-99) and a_e = Actor.act(h'_e,
+ * z'_e, deterministic) (Agent.py:202-210).
+ * frames [n_env][H][W][3] u8 and first [n_env] u8 on the device; states and
+ * outputs are row-major [n_env][...].  Noise: explicit q [n_env*R][C] and eps
+ * [n_env][A]; Philox draws row e as dr_act_step would with row0 + e (sampler
+ * stream `noise.stream`, actor `noise.stream + 1`).  Row e's outputs depend on
+ * row e's inputs and noise alone and are the bits dr_act_step gives on them.
+ * h / h_out, z_prev / z_out and a_prev / a_out may alias.
+ * DR_E_UNSUPPORTED: n_env > DR_ACT_MAX_ENVS, the dims dr_act_step rejects, or
+ * a device that cannot hold the grid (checked per n_env with the dynamic LDS
+ * that batch launches).  DR_E_INVALID: n_env < 1, null pointers.
+ * status and DREAMER_ACT_FORCE as dr_act_step: after a barrier timeout status
+ * is 1 and all five outputs of every row hold NaN. */
+#define DR_ACT_MAX_ENVS 16
+size_t dr_act_batch_workspace_bytes(const dr_dims* d, int n_env);
+int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr_actor* actor, int n_env,
+                 const unsigned char* frames, const unsigned char* first, const float* z_prev, const float* h,
+                 const float* a_prev, dr_noise noise, int deterministic, float* z_out, float* h_out, float* a_out,
+                 float* mu_out, float* sigma_out, float* logits_out, int* status, void* ws, size_t ws_bytes,
+                 hipStream_t stream);
 
 /* GRU cell (SequenceModel.py:19-24) */
 int dr_gru_cell(const dr_dims* d, const dr_world_model* wm, int B, const float* z, const float* h,
