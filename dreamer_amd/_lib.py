@@ -109,6 +109,9 @@ _SIGS = {
     "dr_act_batch_workspace_bytes": (_sz, [_P(dr_dims), _i]),
     "dr_act_batch": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, fp, fp, fp, fp, fp, dr_noise, _i,
                           fp, fp, fp, fp, fp, fp, fp, fp, _sz, fp]),
+    "dr_act_vec_workspace_bytes": (_sz, [_P(dr_dims), _i]),
+    "dr_act_vec": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, fp, fp, fp, fp, fp, dr_noise, _i,
+                        fp, fp, fp, fp, fp, fp, fp, fp, _sz, fp]),
     "dr_gru_cell": (_i, [_P(dr_dims), _P(dr_world_model), _i, fp, fp, fp, fp, fp, _sz, fp]),
     "dr_categorical_sample": (_i, [_i, _i, _i, fp, dr_noise, fp, fp, fp, fp]),
     "dr_mlp3_fwd": (_i, [_P(dr_mlp3), _i, _i, fp, _ll, _i, fp, _ll, _i, _i, _i, fp, _ll, fp, _sz, fp]),
@@ -173,7 +176,8 @@ def load():
 
 # include/dreamer_hip.h error codes
 DR_E_INVALID, DR_E_HIP, DR_E_WORKSPACE, DR_E_UNSUPPORTED = 1001, 1002, 1003, 1004
-DR_ACT_MAX_ENVS = 16  # include/dreamer_hip.h: rows of one dr_act_batch launch
+DR_ACT_MAX_ENVS = 16  # include/dreamer_hip.h: rows of one dr_act_batch / dr_act_vec launch
+DR_ACT_VEC_MAX_OBS = 1023  # include/dreamer_hip.h: widest observation vector dr_act_vec takes
 
 
 class HipError(RuntimeError):

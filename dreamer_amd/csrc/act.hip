@@ -1111,3 +1111,288 @@ extern "C" int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr
   }
   return dr_check_launch("act_batch");
 }
+
+// ---------------------------------------------------------------------------
+// Acting on vector observations (dr_dims.obs_dim = D > 0, BASELINE configs[4])
+// in one launch, for n_env = 1 ... DR_ACT_MAX_ENVS rows.  The encoder's four
+// conv stages are two small dense layers (conv[0] = Linear(D, F) + SiLU,
+// conv[1] = Linear(F, F) + SiLU, F = 4 * enc_f2), which overlap
+// the two GRU stages, so the step takes five barrier rounds instead of eight.
+// Every dense stage is act_dense_batch (per row the one-row summation order: k
+// = lane + 64 j, j ascending, then wave_sum), so a row's outputs are the same
+// bits for every n_env, row position and mix of first flags; n_env = 1 is the
+// batch-1 step (no separate kernel).  A layer's SiLU is applied where the next
+// stage stages its input into LDS.  Same grid, barrier, sampler, actor tail and
+// failure path as k_act_batch.
+struct alignas(16) ActVecArgs {
+  dr_dims d;
+  dr_world_model wm;
+  dr_actor ac;
+  const float* obs;            // [n_env][obs_dim] f32
+  const unsigned char* first;  // [n_env]: 1 = episode start (h' = 0)
+  int n_env, det;
+  const float *z_prev, *h, *a_prev;  // [n_env][L], [n_env][hidden], [n_env][A]
+  dr_noise noise;
+  float *z_out, *h_out, *a_out, *mu_out, *sig_out, *logits_out;
+  int* status;
+  // workspace (y0 ... prea: one copy per row)
+  unsigned* bar;
+  float *y0, *y1, *gi, *gh, *hn, *pre1, *prea;  // y0, y1: the encoder layers' pre-activations [F]
+  int* fail;
+  int spin_limit;
+  long long* ts;
+};
+
+__device__ __forceinline__ float act_silu(float v) { return v / (1.0f + expf(-v)); }
+
+template <int NE>
+__global__ __launch_bounds__(ACT_NT) void k_act_vec(ActVecArgs ga) {
+  __shared__ ActVecArgs a;
+  __shared__ int s_ok;
+  __shared__ unsigned s_first;  // bit e: row e starts an episode
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  static_assert(sizeof(ActVecArgs) / 16 <= ACT_NT, "argument copy");
+  if (threadIdx.x < sizeof(ActVecArgs) / 16)
+    reinterpret_cast<int4*>(&a)[threadIdx.x] = reinterpret_cast<const int4*>(&ga)[threadIdx.x];
+  if (threadIdx.x == 0) {
+    unsigned m = 0;
+    for (int e = 0; e < ga.n_env; ++e)
+      if (ga.first[e]) m |= 1u << e;
+    s_first = m;
+  }
+  __syncthreads();
+  const dr_dims& d = a.d;
+  const int N = a.n_env;
+  const unsigned first = s_first;
+  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6);
+  const int Hd = d.hidden, R = d.rows, C = d.cols, L = R * C, A = d.action;
+  const int D = d.obs_dim, F = 4 * d.enc_f2;
+  unsigned round = 0;
+  bool ok = true;
+  ACT_TS(a, 0);
+
+  // ---- stage 1: GRU pre-activations of the continuing rows  ||  encoder layer 0, y0 = W0 x + b0 ----
+  act_dense_batch<17, NE>(N, first, 3 * Hd, L + A, a.wm.w_ih, a.wm.b_ih, xs, a.gi, 3 * Hd, [&](float* dst, int e) {
+    act_stage<5>(dst, L + A, [&](int i) { return i < L ? a.z_prev[(long long)e * L + i] : a.a_prev[e * A + i - L]; });
+  });
+  act_dense_batch<10, NE>(N, first, 3 * Hd, Hd, a.wm.w_hh, a.wm.b_hh, xs, a.gh, 3 * Hd, [&](float* dst, int e) {
+    act_stage<3>(dst, Hd, [&](int i) { return a.h[e * Hd + i]; });
+  });
+  act_dense_batch<4, NE>(N, 0u, F, D, a.wm.conv[0].w, a.wm.conv[0].b, xs, a.y0, F, [&](float* dst, int e) {
+    act_stage<2>(dst, D, [&](int i) { return a.obs[(long long)e * D + i]; });
+  });
+  ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 1);
+  // ---- stage 2: GRU gates; h' = 0 at an episode start  ||  encoder layer 1, y1 = W1 SiLU(y0) + b1 ----
+  if (ok) {
+    const int gt = blockIdx.x * ACT_NT + threadIdx.x;
+    for (int i = gt; i < N * Hd; i += ACT_NB * ACT_NT) {
+      const int e = i / Hd, j = i - e * Hd;
+      const float hn = ((first >> e) & 1u) ? 0.f : act_gru_gates(a.gi + e * 3 * Hd, a.gh + e * 3 * Hd, Hd, j, a.h[i]);
+      a.hn[i] = hn;
+      a.h_out[i] = hn;
+    }
+    act_dense_batch<4, NE>(N, 0u, F, F, a.wm.conv[1].w, a.wm.conv[1].b, xs, a.y1, F, [&](float* dst, int e) {
+      act_stage<1>(dst, F, [&](int i) { return act_silu(a.y0[e * F + i]); });
+    });
+  }
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 2);
+  // ---- stage 3: latent_mapper.0 on cat(SiLU(y1), h') (VAE.py:73) ----
+  if (ok)
+    act_dense_batch<14, NE>(N, 0u, d.enc_hidden, F + Hd, a.wm.map0.w, a.wm.map0.b, xs, a.pre1, d.enc_hidden,
+                            [&](float* dst, int e) {
+                              act_stage<4>(dst, F + Hd, [&](int i) {
+                                return i < F ? act_silu(a.y1[e * F + i]) : a.hn[e * Hd + i - F];
+                              });
+                            });
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 3);
+  // ---- stage 4: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per (row, latent group) ----
+  if (ok)
+    for (int t = gw; t < N * R; t += ACT_NW) {
+      const int e = t / R, grp = t - e * R;
+      act_latent_group(d, a.wm, a.pre1 + e * d.enc_hidden, grp, a.noise.q ? a.noise.q + (long long)e * L : nullptr,
+                       a.noise.rng, a.noise.stream, a.noise.row0 + e, a.z_out + (long long)e * L,
+                       a.logits_out ? a.logits_out + (long long)e * L : nullptr, xs);
+    }
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 4);
+  // ---- stage 5: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
+  if (ok)
+    act_dense_batch<26, NE>(N, 0u, d.actor_h1, Hd + L, a.ac.l0.w, a.ac.l0.b, xs, a.prea, d.actor_h1,
+                            [&](float* dst, int e) {
+                              act_stage<7>(dst, Hd + L, [&](int i) {
+                                return i < Hd ? a.hn[e * Hd + i] : a.z_out[(long long)e * L + i - Hd];
+                              });
+                            });
+  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  ACT_TS(a, 5);
+  // Failure path as k_act_batch: a timed-out barrier raises the status word and
+  // every failing workgroup writes NaN to all five outputs of every row after
+  // its own writes; the workgroups that run a tail re-read the shared flag.
+  if (blockIdx.x < N) {  // (uniform over the workgroup)
+    __shared__ int s_fail;
+    if (threadIdx.x == 0) s_fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_fail) ok = false;
+  }
+  if (!ok) {
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int i = threadIdx.x; i < N * A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * L; i += ACT_NT) a.z_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * Hd; i += ACT_NT) a.h_out[i] = qnan;
+    return;
+  }
+  // ---- stage 6: row e's actor tail in workgroup e ----
+  if (blockIdx.x >= N) return;
+  const int e = blockIdx.x;
+  act_actor_tail(d, a.ac, a.prea + e * d.actor_h1, a.det, a.noise.eps ? a.noise.eps + e * A : nullptr, a.noise.rng,
+                 a.noise.stream + 1, a.noise.row0 + e, a.a_out + e * A, a.mu_out + e * A, a.sig_out + e * A, xs);
+  ACT_TS(a, 15);
+}
+
+static void act_vec_carve(char* base, const dr_dims* d, int n_env, ActVecArgs& a, size_t& off) {
+  auto take = [&](size_t bytes) {
+    const size_t o = (off + 255) & ~(size_t)255;
+    off = o + bytes;
+    return base ? base + o : nullptr;
+  };
+  const size_t n = (size_t)n_env, F = (size_t)4 * d->enc_f2;
+  a.ts = (long long*)take(16 * sizeof(long long));  // first, as in dr_act_step's workspace
+  a.bar = (unsigned*)take(ACT_BAR_BYTES);
+  a.fail = (int*)take(256);
+  a.y0 = (float*)take(4 * n * F);
+  a.y1 = (float*)take(4 * n * F);
+  a.gi = (float*)take(4 * n * 3 * d->hidden);
+  a.gh = (float*)take(4 * n * 3 * d->hidden);
+  a.hn = (float*)take(4 * n * d->hidden);
+  a.pre1 = (float*)take(4 * n * d->enc_hidden);
+  a.prea = (float*)take(4 * n * d->actor_h1);
+}
+
+// act_dims_ok's bounds on the widths the shared stages are sized for (register batches KJ, the sampler's and the
+// actor tail's LDS areas), F within the latent_mapper.0 batch (F + hidden <= 64 * 14) and the observation cap; the
+// dense helpers loop over K, so obs_dim need not be a multiple of anything
+static bool act_vec_dims_ok(const dr_dims* d) {
+  const int F = 4 * d->enc_f2, L = d->rows * d->cols;
+  return d->obs_dim >= 1 && d->obs_dim <= DR_ACT_VEC_MAX_OBS && F >= 1 && F <= 256 && d->hidden >= 1 &&
+         L + d->action <= 64 * 17 && d->hidden <= 64 * 10 && d->hidden + L <= 64 * 26 && d->cols >= 1 &&
+         d->cols <= 64 && d->rows >= 1 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden >= 1 &&
+         d->enc_hidden <= 256 && d->actor_h1 >= 1 && d->actor_h1 <= 256 && d->actor_h2 >= 1 && d->actor_h2 <= 1024 &&
+         d->action >= 1 && d->action <= 64;
+}
+
+extern "C" size_t dr_act_vec_workspace_bytes(const dr_dims* d, int n_env) {
+  if (!d || n_env < 1) return 0;
+  ActVecArgs a;
+  size_t off = 0;
+  act_vec_carve(nullptr, d, n_env, a, off);
+  return off;
+}
+
+// floats of dynamic LDS: the widest dense stage's chunk of input rows, and at least what the sampler (1280) and the
+// actor tail (3072 + 2 A) use
+static size_t act_vec_lds(const dr_dims* d, int n_env) {
+  const int ne = act_batch_ne(n_env);
+  const size_t F = (size_t)4 * d->enc_f2, L = (size_t)d->rows * d->cols;
+  auto chunk = [&](int nout) {
+    const int nsp = act_dense_splits(nout), per = (n_env + nsp - 1) / nsp;
+    return (size_t)(per < ne ? per : ne);
+  };
+  size_t n = 3072 + 2 * (size_t)d->action;
+  auto need = [&](size_t v) { n = v > n ? v : n; };
+  need(chunk(3 * d->hidden) * (L + d->action));
+  need(chunk(3 * d->hidden) * d->hidden);
+  need(chunk((int)F) * d->obs_dim);
+  need(chunk((int)F) * F);
+  need(chunk(d->enc_hidden) * (F + d->hidden));
+  need(chunk(d->actor_h1) * (d->hidden + L));
+  return n;
+}
+// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_vec_dims_ok admits
+#define ACT_VEC_LDS_MAX (8 * 64 * 26 * 4)
+static_assert(DR_ACT_VEC_MAX_OBS <= 64 * 26 && 3072 + 2 * 64 <= 8 * 64 * 26, "LDS bound covers every stage");
+
+extern "C" int dr_act_vec(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int n_env, const float* obs,
+                          const unsigned char* first, const float* z_prev, const float* h, const float* a_prev,
+                          dr_noise noise, int deterministic, float* z_out, float* h_out, float* a_out, float* mu_out,
+                          float* sigma_out, float* logits_out, int* status, void* ws, size_t ws_bytes,
+                          hipStream_t s) {
+  DR_REQUIRE(n_env >= 1, "n_env < 1");
+  DR_REQUIRE(d && wm && ac && obs && first && z_prev && h && a_prev && z_out && h_out && a_out && mu_out &&
+                 sigma_out && ws,
+             "null argument");
+  DR_REQUIRE(d->obs_dim != 0, "dr_act_vec: vector observations only (pixel models use dr_act_step / dr_act_batch)");
+  if (n_env > DR_ACT_MAX_ENVS) {
+    dr_set_error("dr_act_vec: n_env above DR_ACT_MAX_ENVS");
+    return DR_E_UNSUPPORTED;
+  }
+  if (!act_vec_dims_ok(d)) {
+    dr_set_error("dr_act_vec: dims outside the acting kernel (obs_dim <= DR_ACT_VEC_MAX_OBS, 4 enc_f2 <= 256, widths "
+                 "<= the staging)");
+    return DR_E_UNSUPPORTED;
+  }
+  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
+  const bool force_timeout = force && strcmp(force, "timeout") == 0;
+  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
+  ActVecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.d = *d;
+  a.wm = *wm;
+  a.ac = *ac;
+  a.obs = obs;
+  a.first = first;
+  a.n_env = n_env;
+  a.det = deterministic;
+  a.z_prev = z_prev;
+  a.h = h;
+  a.a_prev = a_prev;
+  a.noise = noise;
+  a.z_out = z_out;
+  a.h_out = h_out;
+  a.a_out = a_out;
+  a.mu_out = mu_out;
+  a.sig_out = sigma_out;
+  a.logits_out = logits_out;
+  a.status = status;
+  size_t off = 0;
+  act_vec_carve((char*)ws, d, n_env, a, off);
+  DR_REQUIRE(off <= ws_bytes, "workspace too small");
+  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(a.bar), 0.f, s));
+  const int ne = act_batch_ne(n_env);
+  const void* fn = ne == 1   ? (const void*)k_act_vec<1>
+                   : ne == 2 ? (const void*)k_act_vec<2>
+                   : ne == 4 ? (const void*)k_act_vec<4>
+                             : (const void*)k_act_vec<8>;
+  const size_t lds = act_vec_lds(d, n_env) * 4;
+  DR_REQUIRE(lds <= ACT_VEC_LDS_MAX, "stage input beyond the LDS budget");
+  // co-residency as dr_act_batch: per batch size, with the dynamic LDS this n_env launches
+  static int resident_ok[DR_ACT_MAX_ENVS + 1][64];  // 0 unknown, 1 ok, -1 too small (idempotent, benign race)
+  int dev = 0;
+  DR_TRY_HIP(hipGetDevice(&dev));
+  DR_REQUIRE(dev >= 0 && dev < 64, "device index");
+  if (resident_ok[n_env][dev] == 0) {
+    DR_TRY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ACT_VEC_LDS_MAX));
+    int per_cu = 0, cus = 0;
+    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ACT_NT, lds));
+    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    resident_ok[n_env][dev] = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
+  }
+  if (resident_ok[n_env][dev] != 1 || force_nonres) {
+    dr_set_error("dr_act_vec: the device cannot hold the acting grid co-resident");
+    return DR_E_UNSUPPORTED;
+  }
+  a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
+  switch (ne) {
+    case 1: hipLaunchKernelGGL(k_act_vec<1>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    case 2: hipLaunchKernelGGL(k_act_vec<2>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    case 4: hipLaunchKernelGGL(k_act_vec<4>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+    default: hipLaunchKernelGGL(k_act_vec<8>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
+  }
+  return dr_check_launch("act_vec");
+}

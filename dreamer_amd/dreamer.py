@@ -314,10 +314,21 @@ class Dreamer(nn.Module):
         WorldModel.py:79-82); without them, h' = 0 (episode start,
         Dreamer.py:186-187).  Then z' = Encoder.encode(h', observation) and
         a' = Actor.act(h', z', deterministic).  observation: the env's H x W x 3
-        uint8 frame.  Returns (a', mu, sigma, z', h') shaped (1, 1, ...)."""
+        uint8 frame.  Returns (a', mu, sigma, z', h') shaped (1, 1, ...).
+
+        A vector-observation model (observation: D floats) runs the same step
+        as dr_act_vec with one row, where the vector dispatch says fused
+        (ACT_VEC_FUSED_N, act_batch_path)."""
         dev = self.device
         L.require_gpu(torch.empty(0, device=dev))
-        if self.world_model.vector_obs or getattr(self, "_act_unfused", False):
+        if self.world_model.vector_obs:
+            if self._act_batch_route(1) == "fused":
+                out = self._act_vec(np.asarray(observation, dtype=np.float32).reshape(1, -1),
+                                    None if z is None else (z, h, a), np.full(1, z is None), deterministic)
+                if out is not None:
+                    return out
+            return self._act_step_unfused(observation, z, h, a, deterministic)
+        if getattr(self, "_act_unfused", False):
             return self._act_step_unfused(observation, z, h, a, deterministic)
         d = self.world_model.dims(self.agent)
         self.agent._ensure_flat()
@@ -384,10 +395,21 @@ class Dreamer(nn.Module):
     # None: dispatch by the table; "fused" / "unfused" / "sequential": that path (tests, timing)
     act_batch_path = None
 
+    # The same table for vector-observation models (dr_act_vec, which also
+    # serves act_step as N = 1): the sizes where the one-launch kernel beat the
+    # batched unfused launches by more than the spread of the repetitions
+    # (profiles/act_vec_timing.txt) -- measured at N = 1,
+    # 2, 4 and 8; at N = 16 the unfused launches are faster, and 9 ... 15 were
+    # not measured, so they go with 16.
+    ACT_VEC_FUSED_N = frozenset(range(1, 9))
+
     def _act_batch_route(self, N):
-        fusable = not (self.world_model.vector_obs or N > L.DR_ACT_MAX_ENVS
-                       or getattr(self, "_act_batch_unsupported", False))
+        vec = self.world_model.vector_obs
+        fusable = not (N > L.DR_ACT_MAX_ENVS
+                       or getattr(self, "_act_vec_unsupported" if vec else "_act_batch_unsupported", False))
         want = self.act_batch_path
+        if want is None and vec:
+            want = "fused" if N in self.ACT_VEC_FUSED_N else "unfused"
         if want is None:
             want = "fused" if N in self.ACT_BATCH_FUSED_N else (
                 "sequential" if N in self.ACT_BATCH_SEQUENTIAL_N else "unfused")
@@ -406,10 +428,12 @@ class Dreamer(nn.Module):
         semantics (and, on the one-launch path, the bits) of act_step.
         Returns (a', mu, sigma, z', h') shaped (N, 1, ...).
 
-        Runs dr_act_batch (one launch) at the batch sizes in ACT_BATCH_FUSED_N;
-        otherwise, for vector observations, the deeper VAE, N >
-        DR_ACT_MAX_ENVS or a device that cannot hold the grid, the batched
-        unfused launches (_act_step_batch_unfused) or N act_step calls."""
+        Runs dr_act_batch (one launch) at the batch sizes in ACT_BATCH_FUSED_N
+        -- for vector observations ((N, D) floats) dr_act_vec at those in
+        ACT_VEC_FUSED_N; otherwise, for the deeper VAE, N > DR_ACT_MAX_ENVS,
+        an observation vector above DR_ACT_VEC_MAX_OBS or a device that cannot
+        hold the grid, the batched unfused launches (_act_step_batch_unfused)
+        or N act_step calls."""
         dev = self.device
         L.require_gpu(torch.empty(0, device=dev))
         observations = np.asarray(observations)
@@ -422,6 +446,12 @@ class Dreamer(nn.Module):
         if state is None and not first.all():
             raise ValueError("act_step_batch: a row that continues an episode needs the previous state")
         route = self._act_batch_route(N)
+        if route == "fused" and self.world_model.vector_obs:
+            out = self._act_vec(np.asarray(observations, dtype=np.float32).reshape(N, -1), state, first,
+                                deterministic)
+            if out is not None:
+                return out
+            route = "unfused"
         if route == "unfused":
             return self._act_step_batch_unfused(observations, state, first, deterministic)
         if route == "sequential":
@@ -474,6 +504,61 @@ class Dreamer(nn.Module):
         self._act_ev.record()
         return a2, mu, sg, z2, h2
 
+    def _act_vec(self, observations, state, first, deterministic):
+        """N rows of vector observations ((N, D) f32) through dr_act_vec in one
+        launch; act_step is the N = 1 call.  Returns None once the entry point
+        answered DR_E_UNSUPPORTED (observation dim above DR_ACT_VEC_MAX_OBS,
+        widths outside the kernel's, a device that cannot hold the grid): the
+        caller then runs the unfused launches, and so does every later step."""
+        dev = self.device
+        N, D = observations.shape
+        d = self.world_model.dims(self.agent)
+        self.agent._ensure_flat()
+        R, C = self.latent_state_dims
+        A, Hd = self.action_dims, self.hidden_state_dims
+        bufs = self.__dict__.setdefault("_act_vec_bufs", {})
+        st = bufs.get(N)
+        if st is None:
+            nb = 4 * N * D
+            st = bufs[N] = dict(
+                vec=True, nb=nb,
+                pin=torch.empty(nb + N, dtype=torch.uint8).pin_memory(),  # the N x D floats, then the first flags
+                dev=torch.empty(nb + N, dtype=torch.uint8, device=dev),
+                z0=torch.zeros(N, R * C, device=dev), h0=torch.zeros(N, Hd, device=dev),
+                a0=torch.zeros(N, A, device=dev),
+                status=torch.zeros(1, dtype=torch.int32, device=dev),
+                status_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                ws=torch.empty(L.query("dr_act_vec_workspace_bytes", d, N), dtype=torch.uint8, device=dev))
+        self._act_sync()  # the previous step's copy out of the pinned staging buffer has run (and it was ok)
+        nb = st["nb"]
+        pin = st["pin"].numpy()
+        pin[:nb].view(np.float32)[...] = observations.reshape(-1)
+        pin[nb:] = first
+        st["dev"].copy_(st["pin"], non_blocking=True)
+        if state is None:
+            zp, hp, ap = st["z0"], st["h0"], st["a0"]
+        else:
+            zp, hp, ap = (t.reshape(N, -1).float().contiguous() for t in state)
+        z2 = torch.empty(N, 1, R, C, device=dev)
+        h2 = torch.empty(N, 1, Hd, device=dev)
+        a2, mu, sg = (torch.empty(N, 1, A, device=dev) for _ in range(3))
+        try:
+            L.call("dr_act_vec", d, self.world_model.packed(), self.agent.actor_struct(), N, L.ptr(st["dev"]),
+                   L.ptr(st["dev"]) + nb, L.ptr(zp), L.ptr(hp), L.ptr(ap), hip.adhoc(dev).noise(),
+                   int(deterministic), L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu), L.ptr(sg), None,
+                   L.ptr(st["status"]), L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
+        except L.HipError as e:
+            if e.code != L.DR_E_UNSUPPORTED:
+                raise
+            self._act_vec_unsupported = True
+            del bufs[N]
+            return None
+        st["status_host"].copy_(st["status"], non_blocking=True)
+        self._act_last = st
+        self._act_ev = torch.cuda.Event()
+        self._act_ev.record()
+        return a2, mu, sg, z2, h2
+
     def _act_step_batch_unfused(self, observations, state, first, deterministic):
         """act_step_batch through the batched launches that exist: dr_gru_cell,
         dr_encoder_features + dr_observe_scan (Encoder.encode) and dr_actor_act
@@ -514,8 +599,9 @@ class Dreamer(nn.Module):
     def _act_step_unfused(self, observation, z, h, a, deterministic):
         """The same step through the unfused HIP launches -- dr_gru_cell,
         dr_encoder_features + dr_observe_scan (Encoder.encode), dr_actor_act:
-        vector observations (BASELINE configs[4]) and devices that cannot hold
-        dr_act_step's grid co-resident."""
+        devices that cannot hold the one-launch grid co-resident, widths
+        outside dr_act_step's / dr_act_vec's, and vector-observation models
+        where the dispatch says unfused."""
         dev = self.device
         wm = self.world_model
         if wm.vector_obs:
@@ -552,7 +638,7 @@ class Dreamer(nn.Module):
             st["status"].zero_()
             st["status_host"].zero_()
             self._act_ev = None
-            name = "dr_act_batch" if "nf" in st else "dr_act_step"
+            name = "dr_act_vec" if "vec" in st else "dr_act_batch" if "nf" in st else "dr_act_step"
             raise RuntimeError(f"{name}: a grid barrier timed out (the acting grid was not co-resident, e.g. "
                                "beside a long-running kernel); that step's outputs are NaN")
 

@@ -273,6 +273,31 @@ int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr_actor* act
                  const float* a_prev, dr_noise noise, int deterministic, float* z_out, float* h_out, float* a_out,
                  float* mu_out, float* sigma_out, float* logits_out, int* status, void* ws, size_t ws_bytes,
                  hipStream_t stream);
+/* dr_act_batch for vector observations (dr_dims.obs_dim = D > 0): the same step
+ * for n_env = 1 ... DR_ACT_MAX_ENVS environments in ONE launch, the encoder's
+ * convolutions replaced by the MLP of DESIGN.md 2c (conv[0] = Linear(D, F) +
+ * SiLU, conv[1] = Linear(F, F) + SiLU, F = 4*enc_f2 features into
+ * latent_mapper.0 on cat(features, h')).  Per row e: if first[e], h'_e = 0
+ * (episode start, Dreamer.py:186-187, 222) and row e of z_prev / h / a_prev is
+ * not read; otherwise h'_e = GRU(z_prev_e, h_e, a_prev_e) (observe_step,
+ * WorldModel.py:79-82).  Then z'_e = Encoder.encode(h'_e, obs_e) (VAE.py:73-99
+ * past the feature extractor) and a_e = Actor.act(h'_e, z'_e, deterministic)
+ * (Agent.py:202-210).  obs [n_env][obs_dim] f32 and first [n_env] u8 on the
+ * device.  Noise, aliasing, status and DREAMER_ACT_FORCE as dr_act_batch; row
+ * e's outputs depend on row e's inputs and noise alone and are the same bits
+ * for every n_env, row position and mix of first flags (n_env = 1 is the
+ * batch-1 step: there is no separate kernel).
+ * DR_E_INVALID: n_env < 1, null pointers, obs_dim == 0 (pixel models use
+ * dr_act_step / dr_act_batch).  DR_E_UNSUPPORTED: n_env > DR_ACT_MAX_ENVS,
+ * obs_dim > DR_ACT_VEC_MAX_OBS, 4*enc_f2 > 256 or the other widths dr_act_step
+ * bounds, or a device that cannot hold the grid. */
+/* obs_dim < 1024; any D up to it is taken (no multiple-of-4 rule here, unlike dr_encoder_features) */
+#define DR_ACT_VEC_MAX_OBS 1023
+size_t dr_act_vec_workspace_bytes(const dr_dims* d, int n_env);
+int dr_act_vec(const dr_dims* d, const dr_world_model* wm, const dr_actor* actor, int n_env, const float* obs,
+               const unsigned char* first, const float* z_prev, const float* h, const float* a_prev, dr_noise noise,
+               int deterministic, float* z_out, float* h_out, float* a_out, float* mu_out, float* sigma_out,
+               float* logits_out, int* status, void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* GRU cell (SequenceModel.py:19-24) */
 int dr_gru_cell(const dr_dims* d, const dr_world_model* wm, int B, const float* z, const float* h,
