@@ -93,6 +93,9 @@ _SIGS = {
     "dr_imagine_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
     "dr_imagine_fwd": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, _i, fp, fp, dr_noise, _i,
                             fp, fp, fp, fp, fp, fp, fp, fp, fp, _sz, fp]),
+    "dr_imagine_actions_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
+    "dr_imagine_actions": (_i, [_P(dr_dims), _P(dr_world_model), _i, _i, fp, fp, fp, _ll, _ll, dr_noise,
+                                fp, fp, fp, fp, fp, _sz, fp]),
     "dr_imagine_bwd": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, _i, fp, fp, fp, fp, fp,
                             fp, fp, fp, fp, _P(dr_actor), fp, _sz, fp]),
     "dr_imagine_bwd_prep": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, _i, fp, fp, fp, fp, _sz, fp]),
@@ -143,6 +146,7 @@ _SIGS = {
     "dr_wm_train_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
     "dr_decoder_workspace_bytes": (_sz, [_P(dr_dims), _i]),
     "dr_decoder_fwd": (_i, [_P(dr_dims), _P(dr_decoder), _i, fp, _ll, fp, _ll, fp, fp, _sz, fp]),
+    "dr_frame_metrics": (_i, [_P(dr_dims), _i, _i, fp, _P(dr_frames), fp, fp, fp, fp]),
     "dr_wm_train_phase": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_decoder), _i, _i, _P(dr_frames),
                                _P(dr_wm_batch), dr_noise, dr_wm_loss_cfg, _i, fp, _i, fp, fp, _P(dr_world_model),
                                _P(dr_decoder), fp, fp, fp, fp, _sz, fp]),

@@ -502,6 +502,10 @@ extern "C" size_t dr_imagine_workspace_bytes(const dr_dims* d, int B, int H) {
   return c.off;
 }
 
+// the reward / continue heads over all B (H + 1) states (after either unroll)
+static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* latents,
+                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s);
+
 // the unroll as seven launches per step (shapes outside dream.hip, launch_form)
 static int imagine_launch_form(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int B, int H,
                                const dr_noise& noise, const dr_noise& nq, int deterministic, float* latents,
@@ -649,11 +653,16 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
   }
   if (!unrolled) DR_TRY(imagine_launch_form(d, wm, ac, B, H, noise, nq, deterministic, latents, hiddens, actions, mus,
                                             sigmas, tp, w, split_gru, zg, s));
+  return imagine_heads(d, wm, B, H, latents, hiddens, rewards, continues, w, s);
+}
 
-  // RewardPredictor / ContinuePredictor (DynamicsPredictors.py:64-74, 95-105)
-  // on every imagined state (h_{t+1}, z_{t+1}) at once: rows m = b (H+1) + t'
-  // of the contiguous [B][H+1] hiddens / latents (t' = 0 rides along unused);
-  // forward only -- the actor loss takes no gradient through the heads
+// RewardPredictor / ContinuePredictor (DynamicsPredictors.py:64-74, 95-105)
+// on every imagined state (h_{t+1}, z_{t+1}) at once: rows m = b (H+1) + t'
+// of the contiguous [B][H+1] hiddens / latents (t' = 0 rides along unused);
+// forward only -- the actor loss takes no gradient through the heads
+static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* latents,
+                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s) {
+  const int L = latent(d), Hd = d->hidden;
   {
     const int M1 = B * (H + 1);
     GemmArgs p[2];
@@ -707,6 +716,115 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
     DR_TRY(op_copy2d_multi(cj, 2, s));
   }
   return DR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// open-loop prediction: the unroll under given actions (WorldModel.py:72-77
+// per step; no actor, no tape).  Launch form only: imagine_launch_form's
+// per-step chain without its actor launches, the same kernels and the same
+// split_gru / planes rules, then imagine_heads.
+// ---------------------------------------------------------------------------
+struct ImActWs {
+  ImWs w;           // the fields the chain and the heads use (the rest stay NULL)
+  float *p1, *p2;   // the prior's two hidden layers [B][prior_h1], [B][prior_h2]
+};
+static void imact_carve(Carve& c, const dr_dims* d, int B, int H, ImActWs& a) {
+  const long long Bl = B, B1 = (long long)B * (H + 1);
+  const int L = latent(d), Hd = d->hidden, A = d->action;
+  ImWs& w = a.w;
+  memset(&w, 0, sizeof(w));
+  w.gh = c.f(Bl * 3 * Hd);
+  w.wt = c.f((long long)(L + A) * 3 * Hd);
+  w.hid16 = (unsigned short*)c.raw(sizeof(unsigned short) * B1 * Hd);
+  w.s3p0 = c.raw(op_nt_split3_ws_bytes(d->prior_h1, Hd));
+  w.s3whh = c.raw(op_nt_split3_ws_bytes(3 * Hd, Hd));
+  w.idx[0] = c.i(2 * Bl * d->rows);
+  w.idx[1] = c.i(2 * Bl * d->rows);
+  a.p1 = c.f(Bl * d->prior_h1);
+  a.p2 = c.f(Bl * d->prior_h2);
+  w.p1r = c.f(B1 * d->rew_h1);
+  w.p1c = c.f(B1 * d->cont_h1);
+  w.p2r = c.f(B1 * d->rew_h2);
+  w.p2c = c.f(B1 * d->cont_h2);
+  w.rlog = c.f(B1 * d->buckets);
+  w.clog = c.f(B1);
+  w.rval = c.f(B1);
+  w.s3r = c.raw(op_nt_split3_ws_bytes(d->rew_h1, Hd + L));
+  w.s3c = c.raw(op_nt_split3_ws_bytes(d->cont_h1, Hd + L));
+  w.s3part_n = op_gemm_nt_split3_part_floats((int)B1, std::max(d->rew_h1, d->cont_h1));
+  w.s3part = c.f((long long)w.s3part_n);
+}
+
+extern "C" size_t dr_imagine_actions_workspace_bytes(const dr_dims* d, int B, int H) {
+  if (!d || B <= 0 || H <= 0) return 0;
+  Carve c(nullptr);
+  ImActWs a;
+  imact_carve(c, d, B, H, a);
+  return c.off;
+}
+
+extern "C" int dr_imagine_actions(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* z0,
+                                  const float* h0, const float* actions, long long act_sb, long long act_st,
+                                  dr_noise noise, float* latents, float* hiddens, float* rewards, float* continues,
+                                  void* ws, size_t ws_bytes, hipStream_t s) {
+  DR_REQUIRE(d && wm && z0 && h0 && actions && latents && hiddens && rewards && continues && ws && B > 0 && H > 0,
+             "null argument or empty batch");
+  DR_REQUIRE(wm->w_ih && wm->w_hh && wm->b_ih && wm->b_hh, "GRU weights required");
+  GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
+  Carve c(ws);
+  ImActWs a;
+  imact_carve(c, d, B, H, a);
+  WS_CHECK(c, ws_bytes);
+  ImWs& w = a.w;
+  const int L = latent(d), Hd = d->hidden, A = d->action;
+  const long long ldH = (long long)(H + 1) * Hd, ldL = (long long)(H + 1) * L;
+  {
+    const Copy2dJob cj[2] = {{latents, ldL, z0, L, L, B}, {hiddens, ldH, h0, Hd, Hd, B}};
+    DR_TRY(op_copy2d_multi(cj, 2, s));
+  }
+  // dr_imagine_fwd's rules: at B >= 128 the next step's hidden product rides
+  // with the prior's first Linear, on the weight planes where they apply
+  const bool split_gru = B >= 128;
+  const bool planes = split_gru && H > 1 && Hd % 8 == 0;
+  const bool a16 = planes && d->precision == DR_PREC_BF16;
+  DR_TRY(op_transpose(3 * Hd, L + A, wm->w_ih, w.wt, s));
+  DR_TRY(op_onehot_index(B, d->rows, d->cols, latents, ldL, w.idx[0], onehot_vals(w.idx[0], B, d->rows), s));
+  if (planes) {
+    DR_TRY(split_planes(d->prior_h1, Hd, wm->prior.l0.w, Hd, w.s3p0, s));
+    DR_TRY(split_planes(3 * Hd, Hd, wm->w_hh, Hd, w.s3whh, s));
+  }
+  for (int t = 0; t < H; ++t) {
+    float* h_t = hiddens + (long long)t * Hd;
+    float* h_n = hiddens + (long long)(t + 1) * Hd;
+    float* z_t = latents + (long long)t * L;
+    float* z_n = latents + (long long)(t + 1) * L;
+    unsigned short* h_n16 = a16 ? w.hid16 + (long long)(t + 1) * Hd : nullptr;
+    DR_TRY(gru_onehot(d, wm, B, w.idx[t & 1], actions + (long long)t * act_st, act_sb, h_t, ldH, h_n, ldH, w.wt,
+                      nullptr, nullptr, nullptr, nullptr, s, z_t, ldL, w.gh, split_gru && t > 0, h_n16));
+    {
+      GemmArgs p[2];
+      int np = 0;
+      p[np] = lin(B, d->prior_h1, Hd, h_n, ldH, wm->prior.l0.w, Hd, wm->prior.l0.b, a.p1, d->prior_h1);
+      if (planes) wplanes(p[np], w.s3p0);
+      ++np;
+      if (t + 1 < H && split_gru) {
+        p[np] = lin(B, 3 * Hd, Hd, h_n, ldH, wm->w_hh, Hd, wm->b_hh, w.gh, 3 * Hd);
+        if (planes) wplanes(p[np], w.s3whh);
+        ++np;
+      }
+      for (int i = 0; i < np; ++i) {
+        if (!planes) p[i].bf16 = 0;
+        p[i].A16 = h_n16;
+      }
+      DR_TRY(gemm_launch(G_NT, AM_PLAIN, p, np, s));
+    }
+    DR_TRY(run(G_NT, AM_LNSILU, lin_ln(B, d->prior_h2, d->prior_h1, a.p1, d->prior_h1, wm->prior.n1, wm->prior.l3.w,
+                                       wm->prior.l3.b, a.p2, d->prior_h2), s));
+    GemmArgs g = lin_ln(B, L, d->prior_h2, a.p2, d->prior_h2, wm->prior.n4, wm->prior.l6.w, wm->prior.l6.b, nullptr, 0);
+    with_sampler(g, d, noise, t, z_n, ldL, w.idx[(t + 1) & 1], nullptr, 0);
+    DR_TRY(run(G_NT, AM_LNSILU, g, s));
+  }
+  return imagine_heads(d, wm, B, H, latents, hiddens, rewards, continues, w, s);
 }
 
 // part 1 of the backward: upstream state gradients into the workspace and the

@@ -171,6 +171,126 @@ class Dreamer(nn.Module):
                hip.adhoc(dev).noise(), L.ptr(z), L.ptr(h), None, L.ptr(ws2), ws2.numel(), st)
         return z, h
 
+    # ------------------------------------------- world-model evaluation (HIP)
+    def open_loop(self, starts=None, batch_size=None, context=None, horizon=None, sample=True, noise=None,
+                  _mark=None):
+        """Open-loop prediction on replay windows (open_loop.py): filter the
+        first `context` frames of each window (warm_start_generator's scan,
+        Dreamer.py:244-262), roll the prior forward `horizon` steps under the
+        recorded actions (WorldModel.py:72-77), decode states 0..horizon and
+        compare them with what the ring holds.  Returns an OpenLoopResult.
+
+        starts: window starts (default: buffer.sample_start_indices(batch_size
+        or self.batch_size)); context defaults to S // 2 (the warm start's),
+        horizon to min(self.horizon, S - context).  noise: optional pair of
+        explicit Exp(1) draws (q_context (Tc, B*R, C), q (H, B*R, C)), else
+        Philox; sample=False takes the mode of every categorical (q == 1).
+        Frames are read straight from the device ring; everything runs on the
+        current stream without a sync.  _mark: stage hook of
+        tools/open_loop_timing.py (called with the stage's name once it is
+        enqueued)."""
+        from .open_loop import OpenLoopResult, check_lengths
+        from .utils import symlog
+        mark = _mark or (lambda name: None)
+        S = self.sequence_length
+        Tc = S // 2 if context is None else int(context)
+        H = min(self.horizon, S - Tc) if horizon is None else int(horizon)
+        check_lengths(Tc, H, S)
+        buf, wmod = self.buffer, self.world_model
+        dev = buf.device
+        if starts is None:
+            starts = buf.sample_start_indices(batch_size or self.batch_size)
+        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
+            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
+        B = int(st.numel())
+        R, C = self.latent_state_dims
+        A, Hd = self.action_dims, self.hidden_state_dims
+        if noise is not None:
+            q_ctx, q = (t.float().contiguous() for t in noise)
+            if tuple(q_ctx.shape) != (Tc, B * R, C) or tuple(q.shape) != (H, B * R, C):
+                raise ValueError(f"noise must be ({Tc}, {B * R}, {C}) and ({H}, {B * R}, {C})")
+        elif not sample:
+            q_ctx, q = torch.ones(Tc, B * R, C, device=dev), torch.ones(H, B * R, C, device=dev)
+        else:
+            q_ctx = q = None
+        d = wmod.dims(self.agent)
+        wm = wmod.packed()
+        stream = hip.stream()
+        m = buf._mirror()
+        act = torch.empty(B, S, A, device=dev)
+        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
+        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
+               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
+        mark("gather")
+        # posterior after the context frames
+        fr = buf.frames_struct(st)
+        feat = torch.empty(Tc * B, d.enc_hidden, device=dev)
+        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, Tc * B))
+        L.call("dr_encoder_features", d, wm, fr, B, Tc, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
+        mark("encoder")
+        z0, h0 = torch.empty(B, R * C, device=dev), torch.empty(B, Hd, device=dev)
+        nz = hip.explicit_noise(q=q_ctx, device=dev) if q_ctx is not None else hip.adhoc(dev).noise()
+        ws = hip.workspace(dev).get("obs", L.query("dr_observe_workspace_bytes", d, B))
+        L.call("dr_observe_scan", d, wm, B, Tc, L.ptr(feat), L.ptr(act), S * A, A, None, None, nz, L.ptr(z0),
+               L.ptr(h0), None, L.ptr(ws), ws.numel(), stream)
+        mark("scan")
+        # the prior under the recorded actions: action Tc-1+k drives state k -> k+1
+        lat, hid, r, c = wmod._imagine_actions(d, B, H, z0, h0, act.data_ptr() + 4 * (Tc - 1) * A, S * A, A, q)
+        mark("unroll")
+        # decode states 0..H and compare with the ring's frames Tc-1 .. Tc-1+H
+        M = B * (H + 1)
+        vector = buf.vector
+        shape = (d.obs_dim,) if vector else (3, d.img_h, d.img_w)
+        mu = torch.empty(B, H + 1, *shape, device=dev)
+        ws = hip.workspace(dev).get("dec", L.query("dr_decoder_workspace_bytes", d, M))
+        L.call("dr_decoder_fwd", d, wmod.packed_decoder(), M, L.ptr(hid), Hd, L.ptr(lat), R * C, L.ptr(mu), L.ptr(ws),
+               ws.numel(), stream)
+        mark("decoder")
+        sqerr = torch.empty(B, H + 1, device=dev)
+        pred = true = None
+        if not vector:
+            pred = torch.empty(B, H + 1, *shape, dtype=torch.uint8, device=dev)
+            true = torch.empty_like(pred)
+        truth = buf.frames_struct(st)
+        truth.t0 = Tc - 1
+        L.call("dr_frame_metrics", d, B, H + 1, L.ptr(mu), truth, L.ptr(sqerr), L.ptr(pred), L.ptr(true), stream)
+        mark("metrics")
+        sl = slice(Tc - 1, Tc - 1 + H)  # state k = 1..H against window step Tc+k-2
+        return OpenLoopResult(latents=lat, hiddens=hid, mu=mu, frames_pred=pred, frames_true=true, sqerr=sqerr,
+                              reward_pred=symlog(r), reward_true=rew[:, sl].unsqueeze(-1).clone(),
+                              continue_pred=c, continue_true=cont[:, sl].unsqueeze(-1).clone(), context=Tc,
+                              horizon=H)
+
+    def evaluate_world_model(self, batches=1, batch_size=None, context=None, horizon=None, sample=True):
+        """Per-step open-loop error curves averaged over `batches` sampled
+        batches of windows: a dict of CPU float lists -- mse and psnr (length
+        H+1: state 0 is the posterior reconstruction; psnr is None for vector
+        observations), reward_abs_err (symlog space) and continue_bce (length
+        H).  Leaves np.random's state and the Philox {seed, offset} as it
+        found them, so calling it between training iterations does not change
+        the training run."""
+        np_state = np.random.get_state()
+        ar = hip.adhoc(self.device)
+        rng_state, rng_counter = ar.state.clone(), ar.counter
+        try:
+            acc = None
+            with torch.no_grad():
+                for _ in range(int(batches)):
+                    r = self.open_loop(batch_size=batch_size, context=context, horizon=horizon, sample=sample)
+                    cur = [r.mse().mean(0), r.psnr().mean(0) if r.frames_pred is not None else None,
+                           (r.reward_pred - r.reward_true).abs().mean((0, 2)),
+                           torch.nn.functional.binary_cross_entropy(r.continue_pred.clamp(0.0, 1.0), r.continue_true,
+                                                                    reduction="none").mean((0, 2))]
+                    acc = cur if acc is None else [None if a is None else a + b for a, b in zip(acc, cur)]
+        finally:
+            np.random.set_state(np_state)
+            ar.state.copy_(rng_state)
+            ar.counter = rng_counter
+        if acc is None:
+            raise ValueError("evaluate_world_model needs batches >= 1")
+        out = [None if a is None else (a / float(batches)).cpu().tolist() for a in acc]
+        return {"mse": out[0], "psnr": out[1], "reward_abs_err": out[2], "continue_bce": out[3]}
+
     # --------------------------------------------------------------- training
     @property
     def engine(self):

@@ -181,6 +181,42 @@ class WorldModel(nn.Module):
                L.ptr(z2), L.ptr(r), L.ptr(c), L.ptr(ws), ws.numel(), hip.stream())
         return h2, z2, r, c
 
+    def imagine_actions(self, hidden_state, latent_state, actions, noise_q=None, sample=True):
+        """imagine_step (WorldModel.py:72-77) iterated under given actions in
+        one call (dr_imagine_actions): hidden_state (B,1,hidden), latent_state
+        (B,1,R,C), actions (B,H,A); action k drives state k -> k+1.  Returns
+        latents (B,H+1,R,C), hiddens (B,H+1,hidden) (state 0 = the inputs),
+        rewards (B,H,1) and continues (B,H,1) of states 1..H.  noise_q:
+        explicit Exp(1) draws (H, B*R, C) (parity tests), else Philox.
+        sample=False takes the prior's mode: argmax(p_hat / q) with q == 1."""
+        L.require_gpu(hidden_state)
+        B, H = actions.shape[:2]
+        R, C, Hd, A = self.latent_num_rows, self.latent_num_columns, self.hidden_dims, self.action_dims
+        dev = hidden_state.device
+        h = hidden_state.reshape(B, Hd).float().contiguous()
+        z = latent_state.reshape(B, R * C).float().contiguous()
+        a = actions.reshape(B, H, A).float().contiguous()
+        if noise_q is None and not sample:
+            noise_q = torch.ones(H, B * R, C, device=dev)
+        if noise_q is not None:
+            noise_q = noise_q.float().contiguous()
+            if tuple(noise_q.shape) != (H, B * R, C):
+                raise ValueError(f"noise_q must be ({H}, {B * R}, {C}), got {tuple(noise_q.shape)}")
+        out = self._imagine_actions(self.dims(), B, H, z, h, a.data_ptr(), H * A, A, noise_q)
+        return out[0], out[1], out[2], out[3]
+
+    def _imagine_actions(self, d, B, H, z0, h0, act_ptr, act_sb, act_st, noise_q):
+        R, C, Hd = self.latent_num_rows, self.latent_num_columns, self.hidden_dims
+        dev = h0.device
+        lat = torch.empty(B, H + 1, R, C, device=dev)
+        hid = torch.empty(B, H + 1, Hd, device=dev)
+        rew, cont = torch.empty(B, H, 1, device=dev), torch.empty(B, H, 1, device=dev)
+        nz = hip.explicit_noise(q=noise_q, device=dev) if noise_q is not None else hip.adhoc(dev).noise()
+        ws = hip.workspace(dev).get("im_act", L.query("dr_imagine_actions_workspace_bytes", d, B, H))
+        L.call("dr_imagine_actions", d, self.packed(), B, H, L.ptr(z0), L.ptr(h0), act_ptr, act_sb, act_st, nz,
+               L.ptr(lat), L.ptr(hid), L.ptr(rew), L.ptr(cont), L.ptr(ws), ws.numel(), hip.stream())
+        return lat, hid, rew, cont
+
     def observe_step(self, last_latent, last_hidden, last_action, observation):  # WorldModel.py:79-82
         if hip.needs_torch_grad(self.sequence_model, self.encoder):
             return self._observe_step_torch(last_latent, last_hidden, last_action, observation)

@@ -191,6 +191,30 @@ int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const dr_actor* a
                    float* hiddens, float* actions, float* rewards, float* continues, float* mus,
                    float* sigmas, void* tape, void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* ---- open-loop prediction: the same unroll under GIVEN actions (imagine_step
+ *      with a recorded action, WorldModel.py:72-77, iterated as dream_episodes
+ *      iterates it, Dreamer.py:158-164, without the actor) ---------------------
+ * State 0 is (h0, z0) ([B][hidden], [B][R*C]); for k = 1..H
+ *   h_k = GRU(z_{k-1}, a_{k-1}, h_{k-1})  (SequenceModel.py:19-24),
+ *   z_k ~ prior(h_k), draw k-1             (DynamicsPredictors.py:25-39),
+ *   r_k = symexp E[bucket], c_k = sigmoid  (DynamicsPredictors.py:64-74, 95-105)
+ * on (h_k, z_k).  actions element (b, k, i) is at actions[b*act_sb + k*act_st
+ * + i]; entry k drives the step k -> k+1.  Outputs in dr_imagine_fwd's
+ * layouts: latents [B][H+1][R*C], hiddens [B][H+1][hidden], rewards /
+ * continues [B][H] (entry k-1 holds r_k / c_k).  Noise: explicit q
+ * [H][B*R][C] (draw k-1 at step index k-1) or Philox on `noise.stream`.  No
+ * tape, no actor.  Always the launch sequence (per step: fused one-hot GRU;
+ * one grouped launch of the products that read only h_{k+1} -- the prior's
+ * first Linear and, at B >= 128, the next step's hidden product; the prior's
+ * LN-SiLU layer; the sampler head), then the reward / continue heads once over
+ * the B*(H+1) states, the kernels dr_imagine_fwd's launch form runs.  Honours
+ * dr_dims.precision like dr_imagine_fwd. */
+size_t dr_imagine_actions_workspace_bytes(const dr_dims* d, int B, int H);
+int dr_imagine_actions(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* z0, const float* h0,
+                       const float* actions, long long act_sb, long long act_st, dr_noise noise, float* latents,
+                       float* hiddens, float* rewards, float* continues, void* ws, size_t ws_bytes,
+                       hipStream_t stream);
+
 /* Backprop through the unroll for the actor (Agent.py:141-145 backward):
  * given dL/dmus, dL/dsigmas (and optionally dL/dactions, dL/dlatents,
  * dL/dhiddens; NULL = 0), writes dL/d(actor params) into `grad` (overwrite).
@@ -438,6 +462,28 @@ int dr_wm_train_grads(const dr_dims* d, const dr_world_model* wm, const dr_decod
 size_t dr_decoder_workspace_bytes(const dr_dims* d, int M);
 int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, const float* h, long long ldh, const float* z,
                    long long ldz, float* mu, void* ws, size_t ws_bytes, hipStream_t stream);
+
+/* ---- frame metrics: decoded frames against the true ones (the squared error
+ *      of the reconstruction term, WorldModel.py:129, and the u8 frames a
+ *      prediction video shows) -------------------------------------------------
+ * mu [B][T][3][H][W] (pixel models) or [B][T][obs_dim] (vector observations),
+ * as dr_decoder_fwd writes rows m = b*T + t.  `truth` has dr_frames semantics
+ * (t0 included): its frame (b, t) -- the u8 ring + starts, or the f32 form --
+ * is compared with mu[b][t].  The true value is x = (float)u8 / 255.0f - 0.5f
+ * (Dreamer.py:251) for the u8 ring and for f32 frames with raw255; f32 frames
+ * without raw255, and vector rows, are used as stored.
+ *   sqerr[b][t]   = sum over the frame of (mu - x)^2
+ *   pred_u8[b][t] = (u8) min(255, max(0, rintf((mu + 0.5f) * 255.0f))), may be NULL
+ *   true_u8[b][t] = the true frame as u8 (the ring's bytes; an f32 source is
+ *                   quantised like pred_u8), may be NULL
+ * Vector observations have no u8 form: pred_u8 and true_u8 must be NULL
+ * (DR_E_INVALID otherwise), obs_dim <= 1023.
+ * One 256-thread workgroup per frame, no atomics: each thread sums its
+ * elements in ascending order, then a fixed wave reduction and the four wave
+ * sums in wave order -- sqerr of a frame is the same bits at every B, T and
+ * position, and from run to run. */
+int dr_frame_metrics(const dr_dims* d, int B, int T, const float* mu, const dr_frames* truth, float* sqerr,
+                     unsigned char* pred_u8, unsigned char* true_u8, hipStream_t stream);
 
 /* ---- a1  replay gather (Buffer.sample_sequences, Buffer.py:49-61) --------- */
 int dr_replay_gather(long long cap, int B, int S, int frame_elems, int A, const unsigned char* frames,
