@@ -269,6 +269,31 @@ extern "C" size_t dr_observe_workspace_bytes(const dr_dims* d, int B) {
   return c.off;
 }
 
+// Per-step outputs of the launch form (dr_observe_trace): entry t of [B][T][.]
+// arrays (row stride T * width); post_logits may be NULL
+struct ObsTrace {
+  float *latents, *hiddens, *post_logits;
+  float* z_last;  // scratch [B][R*C] and index buffer of a step's last-step form (below)
+  int* idx_last;
+};
+
+// The scan's launch form: per step the fused one-hot GRU, the grouped
+// latent_mapper.0 (+ the next step's hidden product at B >= 128) and the
+// LN-SiLU sampler head.  w.wt holds W_ih^T when a GRU step runs.  z_out is the
+// compact [B][R*C] state the steps work on; with `tr` every step's z, h (and
+// logits) are also written to the trace: the logits through the sampler
+// head's own store, z and h by copies of what the step left.  A trace entry is
+// the bits dr_observe_scan's launch form gives for that prefix.  The scan's
+// last step runs latent_mapper.0 alone (no next hidden product to group it
+// with: the plain product, not the weight planes), so where a traced step that
+// is not the last ran the grouped form (B >= 128), its entry comes from a
+// second run of that step's mapper and sampler head in the last-step form,
+// and the chain goes on from the grouped form as the scan's does.
+static int observe_steps(const dr_dims* d, const dr_world_model* wm, int B, int T, const float* feat,
+                         const float* actions, long long act_sb, long long act_st, const float* h_init,
+                         const float* z_init, const dr_noise& noise, float* z_out, float* h_out, float* logits_out,
+                         ObsWs& w, const ObsTrace* tr, hipStream_t s);
+
 extern "C" int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B, int T, const float* feat,
                                const float* actions, long long act_sb, long long act_st, const float* h_init,
                                const float* z_init, dr_noise noise, float* z_out, float* h_out, float* logits_out,
@@ -297,6 +322,17 @@ extern "C" int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B
                             noise, 0, z_out, h_out, logits_out, w.ring, s);
     if (rc != DR_E_UNSUPPORTED) return rc;
   }
+  return observe_steps(d, wm, B, T, feat, actions, act_sb, act_st, h_init, z_init, noise, z_out, h_out, logits_out, w,
+                       nullptr, s);
+}
+
+static int observe_steps(const dr_dims* d, const dr_world_model* wm, int B, int T, const float* feat,
+                         const float* actions, long long act_sb, long long act_st, const float* h_init,
+                         const float* z_init, const dr_noise& noise, float* z_out, float* h_out, float* logits_out,
+                         ObsWs& w, const ObsTrace* tr, hipStream_t s) {
+  const int L = latent(d), Hd = d->hidden, eh = d->enc_hidden;
+  const int F = enc_feat_dim(d);
+  const long long ldL = (long long)T * L, ldH = (long long)T * Hd;  // the trace's row strides
   const bool planes = B >= 128 && T > 1 && Hd % 8 == 0;
   if (planes) {
     DR_TRY(split_planes(eh, Hd, wm->map0.w + F, F + Hd, w.s3m0, s));
@@ -342,6 +378,7 @@ extern "C" int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B
     g[0] = lin(B, eh, h ? Hd : 0, h, Hd, wm->map0.w + F, F + Hd, nullptr, w.pre1, eh);
     g[0].addend = feat + (long long)t * B * eh;
     g[0].ld_add = eh;
+    const GemmArgs g_last = g[0];  // the form the scan's last step runs
     gh_pre = split_gru && h && t + 1 < T;
     if (gh_pre) {
       g[1] = lin(B, 3 * Hd, Hd, h, Hd, wm->w_hh, Hd, wm->b_hh, w.gh, 3 * Hd);
@@ -356,10 +393,36 @@ extern "C" int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B
     }
     DR_TRY(gemm_launch(G_NT, AM_PLAIN, g, gh_pre ? 2 : 1, s));
     float* lg = (t == T - 1 && logits_out) ? logits_out : nullptr;
-    GemmArgs gp = lin_ln(B, L, eh, w.pre1, eh, wm->map1, wm->map3.w, wm->map3.b, lg, L);
+    long long ld_lg = L;
+    // (the grouped form differs from g_last on the planes, and in bf16 mode)
+    const bool dual = tr && gh_pre && (planes || d->precision == DR_PREC_BF16);
+    if (tr && tr->post_logits) {
+      lg = tr->post_logits + (long long)t * L;
+      ld_lg = ldL;
+    }
+    GemmArgs gp = lin_ln(B, L, eh, w.pre1, eh, wm->map1, wm->map3.w, wm->map3.b, dual ? nullptr : lg, ld_lg);
     with_sampler(gp, d, noise, t, z_out, L, w.idx, nullptr, 0);
     DR_TRY(run(G_NT, AM_LNSILU, gp, s));
+    const float* zs = z_out;
+    if (dual) {
+      DR_TRY(gemm_launch(G_NT, AM_PLAIN, &g_last, 1, s));
+      GemmArgs gq = lin_ln(B, L, eh, w.pre1, eh, wm->map1, wm->map3.w, wm->map3.b, lg, ld_lg);
+      with_sampler(gq, d, noise, t, tr->z_last, L, tr->idx_last, nullptr, 0);
+      DR_TRY(run(G_NT, AM_LNSILU, gq, s));
+      zs = tr->z_last;
+    }
+    if (tr) {
+      const float* hs = h;
+      if (!hs) {  // (t == 0 of a window traced from the zero state: hb[0] is free until the first GRU)
+        DR_TRY(zero(w.hb[0], (long long)B * Hd, s));
+        hs = w.hb[0];
+      }
+      const Copy2dJob cj[2] = {{tr->latents + (long long)t * L, ldL, zs, L, L, B},
+                               {tr->hiddens + (long long)t * Hd, ldH, hs, Hd, Hd, B}};
+      DR_TRY(op_copy2d_multi(cj, 2, s));
+    }
   }
+  if (!h_out) return DR_OK;
   if (h) DR_TRY(copy2d(h_out, Hd, h, Hd, Hd, B, s));
   else DR_TRY(zero(h_out, (long long)B * Hd, s));
   return DR_OK;
@@ -503,8 +566,10 @@ extern "C" size_t dr_imagine_workspace_bytes(const dr_dims* d, int B, int H) {
 }
 
 // the reward / continue heads over all B (H + 1) states (after either unroll)
+// (keep0: rewards / continues are [B][H+1] and keep entry 0, dr_observe_trace's layout)
 static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* latents,
-                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s);
+                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s,
+                         bool keep0 = false);
 
 // the unroll as seven launches per step (shapes outside dream.hip, launch_form)
 static int imagine_launch_form(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int B, int H,
@@ -661,7 +726,7 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
 // of the contiguous [B][H+1] hiddens / latents (t' = 0 rides along unused);
 // forward only -- the actor loss takes no gradient through the heads
 static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* latents,
-                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s) {
+                         const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s, bool keep0) {
   const int L = latent(d), Hd = d->hidden;
   {
     const int M1 = B * (H + 1);
@@ -712,7 +777,8 @@ static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int 
       DR_TRY(gemm_launch(G_NT, AM_LNSILU, p, 2, s));
     }
     DR_TRY(op_bucket_value(M1, d->buckets, w.rlog, d->buckets, wm->buckets_rew, w.rval, 1, s));
-    const Copy2dJob cj[2] = {{rewards, H, w.rval + 1, H + 1, H, B}, {continues, H, w.clog + 1, H + 1, H, B}};
+    const int k0 = keep0 ? 0 : 1, Ho = H + 1 - k0;
+    const Copy2dJob cj[2] = {{rewards, Ho, w.rval + k0, H + 1, Ho, B}, {continues, Ho, w.clog + k0, H + 1, Ho, B}};
     DR_TRY(op_copy2d_multi(cj, 2, s));
   }
   return DR_OK;
@@ -1276,6 +1342,80 @@ extern "C" int dr_mlp3_fwd(const dr_mlp3* m, int M, int in_h, const float* h, lo
   float* p2 = c.f((long long)M * h2);
   WS_CHECK(c, ws_bytes);
   return mlp3(*m, M, in_h, h, ldh, in_z, z, ldz, h1, h2, n_out, out, ldo, p1, p2, s);
+}
+
+// ---------------------------------------------------------------------------
+// posterior trace: dr_observe_scan's launch form keeping every step
+// (observe_steps), then the prior MLP (DynamicsPredictors.py:25-29) and the
+// reward / continue heads (imagine_heads) once over the B*T traced states
+// ---------------------------------------------------------------------------
+struct TraceWs {
+  ObsWs o;
+  float *zc, *zl;  // the compact [B][R*C] state the steps work on; a step's last-step form (ObsTrace)
+  int* idxl;
+  float *p1, *p2;  // the prior's two hidden layers [B*T][prior_h1], [B*T][prior_h2]
+  ImWs w;          // the fields imagine_heads uses (the rest stay NULL)
+};
+static void trace_carve(Carve& c, const dr_dims* d, int B, int T, TraceWs& a) {
+  const long long BT = (long long)B * T;
+  const int L = latent(d), Hd = d->hidden;
+  obs_carve(c, d, B, a.o);
+  a.zc = c.f((long long)B * L);
+  a.zl = c.f((long long)B * L);
+  a.idxl = c.i(2LL * B * d->rows);
+  a.p1 = c.f(BT * d->prior_h1);
+  a.p2 = c.f(BT * d->prior_h2);
+  ImWs& w = a.w;
+  memset(&w, 0, sizeof(w));
+  w.p1r = c.f(BT * d->rew_h1);
+  w.p1c = c.f(BT * d->cont_h1);
+  w.p2r = c.f(BT * d->rew_h2);
+  w.p2c = c.f(BT * d->cont_h2);
+  w.rlog = c.f(BT * d->buckets);
+  w.clog = c.f(BT);
+  w.rval = c.f(BT);
+  w.s3r = c.raw(op_nt_split3_ws_bytes(d->rew_h1, Hd + L));
+  w.s3c = c.raw(op_nt_split3_ws_bytes(d->cont_h1, Hd + L));
+  w.s3part_n = op_gemm_nt_split3_part_floats((int)BT, std::max(d->rew_h1, d->cont_h1));
+  w.s3part = c.f((long long)w.s3part_n);
+}
+
+extern "C" size_t dr_observe_trace_workspace_bytes(const dr_dims* d, int B, int T) {
+  if (!d || B <= 0 || T <= 0 || (long long)B * T > 0x7fffffffLL) return 0;
+  Carve c(nullptr);
+  TraceWs a;
+  trace_carve(c, d, B, T, a);
+  return c.off;
+}
+
+extern "C" int dr_observe_trace(const dr_dims* d, const dr_world_model* wm, int B, int T, const float* feat,
+                                const float* actions, long long act_sb, long long act_st, const float* h_init,
+                                const float* z_init, dr_noise noise, float* latents, float* hiddens,
+                                float* post_logits, float* prior_logits, float* rewards, float* continues, void* ws,
+                                size_t ws_bytes, hipStream_t s) {
+  DR_REQUIRE(d && wm && feat && latents && hiddens && ws && B > 0 && T > 0, "null argument or empty batch");
+  DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many states");
+  DR_REQUIRE((rewards == nullptr) == (continues == nullptr), "rewards and continues: both or neither");
+  DR_REQUIRE(actions || (z_init == nullptr && T == 1), "actions required");
+  GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
+  Carve c(ws);
+  TraceWs a;
+  trace_carve(c, d, B, T, a);
+  WS_CHECK(c, ws_bytes);
+  const int L = latent(d), Hd = d->hidden;
+  if (z_init != nullptr || T > 1) {
+    DR_REQUIRE(wm->w_ih && wm->w_hh && wm->b_ih && wm->b_hh, "GRU weights required");
+    DR_TRY(op_transpose(3 * Hd, L + d->action, wm->w_ih, a.o.wt, s));
+  }
+  const ObsTrace tr = {latents, hiddens, post_logits, a.zl, a.idxl};
+  DR_TRY(observe_steps(d, wm, B, T, feat, actions, act_sb, act_st, h_init, z_init, noise, a.zc, nullptr, nullptr, a.o,
+                       &tr, s));
+  const int M = B * T;
+  if (prior_logits)
+    DR_TRY(mlp3(wm->prior, M, Hd, hiddens, Hd, 0, nullptr, 0, d->prior_h1, d->prior_h2, L, prior_logits, L, a.p1, a.p2,
+                s));
+  if (rewards) DR_TRY(imagine_heads(d, wm, B, T - 1, latents, hiddens, rewards, continues, a.w, s, true));
+  return DR_OK;
 }
 
 extern "C" int dr_gru_cell(const dr_dims* d, const dr_world_model* wm, int B, const float* z, const float* h,

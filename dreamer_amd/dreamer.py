@@ -291,6 +291,144 @@ class Dreamer(nn.Module):
         out = [None if a is None else (a / float(batches)).cpu().tolist() for a in acc]
         return {"mse": out[0], "psnr": out[1], "reward_abs_err": out[2], "continue_bce": out[3]}
 
+    def closed_loop(self, starts=None, batch_size=None, length=None, sample=True, noise=None, predict=True,
+                    _mark=None):
+        """Posterior trace on replay windows (closed_loop.py): run the filter
+        (warm_start_generator's scan, Dreamer.py:244-262) over the first
+        `length` frames of each window keeping every step, and report per step
+        the posterior and prior logits, KL(posterior || prior) and the two
+        entropies, the posterior's reconstruction and -- predict=True -- the
+        decode of a sample of the prior of h_t (what the model expected before
+        frame t arrived), both against the ring's frame t, and the reward /
+        continue heads against the stored values.  Returns a ClosedLoopResult.
+
+        starts: window starts (default: buffer.sample_start_indices(batch_size
+        or self.batch_size)); length defaults to S.  noise: optional pair of
+        explicit Exp(1) draws (q_post (T, B*R, C), q_prior (T, B*R, C)), else
+        Philox on two distinct ad-hoc streams; sample=False takes the mode of
+        every categorical (q == 1 for both).  Frames are read straight from the
+        device ring; everything runs on the current stream without a sync.
+        _mark: stage hook of tools/closed_loop_timing.py."""
+        from .closed_loop import ClosedLoopResult, check_length
+        from .utils import symlog
+        mark = _mark or (lambda name: None)
+        S = self.sequence_length
+        T = S if length is None else int(length)
+        check_length(T, S)
+        buf, wmod = self.buffer, self.world_model
+        dev = buf.device
+        if starts is None:
+            starts = buf.sample_start_indices(batch_size or self.batch_size)
+        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
+            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
+        B = int(st.numel())
+        R, C = self.latent_state_dims
+        A, Hd = self.action_dims, self.hidden_state_dims
+        if noise is not None:
+            q_post, q_prior = (t.float().contiguous() for t in noise)
+            if tuple(q_post.shape) != (T, B * R, C) or tuple(q_prior.shape) != (T, B * R, C):
+                raise ValueError(f"noise must be two tensors of shape ({T}, {B * R}, {C})")
+        elif not sample:
+            q_post = q_prior = torch.ones(T, B * R, C, device=dev)
+        else:
+            q_post = q_prior = None
+        d = wmod.dims(self.agent)
+        wm = wmod.packed()
+        stream = hip.stream()
+        m = buf._mirror()
+        act = torch.empty(B, S, A, device=dev)
+        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
+        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
+               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
+        mark("gather")
+        fr = buf.frames_struct(st)
+        feat = torch.empty(T * B, d.enc_hidden, device=dev)
+        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, T * B))
+        L.call("dr_encoder_features", d, wm, fr, B, T, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
+        mark("encoder")
+        # action t-1 drives frame t; state t's heads are compared with window step t-1
+        lat, hid, plog, prlog, r, c = wmod._observe_trace(d, B, T, feat, act.data_ptr(), S * A, A, None, None, q_post)
+        mark("trace")
+        M = B * T
+        kl, hq, hp = (torch.empty(B, T, device=dev) for _ in range(3))
+        L.call("dr_latent_stats", M, R, C, L.ptr(plog), L.ptr(prlog), L.ptr(kl), L.ptr(hq), L.ptr(hp), None, stream)
+        mark("stats")
+        zp = None
+        if predict:
+            # the prior's own draw t for row (b, t): explicit draws are given time-major, the rows are [B][T]
+            zp = torch.empty(B, T, R, C, device=dev)
+            if q_prior is not None:
+                qp = q_prior.view(T, B, R, C).transpose(0, 1).contiguous()
+                nz = hip.explicit_noise(q=qp, device=dev)
+            else:
+                nz = hip.adhoc(dev).noise()
+            L.call("dr_categorical_sample", M, R, C, L.ptr(prlog), nz, L.ptr(zp), None, None, stream)
+            mark("prior_sample")
+        vector = buf.vector
+        shape = (d.obs_dim,) if vector else (3, d.img_h, d.img_w)
+        ws = hip.workspace(dev).get("dec", L.query("dr_decoder_workspace_bytes", d, M))
+        dec = wmod.packed_decoder()
+        truth = buf.frames_struct(st)
+        truth.t0 = 0
+        out = []
+        for z in (lat, zp):
+            if z is None:
+                out.append((None, None, None))
+                continue
+            mu = torch.empty(B, T, *shape, device=dev)
+            L.call("dr_decoder_fwd", d, dec, M, L.ptr(hid), Hd, L.ptr(z), R * C, L.ptr(mu), L.ptr(ws), ws.numel(),
+                   stream)
+            out.append((mu, torch.empty(B, T, device=dev),
+                        None if vector else torch.empty(B, T, *shape, dtype=torch.uint8, device=dev)))
+        mark("decoder")
+        true = None if vector else torch.empty(B, T, *shape, dtype=torch.uint8, device=dev)
+        for k, (mu, sq, pred) in enumerate(out):
+            if mu is not None:
+                L.call("dr_frame_metrics", d, B, T, L.ptr(mu), truth, L.ptr(sq), L.ptr(pred),
+                       L.ptr(true) if k == 0 else None, stream)
+        mark("metrics")
+        (mu_q, sq_q, fr_q), (mu_p, sq_p, fr_p) = out
+        return ClosedLoopResult(latents=lat, hiddens=hid, post_logits=plog, prior_logits=prlog, kl=kl, post_entropy=hq,
+                                prior_entropy=hp, mu_post=mu_q, mu_prior=mu_p, latents_prior=zp, sqerr_post=sq_q,
+                                sqerr_prior=sq_p, frames_post=fr_q, frames_prior=fr_p, frames_true=true,
+                                reward_pred=symlog(r[:, 1:]), reward_true=rew[:, :T - 1].unsqueeze(-1).clone(),
+                                continue_pred=c[:, 1:].clone(), continue_true=cont[:, :T - 1].unsqueeze(-1).clone(),
+                                length=T)
+
+    def evaluate_filter(self, batches=1, batch_size=None, length=None, sample=True):
+        """Per-step closed-loop curves averaged over `batches` sampled batches
+        of windows: a dict of CPU float lists -- kl, post_entropy,
+        prior_entropy, mse_post, mse_prior, psnr_post, psnr_prior (length T;
+        the psnr entries are None for vector observations), reward_abs_err
+        (symlog space) and continue_bce (length T - 1).  Leaves np.random's
+        state and the Philox {seed, offset} and stream counter as it found
+        them, like evaluate_world_model."""
+        np_state = np.random.get_state()
+        ar = hip.adhoc(self.device)
+        rng_state, rng_counter = ar.state.clone(), ar.counter
+        keys = ("kl", "post_entropy", "prior_entropy", "mse_post", "mse_prior", "psnr_post", "psnr_prior",
+                "reward_abs_err", "continue_bce")
+        try:
+            acc = None
+            with torch.no_grad():
+                for _ in range(int(batches)):
+                    r = self.closed_loop(batch_size=batch_size, length=length, sample=sample)
+                    px = r.frames_post is not None
+                    cur = [r.kl.mean(0), r.post_entropy.mean(0), r.prior_entropy.mean(0), r.mse_post().mean(0),
+                           r.mse_prior().mean(0), r.psnr_post().mean(0) if px else None,
+                           r.psnr_prior().mean(0) if px else None,
+                           (r.reward_pred - r.reward_true).abs().mean((0, 2)),
+                           torch.nn.functional.binary_cross_entropy(r.continue_pred.clamp(0.0, 1.0), r.continue_true,
+                                                                    reduction="none").mean((0, 2))]
+                    acc = cur if acc is None else [None if a is None else a + b for a, b in zip(acc, cur)]
+        finally:
+            np.random.set_state(np_state)
+            ar.state.copy_(rng_state)
+            ar.counter = rng_counter
+        if acc is None:
+            raise ValueError("evaluate_filter needs batches >= 1")
+        return {k: None if a is None else (a / float(batches)).cpu().tolist() for k, a in zip(keys, acc)}
+
     # --------------------------------------------------------------- training
     @property
     def engine(self):

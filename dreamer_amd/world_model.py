@@ -217,6 +217,62 @@ class WorldModel(nn.Module):
                L.ptr(lat), L.ptr(hid), L.ptr(rew), L.ptr(cont), L.ptr(ws), ws.numel(), hip.stream())
         return lat, hid, rew, cont
 
+    def observe_sequence(self, observations, actions, noise_q=None, sample=True, hidden_state=None,
+                         latent_state=None):
+        """The posterior filter over a whole sequence in one call
+        (dr_encoder_features + dr_observe_trace), keeping every step:
+        observations (B,T,3,H,W) holding 0..255 as Buffer.sample_sequences gives
+        them (or (B,T,D) vector observations, used as given), actions (B,>=T,A).
+        Without latent_state it is warm_start_generator's convention
+        (Dreamer.py:244-262): frame 0 is encoded from hidden_state (zeros if
+        None) and action t-1 drives frame t >= 1; with latent_state (B,1,R,C)
+        and hidden_state (B,1,hidden) every frame t runs observe_step
+        (WorldModel.py:79-82) under action t first, so a long sequence can be
+        traced in time chunks.  Returns latents (B,T,R,C), hiddens (B,T,hidden),
+        post_logits and prior_logits (B,T,R,C).  noise_q: explicit Exp(1) draws
+        (T, B*R, C) (parity tests), else Philox; sample=False takes the
+        posterior's mode (q == 1)."""
+        L.require_gpu(observations)
+        B, T = observations.shape[:2]
+        R, C, Hd, A = self.latent_num_rows, self.latent_num_columns, self.hidden_dims, self.action_dims
+        dev = observations.device
+        obs = observations.float().contiguous()
+        act = actions.float().contiguous()
+        if act.shape[0] != B or act.shape[1] < (T if latent_state is not None else T - 1) or act.shape[2] != A:
+            raise ValueError(f"actions {tuple(act.shape)} do not cover {T} steps of {B} windows")
+        if noise_q is None and not sample:
+            noise_q = torch.ones(T, B * R, C, device=dev)
+        if noise_q is not None:
+            noise_q = noise_q.float().contiguous()
+            if tuple(noise_q.shape) != (T, B * R, C):
+                raise ValueError(f"noise_q must be ({T}, {B * R}, {C}), got {tuple(noise_q.shape)}")
+        d = self.dims()
+        fe = int(np.prod(obs.shape[2:]))
+        fr = L.dr_frames(None, 0, None, L.ptr(obs), T * fe, fe, 0 if self.vector_obs else 1)
+        feat = torch.empty(T * B, d.enc_hidden, device=dev)
+        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, T * B))
+        L.call("dr_encoder_features", d, self.packed(), fr, B, T, L.ptr(feat), L.ptr(ws), ws.numel(), hip.stream())
+        h = None if hidden_state is None else hidden_state.reshape(B, Hd).float().contiguous()
+        z = None if latent_state is None else latent_state.reshape(B, R * C).float().contiguous()
+        out = self._observe_trace(d, B, T, feat, act.data_ptr() if act.numel() else None, act.shape[1] * A, A, h, z,
+                                  noise_q, heads=False)
+        return out[0], out[1], out[2], out[3]
+
+    def _observe_trace(self, d, B, T, feat, act_ptr, act_sb, act_st, h_init, z_init, noise_q, heads=True):
+        R, C, Hd = self.latent_num_rows, self.latent_num_columns, self.hidden_dims
+        dev = feat.device
+        lat, plog, prlog = (torch.empty(B, T, R, C, device=dev) for _ in range(3))
+        hid = torch.empty(B, T, Hd, device=dev)
+        rew = cont = None
+        if heads:
+            rew, cont = torch.empty(B, T, 1, device=dev), torch.empty(B, T, 1, device=dev)
+        nz = hip.explicit_noise(q=noise_q, device=dev) if noise_q is not None else hip.adhoc(dev).noise()
+        ws = hip.workspace(dev).get("obs_trace", L.query("dr_observe_trace_workspace_bytes", d, B, T))
+        L.call("dr_observe_trace", d, self.packed(), B, T, L.ptr(feat), act_ptr, act_sb, act_st, L.ptr(h_init),
+               L.ptr(z_init), nz, L.ptr(lat), L.ptr(hid), L.ptr(plog), L.ptr(prlog), L.ptr(rew), L.ptr(cont),
+               L.ptr(ws), ws.numel(), hip.stream())
+        return lat, hid, plog, prlog, rew, cont
+
     def observe_step(self, last_latent, last_hidden, last_action, observation):  # WorldModel.py:79-82
         if hip.needs_torch_grad(self.sequence_model, self.encoder):
             return self._observe_step_torch(last_latent, last_hidden, last_action, observation)

@@ -180,6 +180,47 @@ int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B, int T, co
                     const float* z_init, dr_noise noise, float* z_out, float* h_out, float* logits_out,
                     void* ws, size_t ws_bytes, hipStream_t stream);
 
+/* ---- posterior trace: the same filter keeping EVERY step (the closed-loop
+ *      diagnostic of Dreamer.closed_loop / WorldModel.observe_sequence) ---------
+ * Arguments feat .. noise as dr_observe_scan (warm_start_generator's
+ * convention, Dreamer.py:244-262, when z_init == NULL: h_0 = h_init or 0,
+ * z_0 ~ posterior(h_0, x_0) with draw 0; observe_step, WorldModel.py:79-82, per
+ * further frame, draw t).  Outputs, entry t from the state after frame t:
+ *   latents      [B][T][R*C]     z_t (straight-through one-hot, VAE.py:88-98)
+ *   hiddens      [B][T][hidden]  h_t (SequenceModel.py:19-24)
+ *   post_logits  [B][T][R*C]     the encoder's raw logits (VAE.py:77-87), may be NULL
+ *   prior_logits [B][T][R*C]     dynamics_predictor.logit_net(h_t)
+ *                                (DynamicsPredictors.py:25-29), may be NULL
+ *   rewards / continues [B][T]   symexp E[bucket] and sigmoid of the heads on
+ *                                (h_t, z_t) (DynamicsPredictors.py:64-74, 95-105),
+ *                                both or neither; entry 0 rides along
+ *                                (unroll_model compares entry t >= 1 with the
+ *                                targets of step t-1, WorldModel.py:113-123)
+ * Always the launch sequence (dr_dims.launch_form is ignored; there is no
+ * persistent form): per step dr_observe_scan's launch-form kernels -- the fused
+ * one-hot GRU, the grouped latent_mapper.0 (+ the next hidden product at
+ * B >= 128, on the same weight planes), the LN-SiLU sampler head, whose logits
+ * store goes straight to post_logits -- and one strided copy of z_t, h_t into
+ * the trace; then the prior MLP and the heads once over the B*T rows.  Honours
+ * dr_dims.precision like dr_observe_scan.
+ * Contract: entry t of latents / hiddens / post_logits is bit for bit what
+ * dr_observe_scan returns in launch form (dr_dims.launch_form = 1) for the
+ * prefix T' = t + 1 on the same inputs and noise.  (The scan's last step runs
+ * latent_mapper.0 alone; at B >= 128 a step that is not the last runs it
+ * grouped with the next hidden product on the weight planes and goes on from
+ * that.  The trace does the same, and reports such a step a second time in the
+ * last-step form: two more launches per step at B >= 128.)  A trace of T steps
+ * equals a trace of T1 steps followed by a continuing call (h_init, z_init =
+ * entry T1 - 1, actions / feat / noise advanced by T1 steps) of T - T1 steps,
+ * as a time-chunked dr_observe_scan equals the whole scan: the next step reads
+ * z_t's indices and straight-through values. */
+size_t dr_observe_trace_workspace_bytes(const dr_dims* d, int B, int T);
+int dr_observe_trace(const dr_dims* d, const dr_world_model* wm, int B, int T, const float* feat,
+                     const float* actions, long long act_sb, long long act_st, const float* h_init,
+                     const float* z_init, dr_noise noise, float* latents, float* hiddens, float* post_logits,
+                     float* prior_logits, float* rewards, float* continues, void* ws, size_t ws_bytes,
+                     hipStream_t stream);
+
 /* ---- a7  imagination unroll (dream_episodes, Dreamer.py:143-175) -----------
  * Outputs use the reference's layouts: latents [B][H+1][R*C], hiddens
  * [B][H+1][hidden], actions/mus/sigmas [B][H][A], rewards/continues [B][H].
@@ -484,6 +525,21 @@ int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, const float* 
  * position, and from run to run. */
 int dr_frame_metrics(const dr_dims* d, int B, int T, const float* mu, const dr_frames* truth, float* sqerr,
                      unsigned char* pred_u8, unsigned char* true_u8, hipStream_t stream);
+
+/* ---- latent statistics on raw logits [M][R][C] (no unimix, no free bits, no
+ *      mask: the terms of the KL losses, WorldModel.py:175-181, per row) --------
+ *   kl[m]            = sum_r KL(Cat(logits = post[m][r]) || Cat(logits = prior[m][r]))
+ *                      (torch's _kl_categorical_categorical: sum p (lp - lq), p = exp(lp))
+ *   post_entropy[m]  = sum_r H(softmax post[m][r]);  prior_entropy[m] likewise
+ *   kl_groups[m][r]  = the R terms of kl[m], may be NULL
+ * prior_logits may be NULL: then only post_entropy is written, and kl,
+ * prior_entropy (and kl_groups) must be NULL.  Domain as dr_categorical_sample:
+ * 1 <= C <= 64, R >= 1, M >= 0, else DR_E_INVALID.  Max-subtracted
+ * log-sum-exp; a class whose probability underflows to 0 adds exactly 0.  One
+ * workgroup per row and a fixed reduction order, no atomics: a row has the same
+ * bits at every M and position, and from run to run. */
+int dr_latent_stats(int M, int R, int C, const float* post_logits, const float* prior_logits, float* kl,
+                    float* post_entropy, float* prior_entropy, float* kl_groups, hipStream_t stream);
 
 /* ---- a1  replay gather (Buffer.sample_sequences, Buffer.py:49-61) --------- */
 int dr_replay_gather(long long cap, int B, int S, int frame_elems, int A, const unsigned char* frames,
