@@ -8,6 +8,7 @@ libdreamer_hip.so behind a C ABI (include/dreamer_hip.h)."""
 from .agent import Actor, Agent, Critic  # noqa: F401
 from .buffer import Buffer  # noqa: F401
 from .dreamer import Dreamer  # noqa: F401
+from .agent_trace import AgentTraceResult  # noqa: F401
 from .closed_loop import ClosedLoopResult  # noqa: F401
 from .open_loop import OpenLoopResult  # noqa: F401
 from .networks import (ContinuePredictor, Decoder, DynamicsPredictor, Encoder, RewardPredictor,  # noqa: F401

@@ -93,7 +93,10 @@ _SIGS = {
     "dr_observe_trace": (_i, [_P(dr_dims), _P(dr_world_model), _i, _i, fp, fp, _ll, _ll, fp, fp, dr_noise,
                               fp, fp, fp, fp, fp, fp, fp, _sz, fp]),
     "dr_latent_stats": (_i, [_i, _i, _i, fp, fp, fp, fp, fp, fp, fp]),
-    "dr_imagine_tape_bytes": (_sz, [_P(dr_dims), _i, _i]),
+    "dr_replay_returns": (_i, [_i, _i, fp, _ll, fp, _ll, _i, fp, _f, _f, fp, fp, fp, fp]),
+    "dr_value_stats": (_i, [_i, _i, _i, _i, fp, _ll, fp, fp, fp, fp, fp, fp]),
+    "dr_action_logprob": (_i, [_i, _i, _i, fp, fp, fp, _ll, _ll, fp, fp, fp, fp]),
+    "dr_imagine_tape_bytes":(_sz, [_P(dr_dims), _i, _i]),
     "dr_imagine_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
     "dr_imagine_fwd": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, _i, fp, fp, dr_noise, _i,
                             fp, fp, fp, fp, fp, fp, fp, fp, fp, _sz, fp]),

@@ -1,5 +1,5 @@
-// Metrics of the world-model diagnostics (open-loop prediction, posterior
-// trace).  Frame metrics: decoded frames against
+// Metrics of the diagnostics on replay windows (open-loop prediction, posterior
+// trace, agent trace).  Frame metrics: decoded frames against
 // the true frames of the replay ring -- the per-frame squared error of the
 // reconstruction term (WorldModel.py:129) and the u8 frames of a prediction
 // video.  Built with -ffp-contract=off like the other elementwise code, so the
@@ -258,4 +258,211 @@ extern "C" int dr_latent_stats(int M, int R, int C, const float* post_logits, co
   else hipLaunchKernelGGL(k_latent_stats<1>, grid, block, 0, s, R, C, W, post_logits, prior_logits, kl, post_entropy,
                           prior_entropy, kl_groups);
   return dr_check_launch("latent_stats");
+}
+
+// ---------------------------------------------------------------------------
+// Agent trace on replay windows (agent_trace.py): the per-row statistics the
+// loss kernels keep to themselves (k_critic_ce, k_actor_loss_grad in ops.hip emit
+// means and gradients only), and the return recursion on the ring's windows.
+// Three one-shot kernels: nothing is shared between workgroups, no atomics.
+// ---------------------------------------------------------------------------
+
+// Lambda returns on real rewards (Agent.py:156-172 with H = T - 1): one thread
+// per window, k_lambda_returns' expressions in its order.  Rewards / continues
+// are rows of [B][S] windows (row strides rew_sb / cont_sb, entries 0 .. T-2
+// read); symlog != 0: the stored symlog reward goes through dr_symexp first
+// (DreamerUtils.py:35-37).  R_mc is the same recursion at lam = 1, lam_c = 0
+// (the expression is kept whole, so finite V give dr_lambda_returns(lam = 1)'s
+// bits); td[t] = (r_t + (gamma c_t) V_{t+1}) - V_t.
+__global__ __launch_bounds__(64) void k_replay_returns(int B, int T, const float* __restrict__ rew, long long rew_sb,
+                                                       const float* __restrict__ cont, long long cont_sb, int symlog,
+                                                       const float* __restrict__ V, float gamma, float lam, float lam_c,
+                                                       float* __restrict__ Rl, float* __restrict__ Rmc,
+                                                       float* __restrict__ td) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int H = T - 1;
+  const float* rb = rew + (long long)b * rew_sb;
+  const float* cb = cont + (long long)b * cont_sb;
+  const float* vb = V + (long long)b * T;
+  float* Rb = Rl + (long long)b * H;
+  float* Mb = Rmc ? Rmc + (long long)b * H : nullptr;
+  float* Db = td ? td + (long long)b * H : nullptr;
+  float nxt = 0.0f, mc = 0.0f;
+  for (int t = H - 1; t >= 0; --t) {
+    const float r = symlog ? dr_symexp(rb[t]) : rb[t];
+    const float gc = gamma * cb[t];
+    const float v1 = vb[t + 1];
+    const float boot = r + gc * v1;  // the last step's return, and the one-step target
+    float v, m;
+    if (t == H - 1) {
+      v = boot;
+      m = boot;
+    } else {
+      v = r + gc * ((lam_c * v1) + (lam * nxt));
+      m = r + gc * ((0.0f * v1) + (1.0f * mc));
+    }
+    Rb[t] = v;
+    if (Mb) Mb[t] = m;
+    if (Db) Db[t] = boot - vb[t];
+    nxt = v;
+    mc = m;
+  }
+}
+
+extern "C" int dr_replay_returns(int B, int T, const float* rewards, long long rew_sb, const float* continues,
+                                 long long cont_sb, int rewards_symlog, const float* V, float gamma, float lam,
+                                 float* R_lambda, float* R_mc, float* td, hipStream_t s) {
+  DR_REQUIRE(B >= 0 && T >= 2, "need B >= 0 and T >= 2");
+  DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many rows");
+  DR_REQUIRE(rew_sb >= T - 1 && cont_sb >= T - 1, "window row strides must be >= T - 1");
+  DR_REQUIRE(rewards && continues && V && R_lambda, "rewards, continues, V and R_lambda are required");
+  if (B == 0) return DR_OK;
+  const float lam_c = (float)(1.0 - (double)lam);
+  hipLaunchKernelGGL(k_replay_returns, dim3(dr_cdiv(B, 64)), dim3(64), 0, s, B, T, rewards, rew_sb, continues, cont_sb,
+                     rewards_symlog, V, gamma, lam, lam_c, R_lambda, R_mc, td);
+  return dr_check_launch("replay_returns");
+}
+
+// Per-row statistics of a bucket head's logits (rows m = b*T + t, row stride
+// ldl): entropy H(softmax l), the spread sqrt(sum p (b - sum p b)^2) in bucket
+// (symlog) units, and -- rows t < Tt -- the two-hot cross-entropy against
+// symlog(target[b][t]) (Agent.py:127-135, to_twohot of DreamerUtils.py:39-50 with
+// its clamps and the 1e-8; k_critic_ce's row convention, the weights in double).
+// One wave per row, four rows per workgroup, like k_bucket_value.  Every sum:
+// the lane's classes lane, lane + 64, ... in ascending order, then wave_sum's
+// tree.  log-probabilities are (l - max) - log(sum exp(l - max)); a class whose
+// probability underflowed adds exactly 0 to the entropy.  The spread takes two
+// passes: the mean first, then the squared deviations.
+__global__ __launch_bounds__(256) void k_value_stats(int M, int T, int Tt, int nb, const float* __restrict__ logits,
+                                                     long long ldl, const float* __restrict__ buckets,
+                                                     const float* __restrict__ target, float* __restrict__ entropy,
+                                                     float* __restrict__ spread, float* __restrict__ ce) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= M) return;  // (whole waves leave: every lane of a working wave takes part in the DPP reductions)
+  const int b = row / T, t = row - b * T;
+  const float* l = logits + (long long)row * ldl;
+  float mx = -INFINITY;
+  for (int k = lane; k < nb; k += 64) mx = fmaxf(mx, l[k]);
+  mx = wave_max(mx);
+  float se = 0.0f;
+  for (int k = lane; k < nb; k += 64) se = se + expf(l[k] - mx);
+  se = wave_sum(se);
+  const float lse = logf(se);
+  if (entropy || spread) {
+    float h = 0.0f, mean = 0.0f;
+    for (int k = lane; k < nb; k += 64) {
+      const float lp = (l[k] - mx) - lse;
+      const float p = expf(lp);
+      h = h + (p > 0.0f ? p * lp : 0.0f);  // never 0 * -inf
+      mean = mean + p * buckets[k];
+    }
+    h = wave_sum(h);
+    mean = wave_sum(mean);
+    if (entropy && lane == 0) entropy[row] = -h;
+    if (spread) {
+      float var = 0.0f;
+      for (int k = lane; k < nb; k += 64) {
+        const float p = expf((l[k] - mx) - lse);
+        const float dv = buckets[k] - mean;
+        var = var + p * (dv * dv);
+      }
+      var = wave_sum(var);
+      if (lane == 0) spread[row] = sqrtf(var);
+    }
+  }
+  if (t < Tt) {  // (Tt > 0 only with target and ce)
+    // The two-hot weights in double: an error of one f32 step in symlog(R) moves
+    // w by step / (bucket spacing) and the loss by that times the gap between the
+    // two neighbouring log-probabilities -- with 255 buckets ten f32 steps of the
+    // loss, where k_critic_ce's f32 weights only have to serve a mean.  One
+    // double log per row.
+    const double x = (double)target[(long long)b * Tt + t];
+    double v = log1p(fabs(x));
+    v = x < 0.0 ? -v : v;  // (symlog(0) = 0 either way; NaN falls to the first bucket as in k_critic_ce)
+    v = fmin(fmax(v, (double)buckets[0]), (double)buckets[nb - 1]);
+    int cnt = 0;
+    for (int k = lane; k < nb; k += 64) cnt += ((double)buckets[k] <= v) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    int lo = cnt - 1;
+    if (lo > nb - 2) lo = nb - 2;
+    if (lo < 0) lo = 0;  // ascending buckets never get here; keeps the reads in bounds for any others
+    const double blo = (double)buckets[lo], bhi = (double)buckets[lo + 1];
+    const double wd = (v - blo) / (bhi - blo + 1e-8);
+    const float w = (float)wd, wlo = (float)(1.0 - wd);
+    if (lane == 0) {
+      const float ls_lo = (l[lo] - mx) - lse, ls_hi = (l[lo + 1] - mx) - lse;
+      ce[(long long)b * Tt + t] = -(wlo * ls_lo + w * ls_hi);
+    }
+  }
+}
+
+extern "C" int dr_value_stats(int B, int T, int Tt, int nb, const float* logits, long long ldl, const float* buckets,
+                              const float* target, float* entropy, float* std_symlog, float* ce, hipStream_t s) {
+  DR_REQUIRE(B >= 0 && T >= 1 && Tt >= 0 && Tt <= T, "need B >= 0, T >= 1 and 0 <= Tt <= T");
+  DR_REQUIRE(nb >= 2 && nb <= 1024, "need 2 <= nb <= 1024");
+  DR_REQUIRE(ldl >= nb, "ldl < nb");
+  DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many rows");
+  DR_REQUIRE(logits && buckets, "logits and buckets are required");
+  DR_REQUIRE((target != nullptr) == (ce != nullptr), "target and ce are both NULL or both given");
+  DR_REQUIRE((Tt > 0) == (target != nullptr), "target and ce go with Tt > 0 (Tt = 0: both NULL)");
+  DR_REQUIRE(entropy || std_symlog || ce, "no output requested");
+  const int M = B * T;
+  if (M == 0) return DR_OK;
+  hipLaunchKernelGGL(k_value_stats, dim3(dr_cdiv(M, 4)), dim3(256), 0, s, M, T, Tt, nb, logits, ldl, buckets, target,
+                     entropy, std_symlog, ce);
+  return dr_check_launch("value_stats");
+}
+
+// log-probability of the recorded action under the current actor (Agent.py:110-115):
+// per dimension, TransformedDistribution(Normal(mu, sigma), TanhTransform).log_prob at
+// y = clamp(a, +-(1 - 1e-6)) (the clamp in f32, so +-1 stays finite):
+//   x = atanh(y);  -(x-mu)^2/(2 sigma^2) - log sigma - log sqrt(2 pi) - 2 (log 2 - x - softplus(-2x))
+// k_actor_loss_grad's expressions.  One thread per row (b, t) adds the A terms
+// in ascending order from 0.0f; base_entropy = sum_i ((1/2 + 1/2 log 2 pi) + log sigma_i)
+// likewise (the Normal's entropy: the policy's, less the tanh correction).
+__global__ __launch_bounds__(128) void k_action_logprob(int M, int T, int A, const float* __restrict__ mus,
+                                                        const float* __restrict__ sigmas,
+                                                        const float* __restrict__ actions, long long act_sb,
+                                                        long long act_st, float* __restrict__ logp,
+                                                        float* __restrict__ logp_dims, float* __restrict__ base_ent) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // (b,t)
+  if (i >= M) return;
+  const int b = i / T, t = i - b * T;
+  const float* a = actions + (long long)b * act_sb + (long long)t * act_st;
+  const float HALF_LOG_2PI = 0.91893853320467274178f;  // math.log(math.sqrt(2*math.pi))
+  const float LOG2 = 0.69314718055994530942f;
+  const float ENT0 = 1.41893853320467274178f;  // 1/2 + 1/2 log(2 pi)
+  float acc = 0.0f, ent = 0.0f;
+  for (int k = 0; k < A; ++k) {
+    const long long o = (long long)i * A + k;
+    const float y = fminf(fmaxf(a[k], -1.0f + 1e-6f), 1.0f - 1e-6f);
+    const float x = atanhf(y);
+    const float mu = mus[o], sg = sigmas[o];
+    const float d = x - mu;
+    const float var = sg * sg;
+    const float lsg = logf(sg);
+    const float lp = -(d * d) / (2.0f * var) - lsg - HALF_LOG_2PI;
+    const float ladj = 2.0f * (LOG2 - x - dr_softplus(-2.0f * x));
+    const float term = lp - ladj;
+    if (logp_dims) logp_dims[o] = term;
+    acc = acc + term;
+    ent = ent + (ENT0 + lsg);
+  }
+  logp[i] = acc;
+  if (base_ent) base_ent[i] = ent;
+}
+
+extern "C" int dr_action_logprob(int B, int T, int A, const float* mu, const float* sigma, const float* actions,
+                                 long long act_sb, long long act_st, float* logp, float* logp_dims, float* base_entropy,
+                                 hipStream_t s) {
+  DR_REQUIRE(B >= 0 && T >= 1 && A >= 1, "need B >= 0, T >= 1 and A >= 1");
+  DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many rows");
+  DR_REQUIRE(act_sb >= 0 && act_st >= 0, "negative action stride");
+  DR_REQUIRE(mu && sigma && actions && logp, "mu, sigma, actions and logp are required");
+  const int M = B * T;
+  if (M == 0) return DR_OK;
+  hipLaunchKernelGGL(k_action_logprob, dim3(dr_cdiv(M, 128)), dim3(128), 0, s, M, T, A, mu, sigma, actions, act_sb,
+                     act_st, logp, logp_dims, base_entropy);
+  return dr_check_launch("action_logprob");
 }

@@ -429,6 +429,140 @@ class Dreamer(nn.Module):
             raise ValueError("evaluate_filter needs batches >= 1")
         return {k: None if a is None else (a / float(batches)).cpu().tolist() for k, a in zip(keys, acc)}
 
+    def agent_trace(self, starts=None, batch_size=None, length=None, sample=True, noise=None, _mark=None):
+        """Agent trace on replay windows (agent_trace.py): run closed_loop's
+        filter over the first `length` frames of each window and report per
+        step what the actor and the critic make of real data -- the online and
+        target values and the critic's logits with their entropy and spread,
+        the lambda-returns, discounted real returns and TD errors of the
+        recorded rewards under the target values (Agent.py:156-172), the
+        critic's two-hot loss against those returns (Agent.py:127-135), and the
+        log-probability of the recorded actions under the current actor
+        (Agent.py:110-115).  Returns an AgentTraceResult.
+
+        starts: window starts (default: buffer.sample_start_indices(batch_size
+        or self.batch_size)); length defaults to S, 2 <= length <= S.  noise:
+        optional explicit Exp(1) draws q_post (T, B*R, C), else Philox;
+        sample=False takes the mode of every categorical (q == 1).  gamma and
+        lambda are the agent's.  Frames are read straight from the device
+        ring; everything runs on the current stream without a sync.  _mark:
+        stage hook of tools/agent_trace_timing.py."""
+        from .agent_trace import AgentTraceResult, check_length
+        mark = _mark or (lambda name: None)
+        S = self.sequence_length
+        T = S if length is None else int(length)
+        check_length(T, S)
+        buf, wmod, ag = self.buffer, self.world_model, self.agent
+        dev = buf.device
+        if starts is None:
+            starts = buf.sample_start_indices(batch_size or self.batch_size)
+        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
+            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
+        B = int(st.numel())
+        R, C = self.latent_state_dims
+        A, Hd = self.action_dims, self.hidden_state_dims
+        if noise is not None:
+            q_post = noise.float().contiguous()
+            if tuple(q_post.shape) != (T, B * R, C):
+                raise ValueError(f"noise must be one tensor of shape ({T}, {B * R}, {C})")
+        elif not sample:
+            q_post = torch.ones(T, B * R, C, device=dev)
+        else:
+            q_post = None
+        ag._ensure_flat()
+        d = wmod.dims(ag)
+        wm = wmod.packed()
+        stream = hip.stream()
+        m = buf._mirror()
+        act = torch.empty(B, S, A, device=dev)
+        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
+        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
+               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
+        mark("gather")
+        fr = buf.frames_struct(st)
+        feat = torch.empty(T * B, d.enc_hidden, device=dev)
+        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, T * B))
+        L.call("dr_encoder_features", d, wm, fr, B, T, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
+        mark("encoder")
+        # action t-1 drives frame t: closed_loop's filter, without the prior and the heads
+        lat, hid, _, _, _, _ = wmod._observe_trace(d, B, T, feat, act.data_ptr(), S * A, A, None, None, q_post,
+                                                   heads=False, prior=False)
+        mark("trace")
+        # both critics over the M = B*T states, rows straight from the trace's arrays
+        M, nb = B * T, ag.buckets
+        logits = torch.empty(B, T, nb, device=dev)
+        V, Vt = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
+        ws = hip.workspace(dev).get("at_crit", L.query("dr_critic_workspace_bytes", d, B, T - 1))
+        L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(hid), Hd, L.ptr(lat), R * C, L.ptr(logits), L.ptr(V),
+               None, L.ptr(ws), ws.numel(), stream)
+        L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(hid), Hd, L.ptr(lat), R * C, None, L.ptr(Vt),
+               None, L.ptr(ws), ws.numel(), stream)
+        mark("critics")
+        mu, sg, a_mode = (torch.empty(B, T, A, device=dev) for _ in range(3))
+        ws = hip.workspace(dev).get("act", L.query("dr_actor_act_workspace_bytes", d, M))
+        L.call("dr_actor_act", d, ag.actor_struct(), M, L.ptr(hid), L.ptr(lat), L.dr_noise(), 1, L.ptr(a_mode),
+               L.ptr(mu), L.ptr(sg), L.ptr(ws), ws.numel(), stream)
+        mark("actor")
+        # slot t's stored transition leaves state t: real rewards (symexp of the ring's symlog) under the target values
+        Rl, Rmc, td, ce = (torch.empty(B, T - 1, device=dev) for _ in range(4))
+        L.call("dr_replay_returns", B, T, L.ptr(rew), S, L.ptr(cont), S, 1, L.ptr(Vt), ag.gamma, ag.lambda_, L.ptr(Rl),
+               L.ptr(Rmc), L.ptr(td), stream)
+        # the natural-space rewards as that kernel formed them: at gamma = 0 the recursion is r + 0, so
+        # returns_lambda follows from the result's own reward / cont / value_target bit for bit
+        r_nat = torch.empty(B, T - 1, device=dev)
+        L.call("dr_replay_returns", B, T, L.ptr(rew), S, L.ptr(cont), S, 1, L.ptr(Vt), 0.0, 0.0, L.ptr(r_nat), None,
+               None, stream)
+        mark("returns")
+        ent, std = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
+        L.call("dr_value_stats", B, T, T - 1, nb, L.ptr(logits), nb, L.ptr(ag.critic.buckets_crit), L.ptr(Rl),
+               L.ptr(ent), L.ptr(std), L.ptr(ce), stream)
+        mark("value_stats")
+        logp, hbase = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
+        logp_dims = torch.empty(B, T, A, device=dev)
+        L.call("dr_action_logprob", B, T, A, L.ptr(mu), L.ptr(sg), L.ptr(act), S * A, A, L.ptr(logp), L.ptr(logp_dims),
+               L.ptr(hbase), stream)
+        mark("logprob")
+        return AgentTraceResult(latents=lat, hiddens=hid, value=V, value_target=Vt, value_entropy=ent,
+                                value_std_symlog=std, critic_logits=logits, actor_mu=mu, actor_sigma=sg,
+                                actions=act[:, :T].clone(), action_logprob=logp, policy_entropy_base=hbase,
+                                action_logprob_dims=logp_dims, reward=r_nat,
+                                cont=cont[:, :T - 1].clone(), returns_lambda=Rl, returns_mc=Rmc, td=td, critic_ce=ce,
+                                length=T)
+
+    def evaluate_values(self, batches=1, batch_size=None, length=None, sample=True):
+        """Per-step agent-trace curves averaged over `batches` sampled batches
+        of windows: a dict of CPU float lists -- value, value_target,
+        value_entropy, value_std_symlog, action_logprob, actor_sigma (length
+        T), returns_lambda, returns_mc, abs_td, critic_ce, abs_advantage
+        (length T - 1) -- and the scalar explained_variance (the mean over the
+        batches).  Leaves np.random's state and the Philox {seed, offset} and
+        stream counter as it found them, like evaluate_filter."""
+        np_state = np.random.get_state()
+        ar = hip.adhoc(self.device)
+        rng_state, rng_counter = ar.state.clone(), ar.counter
+        keys = ("value", "value_target", "value_entropy", "value_std_symlog", "action_logprob", "actor_sigma",
+                "returns_lambda", "returns_mc", "abs_td", "critic_ce", "abs_advantage")
+        try:
+            acc, ev = None, 0.0
+            with torch.no_grad():
+                for _ in range(int(batches)):
+                    r = self.agent_trace(batch_size=batch_size, length=length, sample=sample)
+                    cur = [r.value.mean(0), r.value_target.mean(0), r.value_entropy.mean(0),
+                           r.value_std_symlog.mean(0), r.action_logprob.mean(0), r.actor_sigma.mean((0, 2)),
+                           r.returns_lambda.mean(0), r.returns_mc.mean(0), r.td.abs().mean(0), r.critic_ce.mean(0),
+                           r.advantage().abs().mean(0)]
+                    acc = cur if acc is None else [a + b for a, b in zip(acc, cur)]
+                    ev += float(r.explained_variance())
+        finally:
+            np.random.set_state(np_state)
+            ar.state.copy_(rng_state)
+            ar.counter = rng_counter
+        if acc is None:
+            raise ValueError("evaluate_values needs batches >= 1")
+        out = {k: (a / float(batches)).cpu().tolist() for k, a in zip(keys, acc)}
+        out["explained_variance"] = ev / float(batches)
+        return out
+
     # --------------------------------------------------------------- training
     @property
     def engine(self):

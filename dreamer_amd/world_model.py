@@ -258,10 +258,12 @@ class WorldModel(nn.Module):
                                   noise_q, heads=False)
         return out[0], out[1], out[2], out[3]
 
-    def _observe_trace(self, d, B, T, feat, act_ptr, act_sb, act_st, h_init, z_init, noise_q, heads=True):
+    def _observe_trace(self, d, B, T, feat, act_ptr, act_sb, act_st, h_init, z_init, noise_q, heads=True, prior=True):
+        """prior=False: the prior MLP is not run (prior_logits comes back None); the states' bits do not depend on it."""
         R, C, Hd = self.latent_num_rows, self.latent_num_columns, self.hidden_dims
         dev = feat.device
-        lat, plog, prlog = (torch.empty(B, T, R, C, device=dev) for _ in range(3))
+        lat, plog = (torch.empty(B, T, R, C, device=dev) for _ in range(2))
+        prlog = torch.empty(B, T, R, C, device=dev) if prior else None
         hid = torch.empty(B, T, Hd, device=dev)
         rew = cont = None
         if heads:

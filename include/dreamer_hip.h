@@ -541,6 +541,66 @@ int dr_frame_metrics(const dr_dims* d, int B, int T, const float* mu, const dr_f
 int dr_latent_stats(int M, int R, int C, const float* post_logits, const float* prior_logits, float* kl,
                     float* post_entropy, float* prior_entropy, float* kl_groups, hipStream_t stream);
 
+/* ---- agent trace on replay windows: what the actor and the critic make of
+ *      real data (Dreamer.agent_trace).  Slot t of a window holds the frame x_t,
+ *      the action a_t taken on seeing x_t and the symlog reward / continue flag
+ *      of that transition (rollout_policy, Dreamer.py:212); state t + 1's heads
+ *      are compared with slot t (unroll_model, WorldModel.py:113-123).
+ *      Three one-shot kernels without atomics: a row (a window, for the
+ *      returns) has the same bits at every batch size and position, and from
+ *      run to run.  M = 0 rows is a no-op; bad dimensions and missing pointers
+ *      give DR_E_INVALID before any launch. ---------------------------------- */
+/* compute_batched_R_lambda_returns (Agent.py:156-172) with H = T - 1 on real
+ * rewards and continues and the values V [B][T] of the T filtered states:
+ *   R_lambda[b][t] = r_t + gamma c_t ((1 - lam) V_{t+1} + lam R_lambda[b][t+1]),
+ *   R_lambda[b][T-2] = r_{T-2} + gamma c_{T-2} V_{T-1}
+ *   R_mc[b][t]: the same at lam = 1, the discounted real return bootstrapped
+ *               once at the window's end (may be NULL)
+ *   td[b][t]  = (r_t + gamma c_t V_{t+1}) - V_t (may be NULL)
+ * rewards / continues: window rows with strides rew_sb / cont_sb >= T - 1 (the
+ * [B][S] arrays dr_replay_gather writes), entries 0 .. T-2 read; outputs
+ * [B][T-1].  rewards_symlog != 0: the stored reward is in symlog space and goes
+ * through symexp with its clamp (DreamerUtils.py:35-37) first.  c = 0 cuts the
+ * recursion as in the reference.  One thread per window, dr_lambda_returns'
+ * expressions in its order (1 - lam formed in double, rounded once): with
+ * rewards_symlog = 0 R_lambda is bit for bit dr_lambda_returns(B, T - 1, ...),
+ * and for finite V R_mc is bit for bit dr_lambda_returns(..., lam = 1).
+ * B >= 0, T >= 2. */
+int dr_replay_returns(int B, int T, const float* rewards, long long rew_sb, const float* continues,
+                      long long cont_sb, int rewards_symlog, const float* V, float gamma, float lam,
+                      float* R_lambda, float* R_mc, float* td, hipStream_t stream);
+/* Per-row statistics of a bucket head's logits (Critic.forward, Agent.py:231-235):
+ * rows m = b*T + t of `logits`, row stride ldl >= nb.
+ *   entropy[b][t]    = H(softmax l)                              (may be NULL)
+ *   std_symlog[b][t] = sqrt(sum p (bucket - sum p bucket)^2), in bucket (symlog)
+ *                      units, in two passes                      (may be NULL)
+ *   ce[b][t], t < Tt = -sum twohot(symlog(target[b][t])) log_softmax(l)
+ *                      (Agent.py:127-135; to_twohot of DreamerUtils.py:39-50 with
+ *                      its clamps and the 1e-8; symlog and the two weights are
+ *                      formed in double, the log-probabilities in f32)
+ * target (natural-space returns) and ce are [B][Tt], 0 <= Tt <= T: row (b, t) has
+ * a target iff t < Tt (dr_critic_loss_bwd's row convention, so [B][T-1] returns
+ * go in unpadded).  The two are both given (Tt > 0) or both NULL (Tt = 0); at
+ * least one output is required.  2 <= nb <= 1024; buckets [nb] must be ascending
+ * (not checked).  One wave per row: lane-strided terms in ascending order, then
+ * a fixed wave tree; max-subtracted log-sum-exp, a class whose probability
+ * underflows adds exactly 0. */
+int dr_value_stats(int B, int T, int Tt, int nb, const float* logits, long long ldl, const float* buckets,
+                   const float* target, float* entropy, float* std_symlog, float* ce, hipStream_t stream);
+/* log-probability of recorded actions under a tanh-Normal policy (Agent.py:110-115):
+ * mu, sigma [B][T][A] (Actor.forward, Agent.py:191-200); action element
+ * (b, t, i) at actions[b*act_sb + t*act_st + i], as in dr_observe_trace.  Per
+ * dimension, with y = clamp(a, -1 + 1e-6, 1 - 1e-6) in f32 and x = atanh(y):
+ *   -(x - mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi) - 2 (log 2 - x - softplus(-2x))
+ *   logp[b][t]         = the sum of the A terms, in ascending order from 0
+ *   logp_dims[b][t][i] = the terms                                (may be NULL)
+ *   base_entropy[b][t] = sum_i (1/2 + 1/2 log(2 pi) + log sigma_i) (may be NULL)
+ * An action of exactly +-1 gives a finite value.  One thread per row.  A >= 1,
+ * T >= 1, B >= 0. */
+int dr_action_logprob(int B, int T, int A, const float* mu, const float* sigma, const float* actions,
+                      long long act_sb, long long act_st, float* logp, float* logp_dims, float* base_entropy,
+                      hipStream_t stream);
+
 /* ---- a1  replay gather (Buffer.sample_sequences, Buffer.py:49-61) --------- */
 int dr_replay_gather(long long cap, int B, int S, int frame_elems, int A, const unsigned char* frames,
                      const float* actions, const float* rewards, const float* continues,
