@@ -11,6 +11,7 @@ from .dreamer import Dreamer  # noqa: F401
 from .agent_trace import AgentTraceResult  # noqa: F401
 from .closed_loop import ClosedLoopResult  # noqa: F401
 from .open_loop import OpenLoopResult  # noqa: F401
+from .plan import PlanResult, check_plan  # noqa: F401
 from .networks import (ContinuePredictor, Decoder, DynamicsPredictor, Encoder, RewardPredictor,  # noqa: F401
                        SequenceModel)
 from .world_model import WorldModel  # noqa: F401

@@ -96,6 +96,8 @@ _SIGS = {
     "dr_replay_returns": (_i, [_i, _i, fp, _ll, fp, _ll, _i, fp, _f, _f, fp, fp, fp, fp]),
     "dr_value_stats": (_i, [_i, _i, _i, _i, fp, _ll, fp, fp, fp, fp, fp, fp]),
     "dr_action_logprob": (_i, [_i, _i, _i, fp, fp, fp, _ll, _ll, fp, fp, fp, fp]),
+    "dr_plan_sample": (_i, [_i, _i, _i, _i, _i, fp, fp, fp, dr_noise, fp, fp]),
+    "dr_plan_update": (_i, [_i, _i, _i, _i, _i, fp, fp, fp, _f, _f, _f, _f, _f, fp, fp, fp, fp, fp, fp, fp, fp]),
     "dr_imagine_tape_bytes":(_sz, [_P(dr_dims), _i, _i]),
     "dr_imagine_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
     "dr_imagine_fwd": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_actor), _i, _i, fp, fp, dr_noise, _i,
@@ -189,6 +191,8 @@ def load():
 DR_E_INVALID, DR_E_HIP, DR_E_WORKSPACE, DR_E_UNSUPPORTED = 1001, 1002, 1003, 1004
 DR_ACT_MAX_ENVS = 16  # include/dreamer_hip.h: rows of one dr_act_batch / dr_act_vec launch
 DR_ACT_VEC_MAX_OBS = 1023  # include/dreamer_hip.h: widest observation vector dr_act_vec takes
+DR_PLAN_MAX_CANDIDATES = 2048  # include/dreamer_hip.h: candidates per environment of dr_plan_sample / dr_plan_update
+DR_PLAN_MAX_ELEMS = 1024  # include/dreamer_hip.h: H * A of one planned action sequence
 
 
 class HipError(RuntimeError):

@@ -1178,6 +1178,60 @@ class Dreamer(nn.Module):
                     state = tuple(t.index_select(0, idx) for t in (latent, hidden, action))
         return torch.tensor(totals, dtype=torch.float32, device=self.device).mean()
 
+    # ------------------------------------------------- latent planning (HIP)
+    def plan(self, z, h, horizon=None, candidates=512, policy_candidates=24, elites=64, iterations=6,
+             temperature=0.5, momentum=0.1, std_init=0.5, std_min=0.05, std_max=2.0, mean_init=None, sample=True,
+             bootstrap="critic", noise=None, _mark=None):
+        """Choose actions by a CEM / MPPI search over world-model rollouts
+        (plan.py; the definitions are in include/dreamer_hip.h).  z (E, R*C) or
+        the (E,1,R,C) act_step_batch returns, h (E, hidden) or (E,1,hidden): the
+        belief states of E environments.  Per environment `candidates` action
+        sequences of `horizon` (default self.horizon) steps are drawn around a
+        mean (mean_init (E,H,A), default zeros) with std_init, the first
+        `policy_candidates` of them the sampling actor's own; they are rolled
+        out through the prior (dr_imagine_actions), scored by their discounted
+        predicted rewards (gamma is the agent's) plus the value of the end state
+        (bootstrap: "critic", "target" for the target critic, None for 0), and
+        the best `elites` refit mean and std (weights exp((G - G_best) /
+        temperature), all 1 at temperature 0; mean <- momentum mean + (1 -
+        momentum) m; std clamped to [std_min, std_max]), `iterations` times.
+        Returns a PlanResult; its action is the final mean's first step.
+
+        sample=False takes the prior's mode (q == 1) in every rollout, as
+        open_loop does.  noise: a pair (eps (J,E,N,H*A), q (J,H,E*N*R,C)) of
+        explicit N(0,1) / Exp(1) draws (either may be None: Philox, or the mode);
+        the actor's sequence (e, n) then takes the draws of candidate (e, n) of
+        iteration 0.  Every argument is checked (plan.check_plan, ValueError)
+        before the device is touched.  Everything is enqueued on the current
+        stream without a sync, every launch in launch form (never a persistent
+        kernel: the planner may run beside training); the engine's random state
+        is not used.  _mark: stage hook of tools/plan_timing.py."""
+        from .plan import plan
+        return plan(self, z, h, horizon=horizon, candidates=candidates, policy_candidates=policy_candidates,
+                    elites=elites, iterations=iterations, temperature=temperature, momentum=momentum,
+                    std_init=std_init, std_min=std_min, std_max=std_max, mean_init=mean_init, sample=sample,
+                    bootstrap=bootstrap, noise=noise, _mark=_mark)
+
+    def plan_step(self, observations, state=None, first=None, plan_state=None, **plan_kw):
+        """One env step of E environments under the planner: the filter of
+        act_step_batch(observations, state, first, deterministic=True), then
+        plan on its (z', h').  plan_state: the previous step's PlanResult (its
+        shifted() mean warm-starts the search) or an (E,H,A) mean; rows with
+        `first` start from zeros.  A row whose search ended without an elite
+        (PlanResult.ok false) takes the actor's deterministic action.  Returns
+        (actions (E,1,A), (z', h', actions), PlanResult): the state tuple feeds
+        the next call as act_step_batch's does."""
+        from .plan import plan_step
+        return plan_step(self, observations, state=state, first=first, plan_state=plan_state, **plan_kw)
+
+    def evaluate_planner(self, envs, eval_episodes, **plan_kw):
+        """evaluate_agent_vec with plan_step in place of act_step_batch: the
+        same seeds, episode order and bookkeeping; each env's plan is warm-
+        started from its previous step's.  Returns the mean total reward (taken
+        in episode order) as a device scalar."""
+        from .plan import evaluate_planner
+        return evaluate_planner(self, envs, eval_episodes, **plan_kw)
+
     def train_dreamer(self, env, eval_env):  # Dreamer.py:324-372
         """A list or tuple of environments in either position selects the
         vectorised methods (rollout_policy_vec / evaluate_agent_vec) for it."""

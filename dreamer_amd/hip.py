@@ -150,6 +150,22 @@ class noise_override:
         return False
 
 
+class noise_override_suspended:
+    """Sets any enclosing noise_override aside for the block: for a call whose
+    ad-hoc draws are not shaped like the acting step's (Dreamer.plan rolls out
+    E*N rows; the override's variates would be read out of their bounds).
+    Such a call takes its explicit draws as an argument instead."""
+
+    def __enter__(self):
+        self.saved = _override[:]
+        del _override[:]
+        return self
+
+    def __exit__(self, *exc):
+        _override[:] = self.saved
+        return False
+
+
 def explicit_noise(q=None, eps=None, device=None):
     """dr_noise reading caller-supplied variates (parity mode)."""
     st = rng(device).state.data_ptr() if device is not None else None

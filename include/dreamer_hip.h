@@ -601,6 +601,70 @@ int dr_action_logprob(int B, int T, int A, const float* mu, const float* sigma, 
                       long long act_sb, long long act_st, float* logp, float* logp_dims, float* base_entropy,
                       hipStream_t stream);
 
+/* ---- latent planning: CEM / MPPI action search over world-model rollouts ----
+ * (dreamer_amd/plan.py, Dreamer.plan; no reference counterpart: the reference's
+ * only controller is the actor's forward pass, Dreamer.py:295-322.)
+ *
+ * E >= 1 environments, each with a belief state (h_e, z_e); horizon H >= 1; N
+ * candidate action sequences per environment, the first N_pi >= 0 of them the
+ * actor's; 1 <= K <= N elites; J >= 1 iterations.  Per environment the search
+ * keeps mean[H][A] and std[H][A].  One iteration:
+ *  1. sample   candidate (e, n): for n < N_pi the n-th actor sequence, else
+ *              a[k][i] = clamp(mean[k][i] + std[k][i] * eps, -1, 1) in f32 (one
+ *              multiply, one add, no contraction)                [dr_plan_sample]
+ *  2. roll out the E*N rows from the replicated (h_e, z_e): r_k, c_k [E*N][H],
+ *              entry k-1 on state k                          [dr_imagine_actions]
+ *  3. bootstrap V_H = the critic's value of state H of every row, read with the
+ *              row stride (H+1)*width from the rollout's arrays (or V_H = 0)
+ *                                                                 [dr_critic_fwd]
+ *  4. score    G = R_0, R_H = V_H, R_k = r_{k+1} + (gamma c_{k+1}) R_{k+1}:
+ *              k_lambda_returns' expressions at lam = 1 in its order, the
+ *              intermediate values it multiplies by 1 - lam = 0 taken as +0.  For
+ *              finite V with column H = V_H, G is bit for bit column 0 of
+ *              dr_lambda_returns(E*N, H, r, c, V, gamma, 1)
+ *  5. rank     within an environment by score descending, ties by the lower
+ *              candidate index.  A non-finite score (NaN, +-Inf) ranks after
+ *              every finite one and is never an elite: K' = min(K, number of
+ *              finite scores) elites
+ *  6. weights  in rank order j = 0..K'-1: w_j = 1 when temperature = 0 (CEM),
+ *              else w_j = exp((G_j - G_0) / temperature) (MPPI);  W = sum w_j,
+ *              added in rank order from 0.0f
+ *  7. refit    per element (k, i), sequentially in rank order, in f32:
+ *              m = (sum w_j a_j) / W;  s = sqrt((sum w_j (a_j - m)^2) / W) in a
+ *              second pass, then min(max(s, std_min), std_max);
+ *              mean <- momentum * mean + (1 - momentum) * m  (1 - momentum formed
+ *              in f32);  std <- s.  K' = 0: mean and std keep their bits.
+ * Steps 4 to 7 are dr_plan_update.  After J iterations the action is the final
+ * mean's first step.
+ *
+ * Both entry points are one-shot launches (nothing shared between workgroups,
+ * no atomics, no waits); an environment's outputs are the same bits at every E
+ * and position in the batch and from run to run.  E = 0 is a no-op.  Bad
+ * dimensions or missing pointers: DR_E_INVALID before any launch; N >
+ * DR_PLAN_MAX_CANDIDATES (one environment's scores, elite indices and weights
+ * sit in LDS) or H * A > DR_PLAN_MAX_ELEMS: DR_E_UNSUPPORTED.
+ *
+ * dr_plan_sample: mean, std [E][H][A]; policy_actions [E][N_pi][H][A], NULL
+ * exactly when N_pi = 0; actions [E][N][H][A] (out).  Explicit noise: noise.eps
+ * [E][N][H*A], read only for n >= N_pi (noise.q is not used); otherwise Philox:
+ * dr_normal on noise.stream, row (noise.row0 + e) * N + n, element k * A + i.
+ * One thread per element.
+ *
+ * dr_plan_update: rewards, continues [E*N][H]; v_last [E*N] or NULL (V_H = 0);
+ * actions [E][N][H][A]; mean, std [E][H][A] (in/out).  Outputs: scores [E][N]
+ * (the raw value, non-finite included), elite_idx [E][K] in rank order (-1 past
+ * K'), elite_w [E][K] (w_j / W, 0 past K'), n_elite [E] (K').  Needs
+ * temperature >= 0, 0 <= momentum < 1, 0 <= std_min <= std_max.  One 256-thread
+ * workgroup per environment; ranks by counting in LDS. */
+#define DR_PLAN_MAX_CANDIDATES 2048
+#define DR_PLAN_MAX_ELEMS 1024
+int dr_plan_sample(int E, int N, int N_pi, int H, int A, const float* mean, const float* std,
+                   const float* policy_actions, dr_noise noise, float* actions, hipStream_t stream);
+int dr_plan_update(int E, int N, int H, int A, int K, const float* rewards, const float* continues,
+                   const float* v_last, float gamma, float temperature, float momentum, float std_min,
+                   float std_max, const float* actions, float* mean, float* std, float* scores, int* elite_idx,
+                   float* elite_w, int* n_elite, hipStream_t stream);
+
 /* ---- a1  replay gather (Buffer.sample_sequences, Buffer.py:49-61) --------- */
 int dr_replay_gather(long long cap, int B, int S, int frame_elems, int A, const unsigned char* frames,
                      const float* actions, const float* rewards, const float* continues,
