@@ -10,6 +10,7 @@ from .buffer import Buffer  # noqa: F401
 from .dreamer import Dreamer  # noqa: F401
 from .agent_trace import AgentTraceResult  # noqa: F401
 from .closed_loop import ClosedLoopResult  # noqa: F401
+from .futures import FuturesResult  # noqa: F401
 from .open_loop import OpenLoopResult  # noqa: F401
 from .plan import PlanResult, check_plan  # noqa: F401
 from .networks import (ContinuePredictor, Decoder, DynamicsPredictor, Encoder, RewardPredictor,  # noqa: F401

@@ -156,6 +156,8 @@ _SIGS = {
     "dr_decoder_workspace_bytes": (_sz, [_P(dr_dims), _i]),
     "dr_decoder_fwd": (_i, [_P(dr_dims), _P(dr_decoder), _i, fp, _ll, fp, _ll, fp, fp, _sz, fp]),
     "dr_frame_metrics": (_i, [_P(dr_dims), _i, _i, fp, _P(dr_frames), fp, fp, fp, fp]),
+    "dr_frame_ssim": (_i, [_P(dr_dims), _i, _i, fp, _P(dr_frames), fp, fp, fp]),
+    "dr_ensemble_metrics": (_i, [_P(dr_dims), _i, _i, _i, fp, _P(dr_frames), fp, fp, fp, fp, fp, fp]),
     "dr_wm_train_phase": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_decoder), _i, _i, _P(dr_frames),
                                _P(dr_wm_batch), dr_noise, dr_wm_loss_cfg, _i, fp, _i, fp, fp, _P(dr_world_model),
                                _P(dr_decoder), fp, fp, fp, fp, _sz, fp]),
@@ -192,6 +194,7 @@ DR_E_INVALID, DR_E_HIP, DR_E_WORKSPACE, DR_E_UNSUPPORTED = 1001, 1002, 1003, 100
 DR_ACT_MAX_ENVS = 16  # include/dreamer_hip.h: rows of one dr_act_batch / dr_act_vec launch
 DR_ACT_VEC_MAX_OBS = 1023  # include/dreamer_hip.h: widest observation vector dr_act_vec takes
 DR_PLAN_MAX_CANDIDATES = 2048  # include/dreamer_hip.h: candidates per environment of dr_plan_sample / dr_plan_update
+DR_ENSEMBLE_MAX_SAMPLES = 64  # include/dreamer_hip.h: futures per window of dr_ensemble_metrics
 DR_PLAN_MAX_ELEMS = 1024  # include/dreamer_hip.h: H * A of one planned action sequence
 
 

@@ -123,6 +123,24 @@ class ClosedLoopResult:
         self._need_prior("psnr_prior()")
         return self._psnr(self.frames_prior)
 
+    def ssim_post(self):
+        """SSIM of the reconstruction per frame (B,T) (dr_frame_ssim), computed
+        on demand on the current stream."""
+        self._need_frames("ssim_post()")
+        from .futures import frame_ssim
+        return frame_ssim(self.mu_post, self.frames_true)
+
+    def ssim_prior(self):
+        """SSIM of the one-step prediction per frame (B,T), as ssim_post."""
+        self._need_frames("ssim_prior()")
+        self._need_prior("ssim_prior()")
+        from .futures import frame_ssim
+        return frame_ssim(self.mu_prior, self.frames_true)
+
+    def ssim(self):
+        """(ssim_post(), ssim_prior()); the second is None without the one-step prediction."""
+        return self.ssim_post(), (self.ssim_prior() if self.sqerr_prior is not None else None)
+
     def video(self):
         """u8 [T][3][3h][B*w]: per step, the true frames above the posterior
         reconstructions above the one-step predictions, the B windows side by side."""

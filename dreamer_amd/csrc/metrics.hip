@@ -121,6 +121,338 @@ extern "C" int dr_frame_metrics(const dr_dims* d, int B, int T, const float* mu,
 }
 
 // ---------------------------------------------------------------------------
+// Sampled futures on replay windows (futures.py): SSIM of decoded frames and
+// the mean / spread of M decoded futures, both against the ring's true frames.
+// ---------------------------------------------------------------------------
+
+// the true frame (b, t) of a dr_frames source (t0 included), as k_frame_metrics reads it
+struct FmTruth {
+  const unsigned char* r8;  // u8 ring frame, or nullptr
+  const float* rf;          // f32 frame (the vector ring's row, or the f32 form)
+  bool raw;                 // rf holds 0..255
+};
+__device__ __forceinline__ FmTruth fm_truth(const dr_frames& src, int b, int t, int n, int vector) {
+  FmTruth f = {nullptr, nullptr, false};
+  const int tt = t + src.t0;
+  if (src.ring) {
+    long long slot = (src.starts[b] + tt) % src.ring_cap;
+    if (slot < 0) slot += src.ring_cap;
+    if (vector) f.rf = reinterpret_cast<const float*>(src.ring) + slot * n;
+    else f.r8 = src.ring + slot * n;
+  } else {
+    f.rf = src.obs + (long long)b * src.stride_b + (long long)tt * src.stride_t;
+  }
+  f.raw = !vector && src.raw255;
+  return f;
+}
+
+// u8 of a per-element standard deviation: min(255, rint(255 sqrt(var)))
+__device__ __forceinline__ unsigned char fm_quant_std(float var) {
+  return (unsigned char)fminf(255.0f, rintf(255.0f * sqrtf(var)));
+}
+
+// SSIM window: g_k = exp(-(k - 5)^2 / 4.5), k = 0 .. 10, normalised to sum 1 in
+// double and rounded to f32 once (the literals are those f32 values exactly)
+__device__ constexpr float c_ssim_w[11] = {0x1.0d956cp-10f, 0x1.f1fe02p-8f, 0x1.26eb18p-5f, 0x1.bff0fep-4f,
+                                   0x1.b43c4p-3f,   0x1.10656p-2f,  0x1.b43c4p-3f,  0x1.bff0fep-4f,
+                                   0x1.26eb18p-5f,  0x1.f1fe02p-8f, 0x1.0d956cp-10f};
+#define SSIM_SH 8               // frame rows staged per strip (a multiple of 4: the 16-byte loads)
+#define SSIM_RB (SSIM_SH + 10)  // rows of the ring of horizontally filtered rows
+#define SSIM_MAX_LDS 65536
+
+static inline size_t ssim_lds_bytes(int W) {
+  return sizeof(float) * ((size_t)2 * SSIM_SH * W + (size_t)5 * SSIM_RB * (W - 10));
+}
+
+// One 256-thread workgroup per frame m = b*T + t; the three channels in turn.
+// A channel goes through LDS in strips of SSIM_SH rows, each element read from
+// global memory once (VEC: 16-byte loads of mu, 4-byte loads of four u8 pixels;
+// the conditions are dr_frame_metrics' plus H*W % 4 == 0):
+//   1. the strip's clamped predictions p and true values x -> sp, sx [SH][W];
+//   2. the window along W, taps ascending, at the W - 10 valid columns of each
+//      staged row: the five planes  sum w p, w x, w p^2, w x^2, w p x  go to
+//      row (frame row % SSIM_RB) of the ring f[5][SSIM_RB][W - 10];
+//   3. every output row o whose rows o .. o + 10 are now in the ring (o up to
+//      strip end - 11; the ring keeps the last 10 rows of the strips before):
+//      the window along H, taps ascending, then the map.
+// Work items of 2 and 3 are (row, column) in row-major order, item tid, tid +
+// 256, ...: a thread adds its map values in ascending position order over the
+// whole channel; then wave_sum's tree, the four wave sums in wave order, the
+// division by the number of positions; ssim = ((ch0 + ch1) + ch2) / 3.
+// Nothing is shared between workgroups.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_frame_ssim(int T, int H, int W, const float* __restrict__ mu, dr_frames src,
+                                                    float* __restrict__ ssim, float* __restrict__ ssim_ch) {
+  extern __shared__ __align__(16) float ssim_lds[];
+  __shared__ float part[4];
+  __shared__ float chv[3];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int b = m / T, t = m - b * T;
+  const int Wv = W - 10, Hv = H - 10;
+  const int n = 3 * H * W;
+  float* sp = ssim_lds;
+  float* sx = sp + SSIM_SH * W;
+  float* f = sx + SSIM_SH * W;
+  const int plane = SSIM_RB * Wv;
+  const float* mum = mu + (long long)m * n;
+  const FmTruth tr = fm_truth(src, b, t, n, 0);
+  const float C1 = 1e-4f, C2 = 9e-4f;
+  for (int ch = 0; ch < 3; ++ch) {
+    float acc = 0.0f;
+    for (int r0 = 0; r0 < H; r0 += SSIM_SH) {
+      const int rows = min(SSIM_SH, H - r0);
+      const int cnt = rows * W;
+      const int e0 = (ch * H + r0) * W;  // first element of the strip in the frame
+      // 1. stage the strip (the previous strip's readers of sp / sx are past the second barrier)
+      if (VEC) {
+        for (int g = tid; g < (cnt >> 2); g += 256) {
+          const float4 mv = reinterpret_cast<const float4*>(mum + e0)[g];
+          float4 xv;
+          if (tr.r8) {
+            const uchar4 tq = reinterpret_cast<const uchar4*>(tr.r8 + e0)[g];
+            xv = make_float4(fm_norm((float)tq.x), fm_norm((float)tq.y), fm_norm((float)tq.z), fm_norm((float)tq.w));
+          } else {
+            xv = reinterpret_cast<const float4*>(tr.rf + e0)[g];
+            if (tr.raw) xv = make_float4(fm_norm(xv.x), fm_norm(xv.y), fm_norm(xv.z), fm_norm(xv.w));
+          }
+          reinterpret_cast<float4*>(sp)[g] = make_float4(fminf(0.5f, fmaxf(-0.5f, mv.x)), fminf(0.5f, fmaxf(-0.5f, mv.y)),
+                                                         fminf(0.5f, fmaxf(-0.5f, mv.z)), fminf(0.5f, fmaxf(-0.5f, mv.w)));
+          reinterpret_cast<float4*>(sx)[g] = xv;
+        }
+      } else {
+        for (int i = tid; i < cnt; i += 256) {
+          float x;
+          if (tr.r8) x = fm_norm((float)tr.r8[e0 + i]);
+          else x = tr.raw ? fm_norm(tr.rf[e0 + i]) : tr.rf[e0 + i];
+          sp[i] = fminf(0.5f, fmaxf(-0.5f, mum[e0 + i]));
+          sx[i] = x;
+        }
+      }
+      __syncthreads();
+      // 2. along W
+      for (int i = tid; i < rows * Wv; i += 256) {
+        const int r = i / Wv, c = i - r * Wv;
+        const float* pr = sp + r * W + c;
+        const float* xr = sx + r * W + c;
+        float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, s4 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+          const float w = c_ssim_w[k], p = pr[k], x = xr[k];
+          s0 = s0 + w * p;
+          s1 = s1 + w * x;
+          s2 = s2 + w * (p * p);
+          s3 = s3 + w * (x * x);
+          s4 = s4 + w * (p * x);
+        }
+        float* fo = f + ((r0 + r) % SSIM_RB) * Wv + c;
+        fo[0] = s0;
+        fo[plane] = s1;
+        fo[2 * plane] = s2;
+        fo[3 * plane] = s3;
+        fo[4 * plane] = s4;
+      }
+      __syncthreads();
+      // 3. along H and the map, for the output rows completed by this strip
+      const int o_lo = max(0, r0 - 10), o_hi = r0 + rows - 11;  // (inclusive; empty while fewer than 11 rows are in)
+      for (int i = tid; i < (o_hi - o_lo + 1) * Wv; i += 256) {
+        const int ro = i / Wv, c = i - ro * Wv;
+        int slot = (o_lo + ro) % SSIM_RB;
+        float mp = 0.0f, mx = 0.0f, spp = 0.0f, sxx = 0.0f, spx = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+          const float w = c_ssim_w[k];
+          const float* fi = f + slot * Wv + c;
+          mp = mp + w * fi[0];
+          mx = mx + w * fi[plane];
+          spp = spp + w * fi[2 * plane];
+          sxx = sxx + w * fi[3 * plane];
+          spx = spx + w * fi[4 * plane];
+          slot = slot + 1 == SSIM_RB ? 0 : slot + 1;
+        }
+        const float vp = spp - mp * mp, vx = sxx - mx * mx, cv = spx - mp * mx;
+        const float up = mp + 0.5f, ux = mx + 0.5f;
+        const float num = (2.0f * up * ux + C1) * (2.0f * cv + C2);
+        const float den = (up * up + ux * ux + C1) * (vp + vx + C2);
+        acc = acc + num / den;
+      }
+      // (the next strip's stage 2 writes the ring only after its first barrier, which every reader here reaches first)
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) part[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) chv[ch] = (((part[0] + part[1]) + part[2]) + part[3]) / (float)(Hv * Wv);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    ssim[m] = ((chv[0] + chv[1]) + chv[2]) / 3.0f;
+    if (ssim_ch) {
+      ssim_ch[(long long)m * 3 + 0] = chv[0];
+      ssim_ch[(long long)m * 3 + 1] = chv[1];
+      ssim_ch[(long long)m * 3 + 2] = chv[2];
+    }
+  }
+}
+
+extern "C" int dr_frame_ssim(const dr_dims* d, int B, int T, const float* mu, const dr_frames* truth, float* ssim,
+                             float* ssim_ch, hipStream_t s) {
+  DR_REQUIRE(d && mu && truth && ssim && B > 0 && T > 0, "null argument or empty batch");
+  DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many frames");
+  DR_REQUIRE(d->obs_dim == 0, "SSIM needs pixel observations (obs_dim > 0 is a vector model)");
+  DR_REQUIRE(d->img_h > 0 && d->img_w > 0, "bad frame size");
+  const int H = d->img_h, W = d->img_w;
+  DR_REQUIRE(3LL * H * W <= 0x7fffffffLL, "frame too large");
+  DR_REQUIRE(truth->t0 >= 0, "negative t0");
+  if (truth->ring) DR_REQUIRE(truth->starts && truth->ring_cap > 0, "ring source needs starts and ring_cap");
+  else DR_REQUIRE(truth->obs, "no truth frames");
+  if (H < 11 || W < 11) {
+    dr_set_error("%s: frames of %d x %d are smaller than the 11 x 11 window", __func__, H, W);
+    return DR_E_UNSUPPORTED;
+  }
+  const size_t lds = ssim_lds_bytes(W);
+  if (lds > SSIM_MAX_LDS) {
+    dr_set_error("%s: a strip of %d-pixel rows needs %zu bytes of LDS (limit %d)", __func__, W, lds, SSIM_MAX_LDS);
+    return DR_E_UNSUPPORTED;
+  }
+  const auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  bool vec = ((long long)H * W) % 4 == 0 && al(mu, 16);
+  if (truth->ring) vec = vec && al(truth->ring, 4);
+  else vec = vec && al(truth->obs, 16) && truth->stride_b % 4 == 0 && truth->stride_t % 4 == 0;
+  const dim3 grid((unsigned)(B * T)), block(256);
+  if (vec) hipLaunchKernelGGL(k_frame_ssim<true>, grid, block, lds, s, T, H, W, mu, *truth, ssim, ssim_ch);
+  else hipLaunchKernelGGL(k_frame_ssim<false>, grid, block, lds, s, T, H, W, mu, *truth, ssim, ssim_ch);
+  return dr_check_launch("frame_ssim");
+}
+
+// Mean and spread of M decoded futures per window: one 256-thread workgroup
+// per (b, t); sample m's frame is row (b*M + m)*T + t of mu.  Elements go to
+// threads as in k_frame_metrics (VEC: 4-element groups tid, tid + 256, ...;
+// else elements tid, tid + 256, ...), per element
+//   mean = (sum_m mu_m) / (float)M            (m ascending from 0.0f)
+//   var  = (sum_m (mu_m - mean)^2) / (float)M (a second pass over the M values)
+// and the two frame sums -- (mean - x)^2 and var -- are reduced as sqerr is
+// there.  M = 1: mean == mu and var == 0 exactly, so sqerr_mean is
+// k_frame_metrics' sqerr bit for bit (same VEC class).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ensemble_metrics(int Ms, int T, int n, int vector,
+                                                          const float* __restrict__ mu, dr_frames src,
+                                                          float* __restrict__ sqerr_mean, float* __restrict__ spread,
+                                                          unsigned char* __restrict__ mean_u8,
+                                                          unsigned char* __restrict__ std_u8,
+                                                          float* __restrict__ mean_f32) {
+  __shared__ float part[2][4];
+  const int w = blockIdx.x, tid = threadIdx.x;
+  const int b = w / T, t = w - b * T;
+  const FmTruth tr = fm_truth(src, b, t, n, vector);
+  const float* mu0 = mu + ((long long)b * Ms * T + t) * n;  // sample 0; sample m is m * T * n further
+  const long long sm = (long long)T * n;
+  unsigned char* mq = mean_u8 ? mean_u8 + (long long)w * n : nullptr;
+  unsigned char* sq = std_u8 ? std_u8 + (long long)w * n : nullptr;
+  float* mf = mean_f32 ? mean_f32 + (long long)w * n : nullptr;
+  const float fM = (float)Ms;
+  float a_err = 0.0f, a_var = 0.0f;
+  if (VEC) {
+    for (int g = tid; g < (n >> 2); g += 256) {
+      float sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int k = 0; k < Ms; ++k) {
+        const float4 v = reinterpret_cast<const float4*>(mu0 + k * sm)[g];
+        sum[0] = sum[0] + v.x; sum[1] = sum[1] + v.y; sum[2] = sum[2] + v.z; sum[3] = sum[3] + v.w;
+      }
+      float mean[4], var[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) mean[e] = sum[e] / fM;
+      for (int k = 0; k < Ms; ++k) {
+        const float4 v = reinterpret_cast<const float4*>(mu0 + k * sm)[g];
+        const float dv[4] = {v.x - mean[0], v.y - mean[1], v.z - mean[2], v.w - mean[3]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) var[e] = var[e] + dv[e] * dv[e];
+      }
+      float x[4];
+      if (tr.r8) {
+        const uchar4 tq = reinterpret_cast<const uchar4*>(tr.r8)[g];
+        x[0] = fm_norm((float)tq.x); x[1] = fm_norm((float)tq.y);
+        x[2] = fm_norm((float)tq.z); x[3] = fm_norm((float)tq.w);
+      } else {
+        const float4 fv = reinterpret_cast<const float4*>(tr.rf)[g];
+        const float v[4] = {fv.x, fv.y, fv.z, fv.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = tr.raw ? fm_norm(v[e]) : v[e];
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        var[e] = var[e] / fM;
+        const float dv = mean[e] - x[e];
+        a_err = a_err + dv * dv;
+        a_var = a_var + var[e];
+      }
+      if (mq) reinterpret_cast<uchar4*>(mq)[g] = make_uchar4(fm_quant(mean[0]), fm_quant(mean[1]), fm_quant(mean[2]),
+                                                              fm_quant(mean[3]));
+      if (sq) reinterpret_cast<uchar4*>(sq)[g] = make_uchar4(fm_quant_std(var[0]), fm_quant_std(var[1]),
+                                                              fm_quant_std(var[2]), fm_quant_std(var[3]));
+      if (mf) reinterpret_cast<float4*>(mf)[g] = make_float4(mean[0], mean[1], mean[2], mean[3]);
+    }
+  } else {
+    for (int i = tid; i < n; i += 256) {
+      float sum = 0.0f;
+      for (int k = 0; k < Ms; ++k) sum = sum + mu0[k * sm + i];
+      const float mean = sum / fM;
+      float var = 0.0f;
+      for (int k = 0; k < Ms; ++k) {
+        const float dv = mu0[k * sm + i] - mean;
+        var = var + dv * dv;
+      }
+      var = var / fM;
+      float x;
+      if (tr.r8) x = fm_norm((float)tr.r8[i]);
+      else x = tr.raw ? fm_norm(tr.rf[i]) : tr.rf[i];
+      const float dv = mean - x;
+      a_err = a_err + dv * dv;
+      a_var = a_var + var;
+      if (mq) mq[i] = fm_quant(mean);
+      if (sq) sq[i] = fm_quant_std(var);
+      if (mf) mf[i] = mean;
+    }
+  }
+  a_err = wave_sum(a_err);
+  a_var = wave_sum(a_var);
+  if ((tid & 63) == 0) {
+    part[0][tid >> 6] = a_err;
+    part[1][tid >> 6] = a_var;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    sqerr_mean[w] = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3];
+    spread[w] = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
+  }
+}
+
+extern "C" int dr_ensemble_metrics(const dr_dims* d, int B, int M, int T, const float* mu, const dr_frames* truth,
+                                   float* sqerr_mean, float* spread, unsigned char* mean_u8, unsigned char* std_u8,
+                                   float* mean_f32, hipStream_t s) {
+  DR_REQUIRE(d && mu && truth && sqerr_mean && spread && B > 0 && T > 0, "null argument or empty batch");
+  DR_REQUIRE(M >= 1 && M <= 64, "need 1 <= M <= 64");
+  DR_REQUIRE((long long)B * M * T <= 0x7fffffffLL, "too many frames");
+  const int vector = d->obs_dim > 0;
+  DR_REQUIRE(!vector || (!mean_u8 && !std_u8), "vector observations have no u8 frames (mean_u8 / std_u8 must be NULL)");
+  DR_REQUIRE(!vector || d->obs_dim <= 1023, "obs_dim > 1023");
+  DR_REQUIRE(vector || (d->img_h > 0 && d->img_w > 0), "bad frame size");
+  const long long n = vector ? d->obs_dim : 3LL * d->img_h * d->img_w;
+  DR_REQUIRE(n <= 0x7fffffffLL, "frame too large");
+  DR_REQUIRE(truth->t0 >= 0, "negative t0");
+  if (truth->ring) DR_REQUIRE(truth->starts && truth->ring_cap > 0, "ring source needs starts and ring_cap");
+  else DR_REQUIRE(truth->obs, "no truth frames");
+  const auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+  bool vec = n % 4 == 0 && al(mu, 16) && al(mean_u8, 4) && al(std_u8, 4) && al(mean_f32, 16);
+  if (truth->ring) vec = vec && al(truth->ring, vector ? 16 : 4);
+  else vec = vec && al(truth->obs, 16) && truth->stride_b % 4 == 0 && truth->stride_t % 4 == 0;
+  const dim3 grid((unsigned)(B * T)), block(256);
+  if (vec) hipLaunchKernelGGL(k_ensemble_metrics<true>, grid, block, 0, s, M, T, (int)n, vector, mu, *truth, sqerr_mean,
+                              spread, mean_u8, std_u8, mean_f32);
+  else hipLaunchKernelGGL(k_ensemble_metrics<false>, grid, block, 0, s, M, T, (int)n, vector, mu, *truth, sqerr_mean,
+                          spread, mean_u8, std_u8, mean_f32);
+  return dr_check_launch("ensemble_metrics");
+}
+
+// ---------------------------------------------------------------------------
 // Latent statistics of the posterior trace: per row m of [M][R][C] raw logits
 // (no unimix, as the loss takes them, WorldModel.py:175-181)
 //   kl[m]            = sum_r KL(Cat(logits = post[m][r]) || Cat(logits = prior[m][r]))

@@ -291,6 +291,42 @@ class Dreamer(nn.Module):
         out = [None if a is None else (a / float(batches)).cpu().tolist() for a in acc]
         return {"mse": out[0], "psnr": out[1], "reward_abs_err": out[2], "continue_bce": out[3]}
 
+    def sample_futures(self, starts=None, batch_size=None, context=None, horizon=None, samples=8, noise=None,
+                       ssim=True, _mark=None):
+        """M = `samples` futures per replay window (futures.py; the metric
+        definitions are in include/dreamer_hip.h): open_loop's gather, encoder
+        and context filter once for the B windows (same defaults, same
+        check_lengths), the posterior and the recorded actions replicated M
+        times (rollout row b*M + m), one dr_imagine_actions at B*M rows -- the
+        prior's draws are keyed by row, so the replicas differ -- one
+        dr_decoder_fwd over the B*M*(H+1) states, dr_frame_metrics on the B*M
+        rows (and dr_frame_ssim, pixel models with ssim=True), then
+        dr_ensemble_metrics for the mean frame's error and the spread.  Returns
+        a FuturesResult (best(), mse / psnr / ssim_curve in mean / best /
+        best_sample / ensemble variants, coverage(), reward_spread(), video()).
+
+        samples: an integer in 1 .. 64 with B * samples <= plan.PLAN_MAX_ROWS
+        (ValueError otherwise).  noise: optional pair of explicit Exp(1) draws
+        (q_context (Tc, B*R, C), q (H, B*M*R, C)), else Philox.  Everything
+        runs on the current stream without a sync.  _mark: stage hook of
+        tools/futures_timing.py."""
+        from .futures import sample_futures
+        return sample_futures(self, starts=starts, batch_size=batch_size, context=context, horizon=horizon,
+                              samples=samples, noise=noise, ssim=ssim, _mark=_mark)
+
+    def evaluate_futures(self, batches=1, batch_size=None, context=None, horizon=None, samples=8):
+        """Per-step curves of sample_futures averaged over `batches` sampled
+        batches of windows: a dict of CPU float lists -- mse_mean, mse_best (the
+        smallest of the M per step and window), mse_ensemble, spread (per
+        element), psnr_mean, psnr_best, ssim_mean, ssim_best, coverage (length
+        H+1; the psnr / ssim entries are None for vector observations) and
+        reward_spread (length H).  Leaves np.random's state and the Philox
+        {seed, offset} and stream counter as it found them, like
+        evaluate_world_model."""
+        from .futures import evaluate_futures
+        return evaluate_futures(self, batches=batches, batch_size=batch_size, context=context, horizon=horizon,
+                                samples=samples)
+
     def closed_loop(self, starts=None, batch_size=None, length=None, sample=True, noise=None, predict=True,
                     _mark=None):
         """Posterior trace on replay windows (closed_loop.py): run the filter

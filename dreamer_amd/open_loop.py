@@ -87,6 +87,14 @@ class OpenLoopResult:
         m = d.pow(2).flatten(2).mean(-1)
         return 10.0 * torch.log10(255.0 ** 2 / m)
 
+    def ssim(self):
+        """SSIM per frame (B,H+1) of mu against the true frames (dr_frame_ssim:
+        11-tap Gaussian window, sigma 1.5, data range 1), computed on demand on
+        the current stream."""
+        self._need_frames("ssim()")
+        from .futures import frame_ssim
+        return frame_ssim(self.mu, self.frames_true)
+
     def video(self):
         """u8 [H+1][3][2h][B*w]: per step, the true frames above the predicted
         ones, the B windows side by side."""

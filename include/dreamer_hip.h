@@ -526,6 +526,57 @@ int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, const float* 
 int dr_frame_metrics(const dr_dims* d, int B, int T, const float* mu, const dr_frames* truth, float* sqerr,
                      unsigned char* pred_u8, unsigned char* true_u8, hipStream_t stream);
 
+/* ---- sampled futures on replay windows (Dreamer.sample_futures): SSIM of
+ *      decoded frames, and the mean and spread of M decoded futures.  No
+ *      reference counterpart: the definitions are these. ------------------------
+ * dr_frame_ssim: mu, truth and the frame indexing (t0 included) as
+ * dr_frame_metrics.  Pixel observations only (obs_dim > 0: DR_E_INVALID).
+ *   p = min(0.5f, max(-0.5f, mu)) the clamped prediction, x the true value as
+ *   dr_frame_metrics defines it; both centred on 0 (data range 1).
+ *   Window: the 11-tap Gaussian with sigma = 1.5, g_k = exp(-(k - 5)^2 / 4.5),
+ *   normalised to sum 1 in double and rounded to f32 once (constant data),
+ *   applied separably -- along W first, then along H, taps in ascending order --
+ *   at the (H - 10) x (W - 10) valid positions only.
+ *   Per channel and position, on the centred values:
+ *     m_p = sum w p, m_x = sum w x, v_p = sum w p^2 - m_p^2, v_x = sum w x^2 - m_x^2,
+ *     c = sum w p x - m_p m_x;  u_p = m_p + 0.5, u_x = m_x + 0.5 (luminance means)
+ *     map = ((2 u_p u_x + C1)(2 c + C2)) / ((u_p^2 + u_x^2 + C1)(v_p + v_x + C2)),
+ *     C1 = 1e-4, C2 = 9e-4
+ *   ssim_ch[b][t][ch] = mean of the map over the channel's valid positions (may be NULL)
+ *   ssim[b][t]        = ((ch0 + ch1) + ch2) / 3
+ * img_h < 11 or img_w < 11: DR_E_UNSUPPORTED, nothing launched; every size from
+ * 11 x 11 up to img_w <= 163 (any img_h) is served (wider rows do not fit the
+ * kernel's 64 KiB of LDS: DR_E_UNSUPPORTED).
+ * One 256-thread workgroup per frame, no atomics, nothing shared between
+ * workgroups.  A thread adds the map at its positions (row-major position tid,
+ * tid + 256, ... of each strip of rows, strips in ascending order) in ascending
+ * order per channel, then a fixed wave reduction and the four wave sums in wave
+ * order: a frame's results are the same bits at every B, T and position, and
+ * from run to run.  A prediction bit-equal to the (in-range) truth gives 1.0f. */
+int dr_frame_ssim(const dr_dims* d, int B, int T, const float* mu, const dr_frames* truth, float* ssim,
+                  float* ssim_ch, hipStream_t stream);
+
+/* dr_ensemble_metrics: M decoded futures per window, mu [B][M][T][n] with row
+ * (b*M + m)*T + t as dr_decoder_fwd writes it for rollout rows b*M + m; n =
+ * 3*H*W, or obs_dim for vector observations.  truth (b, t) as dr_frame_metrics.
+ * Per element i, in f32:  mean_i = (sum_m mu_m,i) / M  (m ascending),
+ * var_i = (sum_m (mu_m,i - mean_i)^2) / M  (a second pass: the population variance).
+ *   sqerr_mean[b][t] = sum_i (mean_i - x_i)^2      the ensemble mean's error
+ *   spread[b][t]     = sum_i var_i
+ *   mean_u8[b][t]    = the mean frame quantised as pred_u8 is (may be NULL)
+ *   std_u8[b][t]     = (u8) min(255, rintf(255.0f * sqrtf(var_i))) (may be NULL)
+ *   mean_f32[b][t][n] = the mean frame (may be NULL; dr_frame_ssim takes it as mu)
+ * mean_u8 and std_u8 must be NULL for vector observations (DR_E_INVALID).
+ * 1 <= M <= 64, else DR_E_INVALID.  M = 1: spread is exactly 0 and sqerr_mean
+ * is dr_frame_metrics' sqerr bit for bit (buffers of the same alignment).
+ * One 256-thread workgroup per (b, t), dr_frame_metrics' element order and
+ * reduction, no atomics: the same bits at every B, T and position, and from
+ * run to run.  Per-sample squared errors are dr_frame_metrics on B*M rows
+ * with starts repeated M times. */
+int dr_ensemble_metrics(const dr_dims* d, int B, int M, int T, const float* mu, const dr_frames* truth,
+                        float* sqerr_mean, float* spread, unsigned char* mean_u8, unsigned char* std_u8,
+                        float* mean_f32, hipStream_t stream);
+
 /* ---- latent statistics on raw logits [M][R][C] (no unimix, no free bits, no
  *      mask: the terms of the KL losses, WorldModel.py:175-181, per row) --------
  *   kl[m]            = sum_r KL(Cat(logits = post[m][r]) || Cat(logits = prior[m][r]))
