@@ -1,5 +1,6 @@
-"""Closed-loop (posterior) trace on replay windows: the result container of
-``Dreamer.closed_loop`` and the window arithmetic it shares with the tests.
+"""Closed-loop (posterior) trace on replay windows: ``Dreamer.closed_loop`` and
+``evaluate_filter``, their result container and the window arithmetic they
+share with the tests (the front end is replay_eval.py's).
 
 A window b is S = sequence_length consecutive ring slots from starts[b].  The
 filter is warm_start_generator's (Dreamer.py:244-262): h_0 = 0, z_0 ~
@@ -13,6 +14,12 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
+
+from . import _lib as L
+from . import hip
+from .replay_eval import (FrameResult, average_curves, check_window, decode_and_score, head_errors, psnr_u8,
+                          resolve_noise, ring_slots, video_rows, window_prologue)
+from .utils import symlog
 
 
 def frame_step(t):
@@ -31,19 +38,16 @@ def target_step(t):
 
 def target_slots(starts, length, capacity):
     """(frame slots [B][T], reward / continue slots [B][T-1]) in the ring, as int64 tensors."""
-    st = torch.as_tensor(starts, dtype=torch.int64).reshape(-1, 1)
-    kf = torch.arange(0, length, dtype=torch.int64).reshape(1, -1)
-    kt = torch.arange(1, length, dtype=torch.int64).reshape(1, -1)
-    return (st + kf) % capacity, (st + kt - 1) % capacity
+    return ring_slots(starts, 0, length, capacity), ring_slots(starts, 0, length - 1, capacity)
 
 
 def check_length(length, sequence_length):
-    if length < 1 or length > sequence_length:
-        raise ValueError(f"closed loop needs 1 <= length <= sequence_length (got {length} vs {sequence_length})")
+    check_window(1 <= length <= sequence_length, "closed loop needs 1 <= length <= sequence_length", length,
+                 sequence_length)
 
 
 @dataclass
-class ClosedLoopResult:
+class ClosedLoopResult(FrameResult):
     """Device tensors of one posterior trace over B windows of T = length steps.
 
     latents (B,T,R,C), hiddens (B,T,hidden): the filtered states.
@@ -84,11 +88,7 @@ class ClosedLoopResult:
     continue_true: torch.Tensor
     length: int
 
-    def frame_elems(self):
-        n = 1
-        for s in self.mu_post.shape[2:]:
-            n *= int(s)
-        return n
+    _mu, _u8 = "mu_post", ("frames_post", "frames_true")
 
     def _need_prior(self, what):
         if self.sqerr_prior is None:
@@ -103,25 +103,16 @@ class ClosedLoopResult:
         self._need_prior("mse_prior()")
         return self.sqerr_prior / float(self.frame_elems())
 
-    def _need_frames(self, what):
-        if self.frames_post is None or self.frames_true is None:
-            raise ValueError(f"{what} needs pixel observations (vector observations have no u8 frames)")
-
-    def _psnr(self, frames):
-        d = frames.float() - self.frames_true.float()
-        m = d.pow(2).flatten(2).mean(-1)
-        return 10.0 * torch.log10(255.0 ** 2 / m)
-
     def psnr_post(self):
         """PSNR of the reconstruction per frame (B,T) in dB on the u8 scale: 10 log10(255^2 / mean((pred - true)^2))."""
         self._need_frames("psnr_post()")
-        return self._psnr(self.frames_post)
+        return psnr_u8(self.frames_post, self.frames_true)
 
     def psnr_prior(self):
         """PSNR of the one-step prediction per frame (B,T), as psnr_post."""
         self._need_frames("psnr_prior()")
         self._need_prior("psnr_prior()")
-        return self._psnr(self.frames_prior)
+        return psnr_u8(self.frames_prior, self.frames_true)
 
     def ssim_post(self):
         """SSIM of the reconstruction per frame (B,T) (dr_frame_ssim), computed
@@ -146,5 +137,67 @@ class ClosedLoopResult:
         reconstructions above the one-step predictions, the B windows side by side."""
         self._need_frames("video()")
         self._need_prior("video()")
-        row = lambda f: torch.cat(list(f.transpose(0, 1).unbind(1)), dim=-1)  # (B,T,3,h,w) -> (T,3,h,B*w)
-        return torch.cat((row(self.frames_true), row(self.frames_post), row(self.frames_prior)), dim=-2).contiguous()
+        return video_rows(self.frames_true, self.frames_post, self.frames_prior)
+
+
+def closed_loop(dr, starts=None, batch_size=None, length=None, sample=True, noise=None, predict=True, _mark=None):
+    """Dreamer.closed_loop (see its docstring)."""
+    mark = _mark or (lambda name: None)
+    S = dr.sequence_length
+    T = S if length is None else int(length)
+    check_length(T, S)
+    R, C = dr.latent_state_dims
+    A = dr.action_dims
+
+    def draws(B, dev):
+        shape = (T, B * R, C)
+        return resolve_noise(noise, sample, (shape, shape), f"noise must be two tensors of shape ({T}, {B * R}, {C})",
+                             dev)
+
+    w = window_prologue(dr, starts, batch_size, T, draws, mark)
+    B, dev = w.B, w.st.device
+    q_post, q_prior = w.noise
+    # action t-1 drives frame t; state t's heads are compared with window step t-1
+    lat, hid, plog, prlog, r, c = dr.world_model._observe_trace(w.d, B, T, w.feat, w.act.data_ptr(), S * A, A, None,
+                                                                None, q_post)
+    mark("trace")
+    M = B * T
+    kl, hq, hp = (torch.empty(B, T, device=dev) for _ in range(3))
+    L.call("dr_latent_stats", M, R, C, L.ptr(plog), L.ptr(prlog), L.ptr(kl), L.ptr(hq), L.ptr(hp), None, w.stream)
+    mark("stats")
+    zp = None
+    if predict:
+        # the prior's own draw t for row (b, t): explicit draws are given time-major, the rows are [B][T]
+        zp = torch.empty(B, T, R, C, device=dev)
+        if q_prior is not None:
+            qp = q_prior.view(T, B, R, C).transpose(0, 1).contiguous()
+            nz = hip.explicit_noise(q=qp, device=dev)
+        else:
+            nz = hip.adhoc(dev).noise()
+        L.call("dr_categorical_sample", M, R, C, L.ptr(prlog), nz, L.ptr(zp), None, None, w.stream)
+        mark("prior_sample")
+    ((mu_q, sq_q, fr_q), (mu_p, sq_p, fr_p)), true, _ = decode_and_score(dr, w, w.st, (B, T), 0, hid, (lat, zp), True,
+                                                                         mark)
+    return ClosedLoopResult(latents=lat, hiddens=hid, post_logits=plog, prior_logits=prlog, kl=kl, post_entropy=hq,
+                            prior_entropy=hp, mu_post=mu_q, mu_prior=mu_p, latents_prior=zp, sqerr_post=sq_q,
+                            sqerr_prior=sq_p, frames_post=fr_q, frames_prior=fr_p, frames_true=true,
+                            reward_pred=symlog(r[:, 1:]), reward_true=w.rew[:, :T - 1].unsqueeze(-1).clone(),
+                            continue_pred=c[:, 1:].clone(), continue_true=w.cont[:, :T - 1].unsqueeze(-1).clone(),
+                            length=T)
+
+
+CURVES = ("kl", "post_entropy", "prior_entropy", "mse_post", "mse_prior", "psnr_post", "psnr_prior", "reward_abs_err",
+          "continue_bce")
+
+
+def curves_of(r):
+    px = r.frames_post is not None
+    return [r.kl.mean(0), r.post_entropy.mean(0), r.prior_entropy.mean(0), r.mse_post().mean(0),
+            r.mse_prior().mean(0), r.psnr_post().mean(0) if px else None,
+            r.psnr_prior().mean(0) if px else None] + head_errors(r)
+
+
+def evaluate_filter(dr, batches=1, batch_size=None, length=None, sample=True):
+    """Dreamer.evaluate_filter (see its docstring)."""
+    return average_curves("evaluate_filter", dr, batches, CURVES, lambda: dr.closed_loop(
+        batch_size=batch_size, length=length, sample=sample), curves_of)

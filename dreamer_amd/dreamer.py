@@ -189,77 +189,9 @@ class Dreamer(nn.Module):
         current stream without a sync.  _mark: stage hook of
         tools/open_loop_timing.py (called with the stage's name once it is
         enqueued)."""
-        from .open_loop import OpenLoopResult, check_lengths
-        from .utils import symlog
-        mark = _mark or (lambda name: None)
-        S = self.sequence_length
-        Tc = S // 2 if context is None else int(context)
-        H = min(self.horizon, S - Tc) if horizon is None else int(horizon)
-        check_lengths(Tc, H, S)
-        buf, wmod = self.buffer, self.world_model
-        dev = buf.device
-        if starts is None:
-            starts = buf.sample_start_indices(batch_size or self.batch_size)
-        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
-            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
-        B = int(st.numel())
-        R, C = self.latent_state_dims
-        A, Hd = self.action_dims, self.hidden_state_dims
-        if noise is not None:
-            q_ctx, q = (t.float().contiguous() for t in noise)
-            if tuple(q_ctx.shape) != (Tc, B * R, C) or tuple(q.shape) != (H, B * R, C):
-                raise ValueError(f"noise must be ({Tc}, {B * R}, {C}) and ({H}, {B * R}, {C})")
-        elif not sample:
-            q_ctx, q = torch.ones(Tc, B * R, C, device=dev), torch.ones(H, B * R, C, device=dev)
-        else:
-            q_ctx = q = None
-        d = wmod.dims(self.agent)
-        wm = wmod.packed()
-        stream = hip.stream()
-        m = buf._mirror()
-        act = torch.empty(B, S, A, device=dev)
-        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
-        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
-               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
-        mark("gather")
-        # posterior after the context frames
-        fr = buf.frames_struct(st)
-        feat = torch.empty(Tc * B, d.enc_hidden, device=dev)
-        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, Tc * B))
-        L.call("dr_encoder_features", d, wm, fr, B, Tc, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
-        mark("encoder")
-        z0, h0 = torch.empty(B, R * C, device=dev), torch.empty(B, Hd, device=dev)
-        nz = hip.explicit_noise(q=q_ctx, device=dev) if q_ctx is not None else hip.adhoc(dev).noise()
-        ws = hip.workspace(dev).get("obs", L.query("dr_observe_workspace_bytes", d, B))
-        L.call("dr_observe_scan", d, wm, B, Tc, L.ptr(feat), L.ptr(act), S * A, A, None, None, nz, L.ptr(z0),
-               L.ptr(h0), None, L.ptr(ws), ws.numel(), stream)
-        mark("scan")
-        # the prior under the recorded actions: action Tc-1+k drives state k -> k+1
-        lat, hid, r, c = wmod._imagine_actions(d, B, H, z0, h0, act.data_ptr() + 4 * (Tc - 1) * A, S * A, A, q)
-        mark("unroll")
-        # decode states 0..H and compare with the ring's frames Tc-1 .. Tc-1+H
-        M = B * (H + 1)
-        vector = buf.vector
-        shape = (d.obs_dim,) if vector else (3, d.img_h, d.img_w)
-        mu = torch.empty(B, H + 1, *shape, device=dev)
-        ws = hip.workspace(dev).get("dec", L.query("dr_decoder_workspace_bytes", d, M))
-        L.call("dr_decoder_fwd", d, wmod.packed_decoder(), M, L.ptr(hid), Hd, L.ptr(lat), R * C, L.ptr(mu), L.ptr(ws),
-               ws.numel(), stream)
-        mark("decoder")
-        sqerr = torch.empty(B, H + 1, device=dev)
-        pred = true = None
-        if not vector:
-            pred = torch.empty(B, H + 1, *shape, dtype=torch.uint8, device=dev)
-            true = torch.empty_like(pred)
-        truth = buf.frames_struct(st)
-        truth.t0 = Tc - 1
-        L.call("dr_frame_metrics", d, B, H + 1, L.ptr(mu), truth, L.ptr(sqerr), L.ptr(pred), L.ptr(true), stream)
-        mark("metrics")
-        sl = slice(Tc - 1, Tc - 1 + H)  # state k = 1..H against window step Tc+k-2
-        return OpenLoopResult(latents=lat, hiddens=hid, mu=mu, frames_pred=pred, frames_true=true, sqerr=sqerr,
-                              reward_pred=symlog(r), reward_true=rew[:, sl].unsqueeze(-1).clone(),
-                              continue_pred=c, continue_true=cont[:, sl].unsqueeze(-1).clone(), context=Tc,
-                              horizon=H)
+        from .open_loop import open_loop
+        return open_loop(self, starts=starts, batch_size=batch_size, context=context, horizon=horizon, sample=sample,
+                         noise=noise, _mark=_mark)
 
     def evaluate_world_model(self, batches=1, batch_size=None, context=None, horizon=None, sample=True):
         """Per-step open-loop error curves averaged over `batches` sampled
@@ -269,27 +201,9 @@ class Dreamer(nn.Module):
         H).  Leaves np.random's state and the Philox {seed, offset} as it
         found them, so calling it between training iterations does not change
         the training run."""
-        np_state = np.random.get_state()
-        ar = hip.adhoc(self.device)
-        rng_state, rng_counter = ar.state.clone(), ar.counter
-        try:
-            acc = None
-            with torch.no_grad():
-                for _ in range(int(batches)):
-                    r = self.open_loop(batch_size=batch_size, context=context, horizon=horizon, sample=sample)
-                    cur = [r.mse().mean(0), r.psnr().mean(0) if r.frames_pred is not None else None,
-                           (r.reward_pred - r.reward_true).abs().mean((0, 2)),
-                           torch.nn.functional.binary_cross_entropy(r.continue_pred.clamp(0.0, 1.0), r.continue_true,
-                                                                    reduction="none").mean((0, 2))]
-                    acc = cur if acc is None else [None if a is None else a + b for a, b in zip(acc, cur)]
-        finally:
-            np.random.set_state(np_state)
-            ar.state.copy_(rng_state)
-            ar.counter = rng_counter
-        if acc is None:
-            raise ValueError("evaluate_world_model needs batches >= 1")
-        out = [None if a is None else (a / float(batches)).cpu().tolist() for a in acc]
-        return {"mse": out[0], "psnr": out[1], "reward_abs_err": out[2], "continue_bce": out[3]}
+        from .open_loop import evaluate_world_model
+        return evaluate_world_model(self, batches=batches, batch_size=batch_size, context=context, horizon=horizon,
+                                    sample=sample)
 
     def sample_futures(self, starts=None, batch_size=None, context=None, horizon=None, samples=8, noise=None,
                        ssim=True, _mark=None):
@@ -345,91 +259,9 @@ class Dreamer(nn.Module):
         every categorical (q == 1 for both).  Frames are read straight from the
         device ring; everything runs on the current stream without a sync.
         _mark: stage hook of tools/closed_loop_timing.py."""
-        from .closed_loop import ClosedLoopResult, check_length
-        from .utils import symlog
-        mark = _mark or (lambda name: None)
-        S = self.sequence_length
-        T = S if length is None else int(length)
-        check_length(T, S)
-        buf, wmod = self.buffer, self.world_model
-        dev = buf.device
-        if starts is None:
-            starts = buf.sample_start_indices(batch_size or self.batch_size)
-        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
-            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
-        B = int(st.numel())
-        R, C = self.latent_state_dims
-        A, Hd = self.action_dims, self.hidden_state_dims
-        if noise is not None:
-            q_post, q_prior = (t.float().contiguous() for t in noise)
-            if tuple(q_post.shape) != (T, B * R, C) or tuple(q_prior.shape) != (T, B * R, C):
-                raise ValueError(f"noise must be two tensors of shape ({T}, {B * R}, {C})")
-        elif not sample:
-            q_post = q_prior = torch.ones(T, B * R, C, device=dev)
-        else:
-            q_post = q_prior = None
-        d = wmod.dims(self.agent)
-        wm = wmod.packed()
-        stream = hip.stream()
-        m = buf._mirror()
-        act = torch.empty(B, S, A, device=dev)
-        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
-        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
-               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
-        mark("gather")
-        fr = buf.frames_struct(st)
-        feat = torch.empty(T * B, d.enc_hidden, device=dev)
-        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, T * B))
-        L.call("dr_encoder_features", d, wm, fr, B, T, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
-        mark("encoder")
-        # action t-1 drives frame t; state t's heads are compared with window step t-1
-        lat, hid, plog, prlog, r, c = wmod._observe_trace(d, B, T, feat, act.data_ptr(), S * A, A, None, None, q_post)
-        mark("trace")
-        M = B * T
-        kl, hq, hp = (torch.empty(B, T, device=dev) for _ in range(3))
-        L.call("dr_latent_stats", M, R, C, L.ptr(plog), L.ptr(prlog), L.ptr(kl), L.ptr(hq), L.ptr(hp), None, stream)
-        mark("stats")
-        zp = None
-        if predict:
-            # the prior's own draw t for row (b, t): explicit draws are given time-major, the rows are [B][T]
-            zp = torch.empty(B, T, R, C, device=dev)
-            if q_prior is not None:
-                qp = q_prior.view(T, B, R, C).transpose(0, 1).contiguous()
-                nz = hip.explicit_noise(q=qp, device=dev)
-            else:
-                nz = hip.adhoc(dev).noise()
-            L.call("dr_categorical_sample", M, R, C, L.ptr(prlog), nz, L.ptr(zp), None, None, stream)
-            mark("prior_sample")
-        vector = buf.vector
-        shape = (d.obs_dim,) if vector else (3, d.img_h, d.img_w)
-        ws = hip.workspace(dev).get("dec", L.query("dr_decoder_workspace_bytes", d, M))
-        dec = wmod.packed_decoder()
-        truth = buf.frames_struct(st)
-        truth.t0 = 0
-        out = []
-        for z in (lat, zp):
-            if z is None:
-                out.append((None, None, None))
-                continue
-            mu = torch.empty(B, T, *shape, device=dev)
-            L.call("dr_decoder_fwd", d, dec, M, L.ptr(hid), Hd, L.ptr(z), R * C, L.ptr(mu), L.ptr(ws), ws.numel(),
-                   stream)
-            out.append((mu, torch.empty(B, T, device=dev),
-                        None if vector else torch.empty(B, T, *shape, dtype=torch.uint8, device=dev)))
-        mark("decoder")
-        true = None if vector else torch.empty(B, T, *shape, dtype=torch.uint8, device=dev)
-        for k, (mu, sq, pred) in enumerate(out):
-            if mu is not None:
-                L.call("dr_frame_metrics", d, B, T, L.ptr(mu), truth, L.ptr(sq), L.ptr(pred),
-                       L.ptr(true) if k == 0 else None, stream)
-        mark("metrics")
-        (mu_q, sq_q, fr_q), (mu_p, sq_p, fr_p) = out
-        return ClosedLoopResult(latents=lat, hiddens=hid, post_logits=plog, prior_logits=prlog, kl=kl, post_entropy=hq,
-                                prior_entropy=hp, mu_post=mu_q, mu_prior=mu_p, latents_prior=zp, sqerr_post=sq_q,
-                                sqerr_prior=sq_p, frames_post=fr_q, frames_prior=fr_p, frames_true=true,
-                                reward_pred=symlog(r[:, 1:]), reward_true=rew[:, :T - 1].unsqueeze(-1).clone(),
-                                continue_pred=c[:, 1:].clone(), continue_true=cont[:, :T - 1].unsqueeze(-1).clone(),
-                                length=T)
+        from .closed_loop import closed_loop
+        return closed_loop(self, starts=starts, batch_size=batch_size, length=length, sample=sample, noise=noise,
+                           predict=predict, _mark=_mark)
 
     def evaluate_filter(self, batches=1, batch_size=None, length=None, sample=True):
         """Per-step closed-loop curves averaged over `batches` sampled batches
@@ -439,31 +271,8 @@ class Dreamer(nn.Module):
         (symlog space) and continue_bce (length T - 1).  Leaves np.random's
         state and the Philox {seed, offset} and stream counter as it found
         them, like evaluate_world_model."""
-        np_state = np.random.get_state()
-        ar = hip.adhoc(self.device)
-        rng_state, rng_counter = ar.state.clone(), ar.counter
-        keys = ("kl", "post_entropy", "prior_entropy", "mse_post", "mse_prior", "psnr_post", "psnr_prior",
-                "reward_abs_err", "continue_bce")
-        try:
-            acc = None
-            with torch.no_grad():
-                for _ in range(int(batches)):
-                    r = self.closed_loop(batch_size=batch_size, length=length, sample=sample)
-                    px = r.frames_post is not None
-                    cur = [r.kl.mean(0), r.post_entropy.mean(0), r.prior_entropy.mean(0), r.mse_post().mean(0),
-                           r.mse_prior().mean(0), r.psnr_post().mean(0) if px else None,
-                           r.psnr_prior().mean(0) if px else None,
-                           (r.reward_pred - r.reward_true).abs().mean((0, 2)),
-                           torch.nn.functional.binary_cross_entropy(r.continue_pred.clamp(0.0, 1.0), r.continue_true,
-                                                                    reduction="none").mean((0, 2))]
-                    acc = cur if acc is None else [None if a is None else a + b for a, b in zip(acc, cur)]
-        finally:
-            np.random.set_state(np_state)
-            ar.state.copy_(rng_state)
-            ar.counter = rng_counter
-        if acc is None:
-            raise ValueError("evaluate_filter needs batches >= 1")
-        return {k: None if a is None else (a / float(batches)).cpu().tolist() for k, a in zip(keys, acc)}
+        from .closed_loop import evaluate_filter
+        return evaluate_filter(self, batches=batches, batch_size=batch_size, length=length, sample=sample)
 
     def agent_trace(self, starts=None, batch_size=None, length=None, sample=True, noise=None, _mark=None):
         """Agent trace on replay windows (agent_trace.py): run closed_loop's
@@ -483,87 +292,9 @@ class Dreamer(nn.Module):
         lambda are the agent's.  Frames are read straight from the device
         ring; everything runs on the current stream without a sync.  _mark:
         stage hook of tools/agent_trace_timing.py."""
-        from .agent_trace import AgentTraceResult, check_length
-        mark = _mark or (lambda name: None)
-        S = self.sequence_length
-        T = S if length is None else int(length)
-        check_length(T, S)
-        buf, wmod, ag = self.buffer, self.world_model, self.agent
-        dev = buf.device
-        if starts is None:
-            starts = buf.sample_start_indices(batch_size or self.batch_size)
-        st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
-            torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
-        B = int(st.numel())
-        R, C = self.latent_state_dims
-        A, Hd = self.action_dims, self.hidden_state_dims
-        if noise is not None:
-            q_post = noise.float().contiguous()
-            if tuple(q_post.shape) != (T, B * R, C):
-                raise ValueError(f"noise must be one tensor of shape ({T}, {B * R}, {C})")
-        elif not sample:
-            q_post = torch.ones(T, B * R, C, device=dev)
-        else:
-            q_post = None
-        ag._ensure_flat()
-        d = wmod.dims(ag)
-        wm = wmod.packed()
-        stream = hip.stream()
-        m = buf._mirror()
-        act = torch.empty(B, S, A, device=dev)
-        rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
-        L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
-               L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
-        mark("gather")
-        fr = buf.frames_struct(st)
-        feat = torch.empty(T * B, d.enc_hidden, device=dev)
-        ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, T * B))
-        L.call("dr_encoder_features", d, wm, fr, B, T, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
-        mark("encoder")
-        # action t-1 drives frame t: closed_loop's filter, without the prior and the heads
-        lat, hid, _, _, _, _ = wmod._observe_trace(d, B, T, feat, act.data_ptr(), S * A, A, None, None, q_post,
-                                                   heads=False, prior=False)
-        mark("trace")
-        # both critics over the M = B*T states, rows straight from the trace's arrays
-        M, nb = B * T, ag.buckets
-        logits = torch.empty(B, T, nb, device=dev)
-        V, Vt = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
-        ws = hip.workspace(dev).get("at_crit", L.query("dr_critic_workspace_bytes", d, B, T - 1))
-        L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(hid), Hd, L.ptr(lat), R * C, L.ptr(logits), L.ptr(V),
-               None, L.ptr(ws), ws.numel(), stream)
-        L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(hid), Hd, L.ptr(lat), R * C, None, L.ptr(Vt),
-               None, L.ptr(ws), ws.numel(), stream)
-        mark("critics")
-        mu, sg, a_mode = (torch.empty(B, T, A, device=dev) for _ in range(3))
-        ws = hip.workspace(dev).get("act", L.query("dr_actor_act_workspace_bytes", d, M))
-        L.call("dr_actor_act", d, ag.actor_struct(), M, L.ptr(hid), L.ptr(lat), L.dr_noise(), 1, L.ptr(a_mode),
-               L.ptr(mu), L.ptr(sg), L.ptr(ws), ws.numel(), stream)
-        mark("actor")
-        # slot t's stored transition leaves state t: real rewards (symexp of the ring's symlog) under the target values
-        Rl, Rmc, td, ce = (torch.empty(B, T - 1, device=dev) for _ in range(4))
-        L.call("dr_replay_returns", B, T, L.ptr(rew), S, L.ptr(cont), S, 1, L.ptr(Vt), ag.gamma, ag.lambda_, L.ptr(Rl),
-               L.ptr(Rmc), L.ptr(td), stream)
-        # the natural-space rewards as that kernel formed them: at gamma = 0 the recursion is r + 0, so
-        # returns_lambda follows from the result's own reward / cont / value_target bit for bit
-        r_nat = torch.empty(B, T - 1, device=dev)
-        L.call("dr_replay_returns", B, T, L.ptr(rew), S, L.ptr(cont), S, 1, L.ptr(Vt), 0.0, 0.0, L.ptr(r_nat), None,
-               None, stream)
-        mark("returns")
-        ent, std = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
-        L.call("dr_value_stats", B, T, T - 1, nb, L.ptr(logits), nb, L.ptr(ag.critic.buckets_crit), L.ptr(Rl),
-               L.ptr(ent), L.ptr(std), L.ptr(ce), stream)
-        mark("value_stats")
-        logp, hbase = torch.empty(B, T, device=dev), torch.empty(B, T, device=dev)
-        logp_dims = torch.empty(B, T, A, device=dev)
-        L.call("dr_action_logprob", B, T, A, L.ptr(mu), L.ptr(sg), L.ptr(act), S * A, A, L.ptr(logp), L.ptr(logp_dims),
-               L.ptr(hbase), stream)
-        mark("logprob")
-        return AgentTraceResult(latents=lat, hiddens=hid, value=V, value_target=Vt, value_entropy=ent,
-                                value_std_symlog=std, critic_logits=logits, actor_mu=mu, actor_sigma=sg,
-                                actions=act[:, :T].clone(), action_logprob=logp, policy_entropy_base=hbase,
-                                action_logprob_dims=logp_dims, reward=r_nat,
-                                cont=cont[:, :T - 1].clone(), returns_lambda=Rl, returns_mc=Rmc, td=td, critic_ce=ce,
-                                length=T)
+        from .agent_trace import agent_trace
+        return agent_trace(self, starts=starts, batch_size=batch_size, length=length, sample=sample, noise=noise,
+                           _mark=_mark)
 
     def evaluate_values(self, batches=1, batch_size=None, length=None, sample=True):
         """Per-step agent-trace curves averaged over `batches` sampled batches
@@ -573,31 +304,8 @@ class Dreamer(nn.Module):
         (length T - 1) -- and the scalar explained_variance (the mean over the
         batches).  Leaves np.random's state and the Philox {seed, offset} and
         stream counter as it found them, like evaluate_filter."""
-        np_state = np.random.get_state()
-        ar = hip.adhoc(self.device)
-        rng_state, rng_counter = ar.state.clone(), ar.counter
-        keys = ("value", "value_target", "value_entropy", "value_std_symlog", "action_logprob", "actor_sigma",
-                "returns_lambda", "returns_mc", "abs_td", "critic_ce", "abs_advantage")
-        try:
-            acc, ev = None, 0.0
-            with torch.no_grad():
-                for _ in range(int(batches)):
-                    r = self.agent_trace(batch_size=batch_size, length=length, sample=sample)
-                    cur = [r.value.mean(0), r.value_target.mean(0), r.value_entropy.mean(0),
-                           r.value_std_symlog.mean(0), r.action_logprob.mean(0), r.actor_sigma.mean((0, 2)),
-                           r.returns_lambda.mean(0), r.returns_mc.mean(0), r.td.abs().mean(0), r.critic_ce.mean(0),
-                           r.advantage().abs().mean(0)]
-                    acc = cur if acc is None else [a + b for a, b in zip(acc, cur)]
-                    ev += float(r.explained_variance())
-        finally:
-            np.random.set_state(np_state)
-            ar.state.copy_(rng_state)
-            ar.counter = rng_counter
-        if acc is None:
-            raise ValueError("evaluate_values needs batches >= 1")
-        out = {k: (a / float(batches)).cpu().tolist() for k, a in zip(keys, acc)}
-        out["explained_variance"] = ev / float(batches)
-        return out
+        from .agent_trace import evaluate_values
+        return evaluate_values(self, batches=batches, batch_size=batch_size, length=length, sample=sample)
 
     # --------------------------------------------------------------- training
     @property
@@ -1177,6 +885,20 @@ class Dreamer(nn.Module):
         env that finishes takes the next seed and its row starts an episode).
         An env with no episode left drops out of the batch.  Returns the mean
         total reward (taken in episode order) as a device scalar."""
+        def step(frames, state, first, carried):
+            action, _, _, latent, hidden = self.act_step_batch(frames, state, first, deterministic=True)
+            return action, latent, hidden, None
+
+        return self._run_episodes(envs, eval_episodes, step)
+
+    def _run_episodes(self, envs, eval_episodes, step, carry=None):
+        """The episode loop of evaluate_agent_vec and evaluate_planner.
+        step(frames (N,...), state, first, carried) -> (action, latent, hidden,
+        extra) acts for the N episodes in flight: state is the (latent, hidden,
+        action) of the surviving rows (None on the first step), first marks
+        the rows that start an episode.  carry(extra, idx), if given, makes the
+        next step's `carried` out of this step's `extra`, idx (a device int64
+        tensor) being the rows that go on."""
         totals = [0] * eval_episodes
         with torch.no_grad():
             slots = []  # [env, episode index] in flight
@@ -1185,9 +907,9 @@ class Dreamer(nn.Module):
                 slots.append([env, len(slots)])
             started = len(slots)
             frames = [env.reset(seed=self.seed - started + 1 + ep)[0] for env, ep in slots]
-            state, first = None, np.ones(len(slots), dtype=bool)
+            state, carried, first = None, None, np.ones(len(slots), dtype=bool)
             while slots:
-                action, _, _, latent, hidden = self.act_step_batch(np.stack(frames), state, first, deterministic=True)
+                action, latent, hidden, extra = step(np.stack(frames), state, first, carried)
                 action_np = action.detach().cpu().numpy().reshape(len(slots), -1)
                 self.act_check()
                 keep, frames, first = [], [], []
@@ -1212,6 +934,8 @@ class Dreamer(nn.Module):
                 if slots:
                     idx = torch.tensor(keep, device=self.device)
                     state = tuple(t.index_select(0, idx) for t in (latent, hidden, action))
+                    if carry is not None:
+                        carried = carry(extra, idx)
         return torch.tensor(totals, dtype=torch.float32, device=self.device).mean()
 
     # ------------------------------------------------- latent planning (HIP)

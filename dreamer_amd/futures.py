@@ -20,6 +20,10 @@ import torch
 
 from . import _lib as L
 from . import hip
+from .open_loop import target_slots, window_lengths
+from .replay_eval import (FrameResult, average_curves, context_filter, decode_and_score, psnr_u8, resolve_noise,
+                          video_rows, window_prologue)
+from .utils import symlog
 
 WHICH = ("mean", "best", "best_sample", "ensemble")
 
@@ -71,13 +75,8 @@ def frame_ssim(mu, frames_u8):
     return out
 
 
-def _psnr(pred_u8, true_u8):
-    d = pred_u8.float() - true_u8.float()
-    return 10.0 * torch.log10(255.0 ** 2 / d.pow(2).flatten(-3).mean(-1))
-
-
 @dataclass
-class FuturesResult:
+class FuturesResult(FrameResult):
     """Device tensors of M sampled futures over B windows.
 
     Per sample: latents (B,M,H+1,R,C), hiddens (B,M,H+1,hidden), mu
@@ -118,11 +117,7 @@ class FuturesResult:
     def samples(self):
         return int(self.sqerr.shape[1])
 
-    def frame_elems(self):
-        n = 1
-        for s in self.mu.shape[3:]:
-            n *= int(s)
-        return n
+    _lead, _u8 = 3, ("frames_true",)
 
     def best(self):
         """Per window the sample with the smallest sum over states 1..H of
@@ -141,10 +136,6 @@ class FuturesResult:
             return per_sample.gather(1, i).squeeze(1)
         raise ValueError(f"which must be one of {WHICH} (got {which!r})")
 
-    def _need_frames(self, what):
-        if self.frames_true is None:
-            raise ValueError(f"{what} needs pixel observations (vector observations have no u8 frames)")
-
     def mse(self, which="mean"):
         """Mean squared error per frame (B,H+1) on the model's [-0.5, 0.5] scale:
         "mean" over the samples, "best" the smallest of the M at each step (never
@@ -160,8 +151,8 @@ class FuturesResult:
         the variants as mse ("best": the largest of the M at each step)."""
         self._need_frames("psnr()")
         if which == "ensemble":
-            return _psnr(self.frames_mean, self.frames_true)
-        return self._pick(_psnr(self.frames_pred, self.frames_true.unsqueeze(1)), which, True)
+            return psnr_u8(self.frames_mean, self.frames_true)
+        return self._pick(psnr_u8(self.frames_pred, self.frames_true.unsqueeze(1)), which, True)
 
     def ssim_curve(self, which="mean"):
         """SSIM per frame (B,H+1) (dr_frame_ssim); the variants as psnr,
@@ -201,85 +192,42 @@ class FuturesResult:
         self._need_frames("video()")
         i = self.best().view(-1, 1, 1, 1, 1, 1).expand(-1, 1, *self.frames_pred.shape[2:])
         best = self.frames_pred.gather(1, i).squeeze(1)
-        row = lambda f: torch.cat(list(f.transpose(0, 1).unbind(1)), dim=-1)  # (B,K,3,h,w) -> (K,3,h,B*w)
-        return torch.cat((row(self.frames_true), row(best), row(self.frames_mean), row(self.frames_std)),
-                         dim=-2).contiguous()
+        return video_rows(self.frames_true, best, self.frames_mean, self.frames_std)
 
 
 def sample_futures(dr, starts=None, batch_size=None, context=None, horizon=None, samples=8, noise=None, ssim=True,
                    _mark=None, _metrics=None):
     """Dreamer.sample_futures (see there).  _metrics: tools/futures_timing.py's
     replacement of the SSIM / ensemble stage (called with the stage's inputs)."""
-    from .open_loop import check_lengths
-    from .utils import symlog
     mark = _mark or (lambda name: None)
-    S = dr.sequence_length
-    Tc = S // 2 if context is None else int(context)
-    H = min(dr.horizon, S - Tc) if horizon is None else int(horizon)
-    check_lengths(Tc, H, S)
-    buf, wmod = dr.buffer, dr.world_model
-    dev = buf.device
-    if starts is None:
-        n_win = batch_size or dr.batch_size
-        check_futures(int(n_win), samples)
-        starts = buf.sample_start_indices(n_win)
-    st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
-        torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
-    B = int(st.numel())
-    check_futures(B, samples)
-    M = int(samples)
+    Tc, H = window_lengths(dr, context, horizon)
+    buf = dr.buffer
     R, C = dr.latent_state_dims
     A, Hd = dr.action_dims, dr.hidden_state_dims
-    if noise is not None:
-        q_ctx, q = (t.float().contiguous() for t in noise)
-        if tuple(q_ctx.shape) != (Tc, B * R, C) or tuple(q.shape) != (H, B * M * R, C):
-            raise ValueError(f"noise must be ({Tc}, {B * R}, {C}) and ({H}, {B * M * R}, {C})")
-    else:
-        q_ctx = q = None
-    d = wmod.dims(dr.agent)
-    wm = wmod.packed()
-    stream = hip.stream()
-    m = buf._mirror()
-    act = torch.empty(B, S, A, device=dev)
-    rew, cont = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
-    L.call("dr_replay_gather", buf.capacity, B, S, 0, A, None, L.ptr(m["actions"]), L.ptr(m["rewards"]),
-           L.ptr(m["continues"]), L.ptr(st), None, L.ptr(act), L.ptr(rew), L.ptr(cont), stream)
-    mark("gather")
+
+    def draws(B, dev):
+        BM = B * int(samples)
+        return resolve_noise(noise, True, ((Tc, B * R, C), (H, BM * R, C)),
+                             f"noise must be ({Tc}, {B * R}, {C}) and ({H}, {BM * R}, {C})", dev)
+
+    w = window_prologue(dr, starts, batch_size, Tc, draws, mark, check=lambda B: check_futures(B, samples))
+    st, B, M, d, stream = w.st, w.B, int(samples), w.d, w.stream
+    dev = st.device
+    q_ctx, q = w.noise
     # the posterior after the context frames, once per window
-    fr = buf.frames_struct(st)
-    feat = torch.empty(Tc * B, d.enc_hidden, device=dev)
-    ws = hip.workspace(dev).get("enc", L.query("dr_encoder_workspace_bytes", d, Tc * B))
-    L.call("dr_encoder_features", d, wm, fr, B, Tc, L.ptr(feat), L.ptr(ws), ws.numel(), stream)
-    mark("encoder")
-    z0, h0 = torch.empty(B, R * C, device=dev), torch.empty(B, Hd, device=dev)
-    nz = hip.explicit_noise(q=q_ctx, device=dev) if q_ctx is not None else hip.adhoc(dev).noise()
-    ws = hip.workspace(dev).get("obs", L.query("dr_observe_workspace_bytes", d, B))
-    L.call("dr_observe_scan", d, wm, B, Tc, L.ptr(feat), L.ptr(act), S * A, A, None, None, nz, L.ptr(z0),
-           L.ptr(h0), None, L.ptr(ws), ws.numel(), stream)
-    mark("scan")
+    z0, h0 = context_filter(dr, w, Tc, q_ctx, mark)
     # rows b*M + m: the states and the recorded actions Tc-1 .. Tc-2+H, M times each
     BM = B * M
     zr, hr = z0.repeat_interleave(M, dim=0), h0.repeat_interleave(M, dim=0)
-    ar = act[:, Tc - 1:Tc - 1 + H].repeat_interleave(M, dim=0).contiguous()
+    ar = w.act[:, Tc - 1:Tc - 1 + H].repeat_interleave(M, dim=0).contiguous()
     st_rep = st.repeat_interleave(M)
     mark("replicate")
-    lat, hid, r, c = wmod._imagine_actions(d, BM, H, zr, hr, ar.data_ptr(), H * A, A, q)
+    lat, hid, r, c = dr.world_model._imagine_actions(d, BM, H, zr, hr, ar.data_ptr(), H * A, A, q)
     mark("unroll")
     K = H + 1
-    rows = BM * K
     vector = buf.vector
-    shape = (d.obs_dim,) if vector else (3, d.img_h, d.img_w)
-    mu = torch.empty(B, M, K, *shape, device=dev)
-    ws = hip.workspace(dev).get("dec", L.query("dr_decoder_workspace_bytes", d, rows))
-    L.call("dr_decoder_fwd", d, wmod.packed_decoder(), rows, L.ptr(hid), Hd, L.ptr(lat), R * C, L.ptr(mu), L.ptr(ws),
-           ws.numel(), stream)
-    mark("decoder")
-    sqerr = torch.empty(B, M, K, device=dev)
-    pred = None if vector else torch.empty(B, M, K, *shape, dtype=torch.uint8, device=dev)
-    truth_rep = buf.frames_struct(st_rep)
-    truth_rep.t0 = Tc - 1
-    L.call("dr_frame_metrics", d, BM, K, L.ptr(mu), truth_rep, L.ptr(sqerr), L.ptr(pred), None, stream)
-    mark("metrics")
+    ((mu, sqerr, pred),), _, truth_rep = decode_and_score(dr, w, st_rep, (B, M, K), Tc - 1, hid, (lat,), False, mark)
+    shape = tuple(mu.shape[3:])
     truth = buf.frames_struct(st)
     truth.t0 = Tc - 1
     mu_mean = torch.empty(B, K, *shape, device=dev)
@@ -302,20 +250,15 @@ def sample_futures(dr, starts=None, batch_size=None, context=None, horizon=None,
             ss_ens = torch.empty(B, K, device=dev)
             L.call("dr_frame_ssim", d, B, K, L.ptr(mu_mean), truth, L.ptr(ss_ens), None, stream)
         mark("ensemble")
-    # the true frames (target_slots' frame slots, on the device)
-    fslots = (st.view(-1, 1) + (Tc - 1) + torch.arange(K, device=dev).view(1, -1)) % buf.capacity
-    f_true = x_true = None
-    if vector:
-        x_true = m["frames"][fslots]
-    else:
-        f_true = m["frames"][fslots]
+    frames = buf._mirror()["frames"][target_slots(st, Tc, H, buf.capacity)[0]]  # the true frames, on the device
+    f_true, x_true = (None, frames) if vector else (frames, None)
     sl = slice(Tc - 1, Tc - 1 + H)  # state k = 1..H against window step Tc+k-2
     return FuturesResult(latents=lat.view(B, M, K, R, C), hiddens=hid.view(B, M, K, Hd), mu=mu, frames_pred=pred,
                          sqerr=sqerr, ssim=ss, reward_pred=symlog(r).view(B, M, H, 1),
                          continue_pred=c.view(B, M, H, 1), mu_mean=mu_mean, sqerr_mean=sq_mean, spread=spread,
                          ssim_ensemble=ss_ens, frames_mean=f_mean, frames_std=f_std, frames_true=f_true,
-                         x_true=x_true, reward_true=rew[:, sl].unsqueeze(-1).clone(),
-                         continue_true=cont[:, sl].unsqueeze(-1).clone(), context=Tc, horizon=H)
+                         x_true=x_true, reward_true=w.rew[:, sl].unsqueeze(-1).clone(),
+                         continue_true=w.cont[:, sl].unsqueeze(-1).clone(), context=Tc, horizon=H)
 
 
 CURVES = ("mse_mean", "mse_best", "mse_ensemble", "spread", "psnr_mean", "psnr_best", "ssim_mean", "ssim_best",
@@ -336,20 +279,5 @@ def curves_of(r):
 
 def evaluate_futures(dr, batches=1, batch_size=None, context=None, horizon=None, samples=8):
     """Dreamer.evaluate_futures (see there)."""
-    if int(batches) < 1:
-        raise ValueError("evaluate_futures needs batches >= 1")
-    np_state = np.random.get_state()
-    ar = hip.adhoc(dr.device)
-    rng_state, rng_counter = ar.state.clone(), ar.counter
-    try:
-        acc = None
-        with torch.no_grad():
-            for _ in range(int(batches)):
-                cur = curves_of(sample_futures(dr, batch_size=batch_size, context=context, horizon=horizon,
-                                               samples=samples))
-                acc = cur if acc is None else [None if a is None else a + b for a, b in zip(acc, cur)]
-    finally:
-        np.random.set_state(np_state)
-        ar.state.copy_(rng_state)
-        ar.counter = rng_counter
-    return {k: None if a is None else (a / float(batches)).cpu().tolist() for k, a in zip(CURVES, acc)}
+    return average_curves("evaluate_futures", dr, batches, CURVES, lambda: dr.sample_futures(
+        batch_size=batch_size, context=context, horizon=horizon, samples=samples), curves_of)

@@ -1,5 +1,6 @@
-"""Open-loop world-model prediction on replay windows: the result container
-of ``Dreamer.open_loop`` and the window arithmetic it shares with the tests.
+"""Open-loop world-model prediction on replay windows: ``Dreamer.open_loop``
+and ``evaluate_world_model``, their result container and the window arithmetic
+they share with the tests (the front end is replay_eval.py's).
 
 A window b is S = sequence_length consecutive ring slots from starts[b].
 Rollout state 0 is the posterior after the context frames 0 .. Tc-1
@@ -13,6 +14,10 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
+
+from .replay_eval import (FrameResult, average_curves, check_window, context_filter, decode_and_score, head_errors,
+                          psnr_u8, resolve_noise, ring_slots, video_rows, window_prologue)
+from .utils import symlog
 
 
 def frame_step(context, k):
@@ -29,20 +34,27 @@ def target_step(context, k):
 
 def target_slots(starts, context, horizon, capacity):
     """(frame slots [B][H+1], reward / continue slots [B][H]) in the ring, as int64 tensors."""
-    st = torch.as_tensor(starts, dtype=torch.int64).reshape(-1, 1)
-    kf = torch.arange(0, horizon + 1, dtype=torch.int64).reshape(1, -1)
-    kt = torch.arange(1, horizon + 1, dtype=torch.int64).reshape(1, -1)
-    return (st + (context - 1) + kf) % capacity, (st + context + kt - 2) % capacity
+    return ring_slots(starts, context - 1, horizon + 1, capacity), ring_slots(starts, context - 1, horizon, capacity)
 
 
 def check_lengths(context, horizon, sequence_length):
-    if context < 1 or horizon < 1 or context + horizon > sequence_length:
-        raise ValueError(f"open loop needs context >= 1, horizon >= 1 and context + horizon <= sequence_length "
-                         f"(got {context} + {horizon} vs {sequence_length})")
+    check_window(context >= 1 and horizon >= 1 and context + horizon <= sequence_length,
+                 "open loop needs context >= 1, horizon >= 1 and context + horizon <= sequence_length",
+                 f"{context} + {horizon}", sequence_length)
+
+
+def window_lengths(dr, context, horizon):
+    """(Tc, H) with open_loop's defaults -- context S // 2 (the warm start's),
+    horizon min(dr.horizon, S - Tc) -- checked against S."""
+    S = dr.sequence_length
+    Tc = S // 2 if context is None else int(context)
+    H = min(dr.horizon, S - Tc) if horizon is None else int(horizon)
+    check_lengths(Tc, H, S)
+    return Tc, H
 
 
 @dataclass
-class OpenLoopResult:
+class OpenLoopResult(FrameResult):
     """Device tensors of one open-loop prediction over B windows.
 
     latents (B,H+1,R,C), hiddens (B,H+1,hidden): rollout states 0..H.
@@ -66,26 +78,14 @@ class OpenLoopResult:
     context: int
     horizon: int
 
-    def frame_elems(self):
-        n = 1
-        for s in self.mu.shape[2:]:
-            n *= int(s)
-        return n
-
     def mse(self):
         """Mean squared error per frame (B,H+1), on the model's [-0.5, 0.5] scale."""
         return self.sqerr / float(self.frame_elems())
 
-    def _need_frames(self, what):
-        if self.frames_pred is None or self.frames_true is None:
-            raise ValueError(f"{what} needs pixel observations (vector observations have no u8 frames)")
-
     def psnr(self):
         """PSNR per frame (B,H+1) in dB on the u8 scale: 10 log10(255^2 / mean((pred - true)^2))."""
         self._need_frames("psnr()")
-        d = self.frames_pred.float() - self.frames_true.float()
-        m = d.pow(2).flatten(2).mean(-1)
-        return 10.0 * torch.log10(255.0 ** 2 / m)
+        return psnr_u8(self.frames_pred, self.frames_true)
 
     def ssim(self):
         """SSIM per frame (B,H+1) of mu against the true frames (dr_frame_ssim:
@@ -99,5 +99,43 @@ class OpenLoopResult:
         """u8 [H+1][3][2h][B*w]: per step, the true frames above the predicted
         ones, the B windows side by side."""
         self._need_frames("video()")
-        row = lambda f: torch.cat(list(f.transpose(0, 1).unbind(1)), dim=-1)  # (B,K,3,h,w) -> (K,3,h,B*w)
-        return torch.cat((row(self.frames_true), row(self.frames_pred)), dim=-2).contiguous()
+        return video_rows(self.frames_true, self.frames_pred)
+
+
+def open_loop(dr, starts=None, batch_size=None, context=None, horizon=None, sample=True, noise=None, _mark=None):
+    """Dreamer.open_loop (see its docstring)."""
+    mark = _mark or (lambda name: None)
+    Tc, H = window_lengths(dr, context, horizon)
+    R, C = dr.latent_state_dims
+    A, S = dr.action_dims, dr.sequence_length
+
+    def draws(B, dev):
+        shapes = ((Tc, B * R, C), (H, B * R, C))
+        return resolve_noise(noise, sample, shapes, f"noise must be ({Tc}, {B * R}, {C}) and ({H}, {B * R}, {C})", dev)
+
+    w = window_prologue(dr, starts, batch_size, Tc, draws, mark)
+    q_ctx, q = w.noise
+    z0, h0 = context_filter(dr, w, Tc, q_ctx, mark)
+    # the prior under the recorded actions: action Tc-1+k drives state k -> k+1
+    lat, hid, r, c = dr.world_model._imagine_actions(w.d, w.B, H, z0, h0, w.act.data_ptr() + 4 * (Tc - 1) * A, S * A,
+                                                     A, q)
+    mark("unroll")
+    # decode states 0..H and compare with the ring's frames Tc-1 .. Tc-1+H
+    ((mu, sqerr, pred),), true, _ = decode_and_score(dr, w, w.st, (w.B, H + 1), Tc - 1, hid, (lat,), True, mark)
+    sl = slice(Tc - 1, Tc - 1 + H)  # state k = 1..H against window step Tc+k-2
+    return OpenLoopResult(latents=lat, hiddens=hid, mu=mu, frames_pred=pred, frames_true=true, sqerr=sqerr,
+                          reward_pred=symlog(r), reward_true=w.rew[:, sl].unsqueeze(-1).clone(),
+                          continue_pred=c, continue_true=w.cont[:, sl].unsqueeze(-1).clone(), context=Tc, horizon=H)
+
+
+CURVES = ("mse", "psnr", "reward_abs_err", "continue_bce")
+
+
+def curves_of(r):
+    return [r.mse().mean(0), r.psnr().mean(0) if r.frames_pred is not None else None] + head_errors(r)
+
+
+def evaluate_world_model(dr, batches=1, batch_size=None, context=None, horizon=None, sample=True):
+    """Dreamer.evaluate_world_model (see its docstring)."""
+    return average_curves("evaluate_world_model", dr, batches, CURVES, lambda: dr.open_loop(
+        batch_size=batch_size, context=context, horizon=horizon, sample=sample), curves_of)

@@ -276,40 +276,9 @@ def plan_step(dr, observations, state=None, first=None, plan_state=None, **plan_
 
 def evaluate_planner(dr, envs, eval_episodes, **plan_kw):
     """Dreamer.evaluate_planner (see its docstring)."""
-    totals = [0] * eval_episodes
-    with torch.no_grad():
-        slots = []  # [env, episode index] in flight
-        for env in envs[:eval_episodes]:
-            dr.seed += 1
-            slots.append([env, len(slots)])
-        started = len(slots)
-        frames = [env.reset(seed=dr.seed - started + 1 + ep)[0] for env, ep in slots]
-        state, plan_mean, first = None, None, np.ones(len(slots), dtype=bool)
-        while slots:
-            action, (latent, hidden, _), res = plan_step(dr, np.stack(frames), state, first, plan_mean, **plan_kw)
-            action_np = action.detach().cpu().numpy().reshape(len(slots), -1)
-            dr.act_check()
-            keep, frames, first = [], [], []
-            for i, slot in enumerate(slots):
-                env, ep = slot
-                observation_, reward, terminated, truncated, _ = env.step(action_np[i])
-                totals[ep] += reward
-                if not (terminated or truncated):
-                    first.append(False)
-                elif started < eval_episodes:
-                    dr.seed += 1
-                    observation_, _ = env.reset(seed=dr.seed)
-                    slot[1] = started
-                    started += 1
-                    first.append(True)
-                else:
-                    continue
-                keep.append(i)
-                frames.append(observation_)
-            slots = [slots[i] for i in keep]
-            first = np.asarray(first, dtype=bool)
-            if slots:
-                idx = torch.tensor(keep, device=dr.device)
-                state = tuple(t.index_select(0, idx) for t in (latent, hidden, action))
-                plan_mean = res.shifted().index_select(0, idx)
-    return torch.tensor(totals, dtype=torch.float32, device=dr.device).mean()
+    def step(frames, state, first, plan_mean):
+        action, (latent, hidden, _), res = plan_step(dr, frames, state, first, plan_mean, **plan_kw)
+        return action, latent, hidden, res
+
+    # beyond the state, each surviving env carries its plan's shifted mean
+    return dr._run_episodes(envs, eval_episodes, step, carry=lambda res, idx: res.shifted().index_select(0, idx))

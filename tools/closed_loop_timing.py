@@ -15,44 +15,20 @@ min / max of the 3 per-call means.  Needs the GPU.
 
     python tools/closed_loop_timing.py [--out profiles/closed_loop_timing.txt]
 """
-import argparse
-import os
-import sys
-
-import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from open_loop_timing import CFG, HBM_BYTES_PER_S  # noqa: E402
+from timing_common import HBM_BYTES_PER_S, alternate, fill_ring, setup, stage_lines, staged, warm_up, write_out
 
 STAGES = ("gather", "encoder", "trace", "stats", "prior_sample", "decoder", "metrics")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=20)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("closed_loop_timing: needs the GPU (no CPU path)")
-    from dreamer_amd import Dreamer
-    dev = torch.device("cuda:0")
+    args, d = setup("closed_loop_timing", 20)
+    dev = d.device
     B, T = 64, 32
-    torch.manual_seed(0)
-    d = Dreamer(dict(CFG), dev)
-    S, A = d.sequence_length, d.action_dims
+    S = d.sequence_length
     R, C = d.latent_state_dims
-    rng = np.random.default_rng(0)
-    n = 1024
-    d.buffer.load_arrays(rng.integers(0, 256, (n, 3, 64, 64), dtype=np.uint8),
-                         rng.uniform(-1, 1, (n, A)).astype(np.float32), rng.standard_normal(n).astype(np.float32),
-                         np.ones(n, np.float32))
-    np.random.seed(0)
-    starts = d.buffer.sample_start_indices(B)
-    st = torch.as_tensor(starts, dtype=torch.int64).to(dev)
+    st = fill_ring(d, B)
     wm = d.world_model
 
     def new_path(mark=None):
@@ -81,41 +57,10 @@ def main():
         mu_q, mu_p = wm.decoder(hid, lat), wm.decoder(hid, zp)
         return kl, hq, hp, (mu_q - x).pow(2).flatten(2).sum(-1), (mu_p - x).pow(2).flatten(2).sum(-1)
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps  # us per call
-
-    def staged(reps):
-        tot = dict.fromkeys(STAGES, 0.0)
-        for _ in range(reps):
-            ev = [torch.cuda.Event(enable_timing=True)]
-            ev[0].record()
-
-            def mark(name):
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                ev.append(e)
-            new_path(mark)
-            ev[-1].synchronize()
-            for name, a, b in zip(STAGES, ev[:-1], ev[1:]):
-                tot[name] += a.elapsed_time(b) * 1e3
-        return {k: v / reps for k, v in tot.items()}
-
     with torch.no_grad():
-        for _ in range(3):  # warm-up: code objects, workspaces, allocator
-            new_path()
-            old_path()
-        torch.cuda.synchronize()
-        a, b = [], []
-        for _ in range(3):  # alternate the two paths
-            a.append(timed(new_path, args.reps))
-            b.append(timed(old_path, args.reps))
-        split = [staged(args.reps) for _ in range(3)]
+        warm_up(new_path, old_path)
+        a, b = alternate(new_path, old_path, args.reps)
+        split = [staged(STAGES, new_path, args.reps) for _ in range(3)]
     sbytes = B * T * (2 * R * C * 4 + 3 * 4)
     lines = [
         "Closed-loop posterior trace, 1 x MI355X, CarRacing widths, default init under torch.manual_seed(0), fp32,",
@@ -135,9 +80,7 @@ def main():
         "",
         "  stages of (a), us (events between the stages' launches; min / max of 3 means):",
     ]
-    for k in STAGES:
-        v = [s[k] for s in split]
-        lines.append(f"    {k:12s} {min(v):10.1f} / {max(v):10.1f}")
+    lines += stage_lines(STAGES, split, 12)
     sv = [s["stats"] for s in split]
     lines += [
         "",
@@ -147,12 +90,7 @@ def main():
         "  (the stage time is an event interval around one launch, so it includes the launch gap; the",
         "  kernel's own time was not measured).",
     ]
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    write_out(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -17,18 +17,10 @@ the GPU.
 
     python tools/futures_timing.py [--out profiles/futures_timing.txt]
 """
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from open_loop_timing import CFG  # noqa: E402  (the CarRacing widths)
+from timing_common import alternate, fill_ring, setup, stage_lines, staged, warm_up, write_out
 
 STAGES = ("gather", "encoder", "scan", "replicate", "unroll", "decoder", "metrics", "ssim", "ensemble")
 
@@ -69,27 +61,12 @@ def torch_metrics(window2d):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=10)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("futures_timing: needs the GPU (no CPU path)")
-    from dreamer_amd import Dreamer
+    args, d = setup("futures_timing", 10)
     from dreamer_amd.futures import sample_futures
     from dreamer_amd.open_loop import target_slots
-    dev = torch.device("cuda:0")
+    dev = d.device
     B, M, Tc, H = 16, 16, 32, 15
-    torch.manual_seed(0)
-    d = Dreamer(dict(CFG), dev)
-    A = d.action_dims
-    rng = np.random.default_rng(0)
-    n = 1024
-    d.buffer.load_arrays(rng.integers(0, 256, (n, 3, 64, 64), dtype=np.uint8),
-                         rng.uniform(-1, 1, (n, A)).astype(np.float32), rng.standard_normal(n).astype(np.float32),
-                         np.ones(n, np.float32))
-    np.random.seed(0)
-    st = torch.as_tensor(d.buffer.sample_start_indices(B), dtype=torch.int64).to(dev)
+    st = fill_ring(d, B)
     k = np.arange(11, dtype=np.float64)
     g = np.exp(-(k - 5.0) ** 2 / 4.5)
     w = torch.from_numpy((g / g.sum()).astype(np.float32)).to(dev)
@@ -112,34 +89,14 @@ def main():
     def path_b():
         return sample_futures(d, starts=st, context=Tc, horizon=H, samples=M, _metrics=hook)
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps  # us per call
+    hb = []
 
-    def staged(reps):
-        tot = dict.fromkeys(STAGES, 0.0)
-        for _ in range(reps):
-            ev = [torch.cuda.Event(enable_timing=True)]
-            ev[0].record()
-
-            def mark(name):
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                ev.append(e)
-            path_a(mark)
-            ev[-1].synchronize()
-            for name, a, b in zip(STAGES, ev[:-1], ev[1:]):
-                tot[name] += a.elapsed_time(b) * 1e3
-        return {k: v / reps for k, v in tot.items()}
+    def torch_stage():  # (b)'s torch stage over the round's calls
+        hb.append(sum(e0.elapsed_time(e1) for e0, e1 in hook_ev) * 1e3 / len(hook_ev))
+        hook_ev.clear()
 
     with torch.no_grad():
-        for _ in range(3):  # warm-up: code objects, workspaces, allocator
-            path_a(), path_b()
+        warm_up(path_a, path_b)
         # the two paths on the same explicit draws: how far the torch stage is from the kernels
         R, C = d.latent_state_dims
         gen = torch.Generator(device=dev).manual_seed(1)
@@ -150,13 +107,9 @@ def main():
         torch.cuda.synchronize()
         agree = {k: float((getattr(ra, k).float() - getattr(rb, k).float()).abs().max())
                  for k in ("ssim", "ssim_ensemble", "sqerr_mean", "spread", "frames_mean", "frames_std")}
-        a, b, hb = [], [], []
-        for _ in range(3):  # alternate the two paths
-            a.append(timed(path_a, args.reps))
-            hook_ev.clear()
-            b.append(timed(path_b, args.reps))
-            hb.append(sum(e0.elapsed_time(e1) for e0, e1 in hook_ev) * 1e3 / len(hook_ev))
-        split = [staged(args.reps) for _ in range(3)]
+        hook_ev.clear()
+        a, b = alternate(path_a, path_b, args.reps, each_round=torch_stage)
+        split = [staged(STAGES, path_a, args.reps) for _ in range(3)]
     rows = B * M
     lines = [
         "Sampled futures, 1 x MI355X, CarRacing widths, default init under torch.manual_seed(0), fp32,",
@@ -178,17 +131,10 @@ def main():
         "",
         "  stages of (a), us (events between the stages' launches; min / max of 3 means):",
     ]
-    for k in STAGES:
-        v = [s[k] for s in split]
-        lines.append(f"    {k:9s} {min(v):10.1f} / {max(v):10.1f}")
+    lines += stage_lines(STAGES, split, 9)
     lines += ["", "  largest absolute difference between the two paths' outputs on the same explicit draws: "
               + ", ".join(f"{k} {v:.3g}" for k, v in agree.items())]
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    write_out(lines, args.out)
 
 
 if __name__ == "__main__":

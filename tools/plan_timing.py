@@ -16,38 +16,22 @@ min / max of the 3 per-call means.  Needs the GPU.
 
     python tools/plan_timing.py [--out profiles/plan_timing.txt]
 """
-import argparse
-import os
-import sys
-
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from open_loop_timing import CFG  # noqa: E402
+from timing_common import alternate, setup, stage_lines, staged, warm_up, write_out
 
 STAGES_A = ("policy", "sample", "rollout", "critic", "update", "stats")
 STAGES_B = ("policy", "sample", "rollout", "critic", "score", "refit")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--reps", type=int, default=10)
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("plan_timing: needs the GPU (no CPU path)")
-    from dreamer_amd import Dreamer
+    args, d = setup("plan_timing", 10)
     from dreamer_amd import _lib as L
     from dreamer_amd import hip
     from dreamer_amd.plan import _policy_sequences, plan_dims
-    dev = torch.device("cuda:0")
+    dev = d.device
     E, N, N_pi, K, H, J = 8, 512, 24, 64, 15, 6
     temperature, momentum, std_init, std_min, std_max = 0.5, 0.1, 0.5, 0.05, 2.0
-    torch.manual_seed(0)
-    d = Dreamer(dict(CFG), dev)
     R, C = d.latent_state_dims
     A, Hd = d.action_dims, d.hidden_state_dims
     wm, ag = d.world_model, d.agent
@@ -101,42 +85,11 @@ def main():
             mark("refit")
         return mean, std
 
-    def timed(fn, reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) * 1e3 / reps  # us per call
-
-    def staged(fn, stages, reps):
-        tot = dict.fromkeys(stages, 0.0)
-        for _ in range(reps):
-            ev = [(None, torch.cuda.Event(enable_timing=True))]
-            ev[0][1].record()
-
-            def mark(name):
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                ev.append((name, e))
-            fn(mark)
-            ev[-1][1].synchronize()
-            for (_, a), (name, b) in zip(ev[:-1], ev[1:]):
-                tot[name] += a.elapsed_time(b) * 1e3
-        return {k: v / reps for k, v in tot.items()}
-
     with torch.no_grad():
-        for _ in range(2):  # warm-up: code objects, workspaces, allocator
-            new_path()
-            old_path()
-        torch.cuda.synchronize()
-        a, b = [], []
-        for _ in range(3):  # alternate the two paths
-            a.append(timed(new_path, args.reps))
-            b.append(timed(old_path, args.reps))
-        split_a = [staged(new_path, STAGES_A, args.reps) for _ in range(3)]
-        split_b = [staged(old_path, STAGES_B, args.reps) for _ in range(3)]
+        warm_up(new_path, old_path, 2)
+        a, b = alternate(new_path, old_path, args.reps)
+        split_a = [staged(STAGES_A, new_path, args.reps) for _ in range(3)]
+        split_b = [staged(STAGES_B, old_path, args.reps) for _ in range(3)]
     lines = [
         "Latent planning, 1 x MI355X, CarRacing widths, default init under torch.manual_seed(0), fp32,",
         f"E = {E} environments, N = {N} candidates ({N_pi} the actor's), K = {K} elites, H = {H}, J = {J} iterations",
@@ -157,25 +110,16 @@ def main():
         f"  stages of (a), us per call, the {J} iterations summed (events between the stages' launches; min / max of 3",
         "  means):",
     ]
-    for k in STAGES_A:
-        v = [s[k] for s in split_a]
-        lines.append(f"    {k:12s} {min(v):10.1f} / {max(v):10.1f}")
+    lines += stage_lines(STAGES_A, split_a, 12)
     lines += ["", "  stages of (b), likewise:"]
-    for k in STAGES_B:
-        v = [s[k] for s in split_b]
-        lines.append(f"    {k:12s} {min(v):10.1f} / {max(v):10.1f}")
+    lines += stage_lines(STAGES_B, split_b, 12)
     lines += [
         "",
         "  (event intervals around the launches, so they include the launch gaps and the output allocations; the",
         "  kernels' own times were not measured.  sample + update of (a) are the two new kernels; sample + score +",
         "  refit of (b) are the torch ops they replace.)",
     ]
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(text)
+    write_out(lines, args.out)
 
 
 if __name__ == "__main__":
