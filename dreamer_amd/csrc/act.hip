@@ -1,25 +1,34 @@
-// Batch-1 acting step in ONE launch: the per-env-step
-// device work of Dreamer.rollout_policy / evaluate_agent / Run
-// (Dreamer.py:177-226, 295-322, 374-401):
+// The acting step in ONE launch: the per-env-step device
+// work of Dreamer.rollout_policy / evaluate_agent / Run (Dreamer.py:177-226,
+// 295-322, 374-401) for n_env = 1 ... DR_ACT_MAX_ENVS environments at once:
 //
-//   h' = GRU(z, h, a)               WorldModel.observe_step -> SequenceModel   (skipped at an
-//                                   episode start, where h' = h = 0, Dreamer.py:186-187, 222)
-//   z' = Encoder.encode(h', frame)  conv x4 + latent_mapper + categorical sampler (VAE.py:57-99)
+//   h' = GRU(z, h, a)               WorldModel.observe_step -> SequenceModel   (h' = 0 at an
+//                                   episode start, Dreamer.py:186-187, 222)
+//   z' = Encoder.encode(h', obs)    encoder + latent_mapper + categorical sampler (VAE.py:57-99)
 //   a  = Actor.act(h', z')          Agent.py:202-210
 //
-// At batch 1 every stage is a handful of dot products, so the unfused path
-// (about 20 launches per env step) is launch- and dependency-latency bound.
-// Here one cooperative grid of ACT_NB workgroups walks the stages with a grid
-// barrier between dependent ones; inside a stage a wave owns one output row
-// (dense) or one output channel of a 2-row pixel block (conv), holds that
-// row's weights in registers (loads issued together: one round trip), reads
-// the stage input from LDS and reduces with DPP.  f32 VALU arithmetic (no
-// MFMA: at batch 1 no weight fragment has more than 16 rows to serve).
+// At these batch sizes every stage is a handful of dot products, so the
+// unfused path (about 20 launches per env step) is launch- and dependency-
+// latency bound.  Here one cooperative grid of ACT_NB workgroups walks the
+// stages with a grid barrier between dependent ones; inside a stage a wave
+// owns one output row (dense) or one output channel of a 2-row pixel block
+// (conv), holds that row's weights in registers (loads issued together: one
+// round trip) while the rows of the batch pass through it, reads the stage
+// input from LDS and reduces with DPP.  f32 VALU arithmetic (no MFMA: no weight
+// fragment has more than 16 rows to serve).
 //
-// Barrier: one monotonic arrival counter per launch (zeroed by the host before
-// the launch); round k is complete when it reaches k * ACT_NB.  Polling uses
-// agent-scope acquire loads; a bounded spin turns a lost workgroup into NaN
-// outputs instead of a hung GPU.
+// Two kernels share everything but their encoder stages (the skeleton: ActCommon
+// and the act_prologue ... act_finish helpers below):
+//   k_act_batch<NE>  pixel frames, four conv stages        dr_act_step (one row), dr_act_batch
+//   k_act_vec<NE>    vector observations, two dense stages dr_act_vec
+// Every output of every row is summed over k = lane + 64 j, j ascending, then
+// wave_sum, whatever n_env and NE are, so a row's bits do not depend on the
+// batch it travels in.
+//
+// Barrier: monotonic arrival counters per launch (zeroed by the host before
+// the launch); round k is complete when the top counter reaches k * ACT_GROUPS.
+// Polling uses agent-scope loads; a bounded spin turns a lost workgroup into
+// NaN outputs instead of a hung GPU.
 #include "common.h"
 #include "ops.h"
 
@@ -29,21 +38,24 @@
 #define ACT_NT 256
 #define ACT_SPIN_LIMIT (1 << 22)
 #define ACT_BAR_BYTES (4 * 32 * 17)  // 8 group counters, the top counter, 8 generations (128 B apart)
-#define ACT_LDS 6400  // floats of dynamic LDS (25 KB): conv input slabs, GRU / projection inputs
 
-struct alignas(16) ActArgs {
+// What both kernels take: the model, the rows' previous state and noise, the
+// outputs, and the workspace of the shared stages.  Each kernel's argument
+// struct embeds it first and adds its observation pointer and encoder scratch.
+struct alignas(16) ActCommon {
   dr_dims d;
   dr_world_model wm;
   dr_actor ac;
-  const unsigned char* frame;  // [H][W][3] u8 (env observation layout)
-  int has_prev, det;
-  const float *z_prev, *h, *a_prev;
+  const unsigned char* first;  // [n_env] on the device: 1 = episode start (h' = 0); NULL: first_mask
+  unsigned first_mask;         // bit e: row e starts an episode (the host's copy, read when first is NULL)
+  int n_env, det;
+  const float *z_prev, *h, *a_prev;  // [n_env][L], [n_env][hidden], [n_env][A]; a starting row's are not read
   dr_noise noise;
   float *z_out, *h_out, *a_out, *mu_out, *sig_out, *logits_out;
   int* status;  // caller's status word (may be NULL): set to 1 if a grid barrier timed out
-  // workspace
+  // workspace (gi ... prea: one copy per row)
   unsigned* bar;
-  float *c1, *c2, *c3, *c4, *gi, *gh, *hn, *pre1, *prea;
+  float *gi, *gh, *hn, *pre1, *prea;
   int* fail;
   int spin_limit;  // polls before a grid barrier gives up (ACT_SPIN_LIMIT; 0 under DREAMER_ACT_FORCE=timeout)
   long long* ts;  // workgroup 0's stage timestamps (100 MHz wall clock), for profiling
@@ -104,86 +116,17 @@ __device__ __forceinline__ bool act_sync(unsigned* bar, unsigned& round, int* s_
 // so it pays one memory round trip, and reads its stage input from LDS (each
 // workgroup stages the input map / vector it needs).
 
-// k4 s2 p1 conv + bias + SiLU.  Workgroup b owns a block of 2 output rows
-// (pb = b % NPB) and 4 output channels (one per wave): it stages the 6 input
-// rows the block reads into LDS (NHWC, channel stride cin + 1: the pad breaks
-// the stride-2 bank aliasing; rows outside the map are zero padding), each
-// wave holds its channel's weight row [ci][ky][kx] in registers (k = lane +
-// 64 j: coalesced, all issued before the first FMA), then every pixel is one
-// LDS gather + FMA per k and a wave reduction.  cout == 4 * ACT_NB / NPB.
-// FRAME: the input is the u8 HWC frame, normalised x/255 - 0.5 (Dreamer.py:251).
-template <int KJ, bool FRAME, bool NCHW>
-__device__ __forceinline__ void act_conv(int ih, int iw, int cin, int cout, const float* in, const unsigned char* frame,
-                         const float* __restrict__ w, const float* __restrict__ b, float* out, float* xs) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int oh = ih / 2, ow = iw / 2, K = cin * 16, cs = cin + 1;
-  const int npb = oh / 2, pb = blockIdx.x % npb, co = (blockIdx.x / npb) * 4 + wave;
-  const int y0 = 4 * pb - 1;
-  // weights first: their latency overlaps the staging
-  float wv[KJ];
-#pragma unroll
-  for (int j = 0; j < KJ; ++j) {
-    const int k = lane + 64 * j;
-    wv[j] = (k < K && co < cout) ? w[(long long)co * K + k] : 0.f;
-  }
-  const float bias = co < cout ? b[co] : 0.f;
-  const int n = 6 * iw * cin;
-  if (FRAME) {
-    for (int i = threadIdx.x; i < n; i += ACT_NT) {
-      const int r = i / (iw * cin), rem = i - r * iw * cin, y = y0 + r;
-      const int px = rem / cin, ch = rem - px * cin;
-      xs[(r * iw + px) * cs + ch] = (y >= 0 && y < ih) ? (float)frame[(y * iw) * cin + rem] / 255.0f - 0.5f : 0.f;
-    }
-  } else {
-    // 6 float4 per thread at the CarRacing widths (6 x iw x cin = 6144 floats)
-    constexpr int U = 8;
-    const int n4 = n / 4;
-    for (int i0 = threadIdx.x; i0 < n4; i0 += U * ACT_NT) {
-      float4 v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i4 = i0 + u * ACT_NT, e = 4 * i4;
-        const int r = e / (iw * cin), y = y0 + r;
-        v[u] = (i4 < n4 && y >= 0 && y < ih) ? *reinterpret_cast<const float4*>(in + (long long)y0 * iw * cin + e)
-                                              : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i4 = i0 + u * ACT_NT, e = 4 * i4;
-        if (i4 >= n4) break;
-        const int r = e / (iw * cin), rem = e - r * iw * cin, px = rem / cin, ch = rem - px * cin;
-        float* dst = xs + (r * iw + px) * cs + ch;
-        dst[0] = v[u].x; dst[1] = v[u].y; dst[2] = v[u].z; dst[3] = v[u].w;
-      }
-    }
-  }
-  __syncthreads();
-  if (co < cout) {
-    for (int pl = 0; pl < 2 * ow; ++pl) {
-      const int oy = 2 * pb + pl / ow, ox = pl % ow;
-      float acc = 0.f;
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) {
-        const int k = lane + 64 * j, ci = k >> 4, ky = (k >> 2) & 3, kx = k & 3;
-        const int yl = 2 * oy - 1 + ky - y0, x = 2 * ox - 1 + kx;
-        const bool ok = k < K && x >= 0 && x < iw;
-        acc = fmaf(wv[j], ok ? xs[(yl * iw + x) * cs + ci] : 0.f, acc);
-      }
-      acc = wave_sum(acc);
-      if (lane == 0) {
-        const float v = acc + bias;
-        const int p = oy * ow + ox;
-        out[NCHW ? co * oh * ow + p : p * cout + co] = v / (1.0f + expf(-v));
-      }
-    }
-  }
-}
-
-// The batched conv stage: the same (pixel block, channel) task for every frame
-// of a batch with the channel's weights held in registers.  Per frame the
-// one-row path above costs 10-20 us, nearly all of it index arithmetic (about
-// ten VALU instructions per FMA) and one-at-a-time reductions, so here the map
-// shape is a compile-time constant (IW x IW x CIN; act_dims_ok pins it):
+// k4 s2 p1 conv + bias + SiLU, for every frame of the batch.  Workgroup b owns
+// a block of 2 output rows (pb = b % NPB) and 4 output channels (one per wave):
+// it stages the 6 input rows the block reads into an LDS slab (NHWC; rows
+// outside the map are zero padding), each wave holds its channel's weight row
+// [ci][ky][kx] in registers (k = lane + 64 j: coalesced, all issued before the
+// first FMA), then every pixel is one LDS gather + FMA per k and a wave
+// reduction.  cout == 4 * ACT_NB / NPB.
+// Done with run-time map shapes this costs 10-20 us per frame, nearly all of
+// it index arithmetic (about ten VALU instructions per FMA) and one-at-a-time
+// reductions, so the map shape is a compile-time constant (IW x IW x CIN;
+// act_dims_ok pins it):
 //  - the slab has a zero pad column on either side of a row, so no gather
 //    needs a bounds test, and k = lane + 64 j moves the address by 4 j floats,
 //    so every gather is one LDS read at lane base + immediate and one FMA;
@@ -192,8 +135,8 @@ __device__ __forceinline__ void act_conv(int ih, int iw, int cin, int cout, cons
 //    chains overlap; lane p keeps pixel p and the SiLU + store happen once;
 //  - two slabs: frame e + 1 is fetched into registers before frame e's pixels
 //    are computed and written to the other slab after them.
-// Each output is still sum over k = lane + 64 j (j ascending) then wave_sum of
-// the same products as act_conv's, so the bits are the same.
+// Each output is sum over k = lane + 64 j (j ascending) then wave_sum.
+// FRAME: the input is the u8 HWC frame, normalised x/255 - 0.5 (Dreamer.py:251).
 template <int IW, int CIN, bool FRAME>
 struct ActSlab {
   // channel stride CS = 4 (mod 32) and row stride SR = 16 (mod 32): the 64 gather addresses of a pixel,
@@ -287,7 +230,7 @@ __device__ __forceinline__ void act_conv_rows(int n_env, int cout, const float* 
   static_assert(2 * Slab::STRIDE <= ACT_BATCH_CONV_LDS, "slab pair");
   constexpr int NPB = IW / 4;
   const int pb = blockIdx.x % NPB, co = (blockIdx.x / NPB) * 4 + (threadIdx.x >> 6);
-  float wv[KJ];  // the channel's weight row [ci][ky][kx], k = lane + 64 j, as act_conv
+  float wv[KJ];  // the channel's weight row [ci][ky][kx], k = lane + 64 j
 #pragma unroll
   for (int j = 0; j < KJ; ++j) {
     const int k = (threadIdx.x & 63) + 64 * j;
@@ -311,38 +254,12 @@ __device__ __forceinline__ void act_conv_rows(int n_env, int cout, const float* 
   }
 }
 
-// y[o] = b[o] + W[o][0:K] . x for x in LDS: one wave task per output row,
-// k = lane + 64 j (coalesced row reads, KJ loads in flight per batch)
-template <int KJ>
-__device__ __forceinline__ void act_dense(int nout, int K, const float* __restrict__ W, long long ldw, const float* __restrict__ b,
-                          const float* xs, float* y, int gw, int nw) {
-  const int lane = threadIdx.x & 63;
-  for (int o = gw; o < nout; o += nw) {
-    const float* wr = W + (long long)o * ldw;
-    float acc = 0.f;
-    for (int k0 = 0; k0 < K; k0 += 64 * KJ) {
-      float wv[KJ];
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) {
-        const int k = k0 + lane + 64 * j;
-        wv[j] = k < K ? wr[k] : 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < KJ; ++j) {
-        const int k = k0 + lane + 64 * j;
-        acc = fmaf(wv[j], k < K ? xs[k] : 0.f, acc);
-      }
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) y[o] = acc + (b ? b[o] : 0.f);
-  }
-}
-
-// act_dense for up to NE input rows at once (xs + r * xld, outputs y + r * yld;
-// bit r of `rows` set = row r is live): the output row's weights are loaded
-// once and stay in registers while every live input row accumulates against
-// them -- per input row the same k order and reduction as act_dense, so the
-// same bits.
+// y_r[o] = b[o] + W[o][0:K] . x_r for up to NE input rows x_r in LDS (xs + r *
+// xld, outputs y + r * yld; bit r of `rows` set = row r is live): one wave task
+// per output row, k = lane + 64 j (coalesced row reads, KJ loads in flight per
+// batch).  The output row's weights are loaded once and stay in registers
+// while every live input row accumulates against them -- per input row the
+// same k order and reduction whatever NE is, so the same bits.
 template <int KJ, int NE>
 __device__ __forceinline__ void act_dense_rows(int nout, int K, const float* __restrict__ W, long long ldw,
                                                const float* __restrict__ b, const float* xs, int xld, float* y,
@@ -582,259 +499,6 @@ __device__ __forceinline__ void act_actor_tail(const dr_dims& d, const dr_actor&
   }
 }
 
-__global__ __launch_bounds__(ACT_NT) void k_act_step(ActArgs ga) {
-  __shared__ ActArgs a;
-  __shared__ int s_ok;
-  // stage inputs: the largest is conv2's input map, 32 x 32 pixels x 32 channels at a
-  // channel stride of 33 (ACT_LDS floats)
-  extern __shared__ __attribute__((aligned(16))) float xs[];
-  if (threadIdx.x < sizeof(ActArgs) / 16)
-    reinterpret_cast<int4*>(&a)[threadIdx.x] = reinterpret_cast<const int4*>(&ga)[threadIdx.x];
-  __syncthreads();
-  const dr_dims& d = a.d;
-  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6), nw = ACT_NB * (ACT_NT / 64);
-  const int Hd = d.hidden, R = d.rows, C = d.cols, L = R * C, A = d.action;
-  const int c1 = d.enc_f1, c2 = d.enc_f2, c3 = 2 * c2, c4 = 4 * c2;
-  const int H0 = d.img_h, W0 = d.img_w, F = c4 * (H0 / 16) * (W0 / 16);
-  unsigned round = 0;
-  bool ok = true;
-  ACT_TS(a, 0);
-
-  // ---- stage 1: GRU pre-activations gi = W_ih [z; a] + b, gh = W_hh h + b  ||  conv1 from the frame ----
-  const int off = 2048;  // conv slabs use xs[0, 6 * 64 * 4)
-  if (a.has_prev) {
-    act_stage<5>(xs + off, L + A, [&](int i) { return i < L ? a.z_prev[i] : a.a_prev[i - L]; });
-    act_stage<3>(xs + off + 2048, Hd, [&](int i) { return a.h[i]; });
-    __syncthreads();
-    act_dense<17>(3 * Hd, L + A, a.wm.w_ih, L + A, a.wm.b_ih, xs + off, a.gi, gw, nw);
-    act_dense<10>(3 * Hd, Hd, a.wm.w_hh, Hd, a.wm.b_hh, xs + off + 2048, a.gh, gw, nw);
-  }
-  act_conv<1, true, false>(H0, W0, 3, c1, nullptr, a.frame, a.wm.conv[0].w, a.wm.conv[0].b, a.c1, xs);
-  ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 1);
-  // ---- stage 2: conv2  ||  GRU gates (torch gru_cell order r, z, n) ----
-  if (ok) {
-    const int gt = blockIdx.x * ACT_NT + threadIdx.x;
-    for (int j = gt; j < Hd; j += ACT_NB * ACT_NT) {
-      const float hv = a.h[j];
-      const float hn = a.has_prev ? act_gru_gates(a.gi, a.gh, Hd, j, hv) : hv;
-      a.hn[j] = hn;
-      a.h_out[j] = hn;
-    }
-    act_conv<8, false, false>(H0 / 2, W0 / 2, c1, c2, a.c1, nullptr, a.wm.conv[1].w, a.wm.conv[1].b, a.c2, xs);
-  }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 2);
-  if (ok) act_conv<16, false, false>(H0 / 4, W0 / 4, c2, c3, a.c2, nullptr, a.wm.conv[2].w, a.wm.conv[2].b, a.c3, xs);
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 3);
-  if (ok) act_conv<32, false, true>(H0 / 8, W0 / 8, c3, c4, a.c3, nullptr, a.wm.conv[3].w, a.wm.conv[3].b, a.c4, xs);
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 4);
-  // ---- stage 5: latent_mapper.0 on cat(features, h') (VAE.py:73) ----
-  if (ok) {
-    act_stage<19>(xs, F + Hd, [&](int i) { return i < F ? a.c4[i] : a.hn[i - F]; });
-    __syncthreads();
-    act_dense<25>(d.enc_hidden, F + Hd, a.wm.map0.w, F + Hd, a.wm.map0.b, xs, a.pre1, gw, nw);
-  }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 5);
-  // ---- stage 6: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per latent group ----
-  if (ok && gw < R)
-    act_latent_group(d, a.wm, a.pre1, gw, a.noise.q, a.noise.rng, a.noise.stream, a.noise.row0, a.z_out,
-                     a.logits_out, xs);
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 6);
-  // ---- stage 7: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
-  if (ok) {
-    act_stage<7>(xs, Hd + L, [&](int i) { return i < Hd ? a.hn[i] : a.z_out[i - Hd]; });
-    __syncthreads();
-    act_dense<26>(d.actor_h1, Hd + L, a.ac.l0.w, Hd + L, a.ac.l0.b, xs, a.prea, gw, nw);
-  }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 7);
-  // A barrier that timed out (a workgroup never arrived: the grid was not
-  // co-resident) is reported, never silent: every workgroup that saw it raises
-  // the status word the host checks after the step, and writes NaN to every
-  // output (action, mu, sigma, z', h') so nothing downstream can mistake them
-  // for a state.
-  // Workgroup 0 also re-reads the shared fail flag after the last barrier: a
-  // workgroup that timed out there raised it after arriving (its stage data is
-  // complete), but the outputs are poisoned all the same.  `status` stays the
-  // authoritative signal (a flag raised after this read is seen only there).
-  if (blockIdx.x == 0) {  // (uniform over the workgroup: every wave takes both barriers)
-    __shared__ int s_fail;
-    if (threadIdx.x == 0) s_fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_fail) ok = false;
-  }
-  if (!ok) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // every failing workgroup poisons every output after its own writes: a
-    // workgroup that got past the barrier workgroup 0 gave up on still writes
-    // its h' / z' slice (a forced-timeout run caught workgroup 0's NaN being
-    // overwritten that way), but it cannot pass the next barrier (workgroup 0
-    // never arrives), so it fails too and poisons after its writes
-    const float qnan = __int_as_float(0x7fc00000);
-    for (int i = threadIdx.x; i < A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
-    for (int i = threadIdx.x; i < L; i += ACT_NT) a.z_out[i] = qnan;
-    for (int i = threadIdx.x; i < Hd; i += ACT_NT) a.h_out[i] = qnan;
-    return;
-  }
-  // ---- stage 8 (workgroup 0): LN-SiLU, base_net.3, LN-SiLU, mu / log_sigma heads, tanh(mu + eps sigma) ----
-  if (blockIdx.x != 0) return;
-  act_actor_tail(d, a.ac, a.prea, a.det, a.noise.eps, a.noise.rng, a.noise.stream + 1, a.noise.row0, a.a_out,
-                 a.mu_out, a.sig_out, xs);
-  ACT_TS(a, 15);
-}
-
-static void act_carve(char* base, const dr_dims* d, ActArgs& a, size_t& off) {
-  auto take = [&](size_t bytes) {
-    const size_t o = (off + 255) & ~(size_t)255;
-    off = o + bytes;
-    return base ? base + o : nullptr;
-  };
-  const int c1 = d->enc_f1, c2 = d->enc_f2;
-  const long long p1 = (long long)(d->img_h / 2) * (d->img_w / 2);
-  a.ts = (long long*)take(16 * sizeof(long long));  // first: tools read it at offset 0
-  a.bar = (unsigned*)take(ACT_BAR_BYTES);
-  a.fail = (int*)take(256);
-  a.c1 = (float*)take(4 * p1 * c1);
-  a.c2 = (float*)take(4 * (p1 / 4) * c2);
-  a.c3 = (float*)take(4 * (p1 / 16) * 2 * c2);
-  a.c4 = (float*)take(4 * (p1 / 64) * 4 * c2);
-  a.gi = (float*)take(4 * 3 * d->hidden);
-  a.gh = (float*)take(4 * 3 * d->hidden);
-  a.hn = (float*)take(4 * d->hidden);
-  a.pre1 = (float*)take(4 * d->enc_hidden);
-  a.prea = (float*)take(4 * d->actor_h1);
-}
-
-// the stage helpers' register batches (KJ) and the LDS staging are sized for the
-// CarRacing encoder (Dreamer.py:20-64 config); other shapes use the unfused calls
-static bool act_dims_ok(const dr_dims* d) {
-  const int F = 4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = d->rows * d->cols;
-  return (d->enc_depth == 0 || d->enc_depth == 4) && d->img_h == 64 && d->img_w == 64 && d->enc_f1 == 32 &&
-         d->enc_f2 == 64 && F + d->hidden <= 64 * 74 && L + d->action <= 64 * 17 && d->hidden <= 64 * 10 &&
-         d->hidden + L <= 64 * 26 && d->cols <= 64 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden <= 256 &&
-         d->actor_h1 <= 256 && d->actor_h2 <= 1024 && d->action <= 64;
-}
-
-extern "C" size_t dr_act_step_workspace_bytes(const dr_dims* d) {
-  ActArgs a;
-  size_t off = 0;
-  act_carve(nullptr, d, a, off);
-  return off;
-}
-
-extern "C" int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, const unsigned char* frame,
-                           int has_prev, const float* z_prev, const float* h, const float* a_prev, dr_noise noise,
-                           int deterministic, float* z_out, float* h_out, float* a_out, float* mu_out,
-                           float* sigma_out, float* logits_out, int* status, void* ws, size_t ws_bytes,
-                           hipStream_t s) {
-  DR_REQUIRE(d && wm && ac && frame && h && z_out && h_out && a_out && mu_out && sigma_out && ws, "null argument");
-  DR_REQUIRE(!has_prev || (z_prev && a_prev), "has_prev needs z_prev and a_prev");
-  DR_REQUIRE(d->obs_dim == 0, "dr_act_step: pixel observations only (vector observations use the unfused path)");
-  if (!act_dims_ok(d)) {
-    dr_set_error("dr_act_step: dims outside the batch-1 acting kernel (64x64 frames, encoder 32/64 filters, widths "
-                 "<= the staging)");
-    return DR_E_UNSUPPORTED;
-  }
-  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
-  const bool force_timeout = force && strcmp(force, "timeout") == 0;
-  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
-  ActArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d = *d;
-  a.wm = *wm;
-  a.ac = *ac;
-  a.frame = frame;
-  a.has_prev = has_prev;
-  a.det = deterministic;
-  a.z_prev = z_prev;
-  a.h = h;
-  a.a_prev = a_prev;
-  a.noise = noise;
-  a.z_out = z_out;
-  a.h_out = h_out;
-  a.a_out = a_out;
-  a.mu_out = mu_out;
-  a.sig_out = sigma_out;
-  a.logits_out = logits_out;
-  a.status = status;
-  size_t off = 0;
-  act_carve((char*)ws, d, a, off);
-  DR_REQUIRE(off <= ws_bytes, "workspace too small");
-  // barrier lines + fail flag (a kernel, so a captured graph re-arms them too)
-  static_assert((ACT_BAR_BYTES + 512) % 4 == 0, "barrier bytes");
-  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(a.bar), 0.f, s));
-  // A plain launch whose grid barrier needs all ACT_NB workgroups resident at
-  // once.  The cooperative launch would add exactly that check at +15-19 us of
-  // host time per env step (MI355X_MICROARCH.md coop-launch), so it is made
-  // once per device here instead: the occupancy API's blocks per CU (one lower
-  // than reported, the guide's sgpr-count margin) times the CU count must
-  // cover the grid, else the call fails and the caller runs the unfused path.
-  // What no launch-time check can cover -- other work holding CUs for longer
-  // than the bounded spin -- comes back through `status` (and NaN outputs).
-  static int resident_ok[64];  // per device: 0 unknown, 1 ok, -1 too small (idempotent, benign race)
-  int dev = 0;
-  DR_TRY_HIP(hipGetDevice(&dev));
-  DR_REQUIRE(dev >= 0 && dev < 64, "device index");
-  if (resident_ok[dev] == 0) {
-    (void)hipFuncSetAttribute((const void*)k_act_step, hipFuncAttributeMaxDynamicSharedMemorySize, ACT_LDS * 4);
-    int per_cu = 0, cus = 0;
-    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_act_step, ACT_NT, ACT_LDS * 4));
-    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    resident_ok[dev] = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
-  }
-  if (resident_ok[dev] != 1 || force_nonres) {
-    dr_set_error("dr_act_step: the device cannot hold the acting grid co-resident");
-    return DR_E_UNSUPPORTED;
-  }
-  a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
-  hipLaunchKernelGGL(k_act_step, dim3(ACT_NB), dim3(ACT_NT), ACT_LDS * 4, s, a);
-  return dr_check_launch("act_step");
-}
-
-// ---------------------------------------------------------------------------
-// Batched acting: the same step for n_env <= DR_ACT_MAX_ENVS environments in
-// one launch (vectorised rollout_policy / evaluate_agent).  Same grid, same
-// barrier and the same stage helpers as k_act_step; what changes is that a
-// wave keeps its weight row in registers while the rows of the batch pass
-// through it:
-//   conv stages   the workgroup's (pixel block, 4 channels) of every frame in
-//                 turn, slab restaged per frame (act_conv_rows)
-//   dense stages  up to NE rows' inputs side by side in LDS, NE accumulators
-//                 per wave (act_dense_rows); where a stage has at most half as
-//                 many output rows as the grid has waves (latent_mapper.0,
-//                 actor base_net.0) the batch is split over the two halves of
-//                 the grid
-//   sampler       one wave per (row, latent group)
-//   actor tail    row e in workgroup e
-// Every row keeps the one-row kernel's summation order, so its outputs are
-// the bits dr_act_step gives on that row's inputs, whatever n_env is.
-struct alignas(16) ActBatchArgs {
-  dr_dims d;
-  dr_world_model wm;
-  dr_actor ac;
-  const unsigned char* frames;  // [n_env][H][W][3] u8
-  const unsigned char* first;   // [n_env]: 1 = episode start (h' = 0)
-  int n_env, det;
-  const float *z_prev, *h, *a_prev;  // [n_env][L], [n_env][hidden], [n_env][A]
-  dr_noise noise;
-  float *z_out, *h_out, *a_out, *mu_out, *sig_out, *logits_out;
-  int* status;
-  // workspace (c1 ... prea: one copy per row)
-  unsigned* bar;
-  float *c1, *c2, *c3, *c4, *gi, *gh, *hn, *pre1, *prea;
-  int* fail;
-  int spin_limit;
-  long long* ts;
-};
-
 #define ACT_NW (ACT_NB * (ACT_NT / 64))
 // a dense stage with at most ACT_NW / 2 output rows runs as two halves of the grid, each on half the batch
 __host__ __device__ inline int act_dense_splits(int nout) { return 2 * nout <= ACT_NW ? 2 : 1; }
@@ -862,27 +526,156 @@ __device__ __forceinline__ void act_dense_batch(int n_env, unsigned skip, int no
   }
 }
 
-template <int NE>
-__global__ __launch_bounds__(ACT_NT) void k_act_batch(ActBatchArgs ga) {
-  __shared__ ActBatchArgs a;
-  __shared__ int s_ok;
-  __shared__ unsigned s_first;  // bit e: row e starts an episode
-  extern __shared__ __attribute__((aligned(16))) float xs[];
-  static_assert(sizeof(ActBatchArgs) / 16 <= ACT_NT, "argument copy");
-  if (threadIdx.x < sizeof(ActBatchArgs) / 16)
+// ---------------------------------------------------------------------------
+// The skeleton: what k_act_batch and k_act_vec do alike.  A kernel is
+//   act_prologue | act_gru_pre || encoder stage | act_gru_rows || encoder stage
+//   | more encoder stages | latent_mapper.0 | act_sample_rows | act_actor_l0 |
+//   act_finish
+// with an act_sync between the parts divided by `|`; where a stage has at most
+// half as many output rows as the grid has waves (latent_mapper.0, actor
+// base_net.0) act_dense_batch splits the batch over the two halves of the grid.
+// The sampler runs one wave per (row, latent group), row e's actor tail runs
+// in workgroup e.
+
+// a workgroup's words of static LDS beside its copy of the arguments
+struct ActShared {
+  int ok;          // act_sync's verdict on the last round
+  unsigned first;  // bit e: row e starts an episode
+  int fail;        // act_finish's reading of the grid's fail flag
+};
+
+// the kernel arguments into LDS; returns the mask of the rows that start an episode, from first[] on the device
+// or, where the entry point had the flags on the host (dr_act_step), from first_mask
+template <typename Args>
+__device__ __forceinline__ unsigned act_prologue(Args& a, const Args& ga, ActShared& sh) {
+  static_assert(sizeof(Args) % 16 == 0 && sizeof(Args) / 16 <= ACT_NT, "argument copy");
+  if (threadIdx.x < sizeof(Args) / 16)
     reinterpret_cast<int4*>(&a)[threadIdx.x] = reinterpret_cast<const int4*>(&ga)[threadIdx.x];
   if (threadIdx.x == 0) {
-    unsigned m = 0;
-    for (int e = 0; e < ga.n_env; ++e)
-      if (ga.first[e]) m |= 1u << e;
-    s_first = m;
+    unsigned m = ga.c.first_mask;
+    if (ga.c.first) {
+      m = 0;
+      for (int e = 0; e < ga.c.n_env; ++e)
+        if (ga.c.first[e]) m |= 1u << e;
+    }
+    sh.first = m;
   }
   __syncthreads();
+  return sh.first;
+}
+
+// GRU pre-activations of the continuing rows: gi = W_ih [z; a] + b, gh = W_hh h + b
+template <int NE>
+__device__ __forceinline__ void act_gru_pre(const ActCommon& a, unsigned first, float* xs) {
+  const int Hd = a.d.hidden, L = a.d.rows * a.d.cols, A = a.d.action;
+  act_dense_batch<17, NE>(a.n_env, first, 3 * Hd, L + A, a.wm.w_ih, a.wm.b_ih, xs, a.gi, 3 * Hd,
+                          [&](float* dst, int e) {
+                            act_stage<5>(dst, L + A, [&](int i) {
+                              return i < L ? a.z_prev[(long long)e * L + i] : a.a_prev[e * A + i - L];
+                            });
+                          });
+  act_dense_batch<10, NE>(a.n_env, first, 3 * Hd, Hd, a.wm.w_hh, a.wm.b_hh, xs, a.gh, 3 * Hd, [&](float* dst, int e) {
+    act_stage<3>(dst, Hd, [&](int i) { return a.h[e * Hd + i]; });
+  });
+}
+
+// the GRU gates of every row, one element per thread over the grid; h' = 0 at an episode start (h is not read)
+__device__ __forceinline__ void act_gru_rows(const ActCommon& a, unsigned first) {
+  const int Hd = a.d.hidden;
+  const int gt = blockIdx.x * ACT_NT + threadIdx.x;
+  for (int i = gt; i < a.n_env * Hd; i += ACT_NB * ACT_NT) {
+    const int e = i / Hd, j = i - e * Hd;
+    const float hn = ((first >> e) & 1u) ? 0.f : act_gru_gates(a.gi + e * 3 * Hd, a.gh + e * 3 * Hd, Hd, j, a.h[i]);
+    a.hn[i] = hn;
+    a.h_out[i] = hn;
+  }
+}
+
+// LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per (row, latent group)
+__device__ __forceinline__ void act_sample_rows(const ActCommon& a, float* xs) {
+  const int R = a.d.rows, L = R * a.d.cols;
+  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6);
+  for (int t = gw; t < a.n_env * R; t += ACT_NW) {
+    const int e = t / R, grp = t - e * R;
+    act_latent_group(a.d, a.wm, a.pre1 + e * a.d.enc_hidden, grp, a.noise.q ? a.noise.q + (long long)e * L : nullptr,
+                     a.noise.rng, a.noise.stream, a.noise.row0 + e, a.z_out + (long long)e * L,
+                     a.logits_out ? a.logits_out + (long long)e * L : nullptr, xs);
+  }
+}
+
+// actor base_net.0 on cat(h', z') (Agent.py:191-200)
+template <int NE>
+__device__ __forceinline__ void act_actor_l0(const ActCommon& a, float* xs) {
+  const int Hd = a.d.hidden, L = a.d.rows * a.d.cols;
+  act_dense_batch<26, NE>(a.n_env, 0u, a.d.actor_h1, Hd + L, a.ac.l0.w, a.ac.l0.b, xs, a.prea, a.d.actor_h1,
+                          [&](float* dst, int e) {
+                            act_stage<7>(dst, Hd + L, [&](int i) {
+                              return i < Hd ? a.hn[e * Hd + i] : a.z_out[(long long)e * L + i - Hd];
+                            });
+                          });
+}
+
+// After the last barrier: the failure path, else row e's actor tail in workgroup e.
+// A barrier that timed out (a workgroup never arrived: the grid was not
+// co-resident) is reported, never silent: every workgroup that saw it raises
+// the status word the host checks after the step, and writes NaN to every
+// output of every row (action, mu, sigma, z', h') so nothing downstream can
+// mistake them for a state.
+// The workgroups that run a tail also re-read the shared fail flag after the
+// last barrier: a workgroup that timed out there raised it after arriving (its
+// stage data is complete), but the outputs are poisoned all the same.  `status`
+// stays the authoritative signal (a flag raised after this read is seen only
+// there).
+__device__ __forceinline__ void act_finish(const ActCommon& a, bool ok, ActShared& sh, float* xs) {
+  const int N = a.n_env, Hd = a.d.hidden, L = a.d.rows * a.d.cols, A = a.d.action;
+  if (blockIdx.x < N) {  // (uniform over the workgroup: every wave takes both barriers)
+    if (threadIdx.x == 0) sh.fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (sh.fail) ok = false;
+  }
+  if (!ok) {
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    // every failing workgroup poisons every output after its own writes: a
+    // workgroup that got past the barrier workgroup 0 gave up on still writes
+    // its h' / z' slice (a forced-timeout run caught workgroup 0's NaN being
+    // overwritten that way), but it cannot pass the next barrier (workgroup 0
+    // never arrives), so it fails too and poisons after its writes
+    const float qnan = __int_as_float(0x7fc00000);
+    for (int i = threadIdx.x; i < N * A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * L; i += ACT_NT) a.z_out[i] = qnan;
+    for (int i = threadIdx.x; i < N * Hd; i += ACT_NT) a.h_out[i] = qnan;
+    return;
+  }
+  // LN-SiLU, base_net.3, LN-SiLU, mu / log_sigma heads, tanh(mu + eps sigma)
+  if (blockIdx.x >= N) return;
+  const int e = blockIdx.x;
+  act_actor_tail(a.d, a.ac, a.prea + e * a.d.actor_h1, a.det, a.noise.eps ? a.noise.eps + e * A : nullptr, a.noise.rng,
+                 a.noise.stream + 1, a.noise.row0 + e, a.a_out + e * A, a.mu_out + e * A, a.sig_out + e * A, xs);
+  ACT_TS(a, 15);
+}
+
+// ---------------------------------------------------------------------------
+// Pixel observations: the encoder is four conv stages, the first two beside
+// the GRU stages; seven barrier rounds.
+struct alignas(16) ActBatchArgs {
+  ActCommon c;
+  const unsigned char* frames;  // [n_env][H][W][3] u8 (env observation layout)
+  float *c1, *c2, *c3, *c4;     // the conv stages' outputs, one copy per row
+};
+
+template <int NE>
+__global__ __launch_bounds__(ACT_NT) void k_act_batch(ActBatchArgs ga) {
+  __shared__ ActBatchArgs sa;
+  __shared__ ActShared sh;
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  const unsigned first = act_prologue(sa, ga, sh);
+  const ActCommon& a = sa.c;
   const dr_dims& d = a.d;
   const int N = a.n_env;
-  const unsigned first = s_first;
-  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6);
-  const int Hd = d.hidden, R = d.rows, C = d.cols, L = R * C, A = d.action;
+  const int Hd = d.hidden;
   const int c1 = d.enc_f1, c2 = d.enc_f2, c3 = 2 * c2, c4 = 4 * c2;
   const int H0 = d.img_h, W0 = d.img_w, F = c4 * (H0 / 16) * (W0 / 16);
   const long long p1 = (long long)(H0 / 2) * (W0 / 2);
@@ -892,115 +685,301 @@ __global__ __launch_bounds__(ACT_NT) void k_act_batch(ActBatchArgs ga) {
   ACT_TS(a, 0);
 
   // ---- stage 1: GRU pre-activations of the continuing rows  ||  conv1 from the frames ----
-  act_dense_batch<17, NE>(N, first, 3 * Hd, L + A, a.wm.w_ih, a.wm.b_ih, xs, a.gi, 3 * Hd, [&](float* dst, int e) {
-    act_stage<5>(dst, L + A, [&](int i) { return i < L ? a.z_prev[(long long)e * L + i] : a.a_prev[e * A + i - L]; });
-  });
-  act_dense_batch<10, NE>(N, first, 3 * Hd, Hd, a.wm.w_hh, a.wm.b_hh, xs, a.gh, 3 * Hd, [&](float* dst, int e) {
-    act_stage<3>(dst, Hd, [&](int i) { return a.h[e * Hd + i]; });
-  });
+  act_gru_pre<NE>(a, first, xs);
   // (map shapes as template arguments: act_dims_ok admits only 64 x 64 frames and 32 / 64 filters)
-  act_conv_rows<1, true, false, 64, 3>(N, c1, nullptr, 0, a.frames, a.wm.conv[0].w, a.wm.conv[0].b, a.c1, n1, xs);
-  ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  act_conv_rows<1, true, false, 64, 3>(N, c1, nullptr, 0, sa.frames, a.wm.conv[0].w, a.wm.conv[0].b, sa.c1, n1, xs);
+  ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 1);
-  // ---- stage 2: conv2  ||  GRU gates; h' = 0 at an episode start ----
+  // ---- stage 2: conv2  ||  GRU gates ----
   if (ok) {
-    const int gt = blockIdx.x * ACT_NT + threadIdx.x;
-    for (int i = gt; i < N * Hd; i += ACT_NB * ACT_NT) {
-      const int e = i / Hd, j = i - e * Hd;
-      const float hn = ((first >> e) & 1u) ? 0.f : act_gru_gates(a.gi + e * 3 * Hd, a.gh + e * 3 * Hd, Hd, j, a.h[i]);
-      a.hn[i] = hn;
-      a.h_out[i] = hn;
-    }
-    act_conv_rows<8, false, false, 32, 32>(N, c2, a.c1, n1, nullptr, a.wm.conv[1].w, a.wm.conv[1].b, a.c2, n2, xs);
+    act_gru_rows(a, first);
+    act_conv_rows<8, false, false, 32, 32>(N, c2, sa.c1, n1, nullptr, a.wm.conv[1].w, a.wm.conv[1].b, sa.c2, n2, xs);
   }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 2);
   if (ok)
-    act_conv_rows<16, false, false, 16, 64>(N, c3, a.c2, n2, nullptr, a.wm.conv[2].w, a.wm.conv[2].b, a.c3, n3, xs);
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+    act_conv_rows<16, false, false, 16, 64>(N, c3, sa.c2, n2, nullptr, a.wm.conv[2].w, a.wm.conv[2].b, sa.c3, n3, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 3);
   if (ok)
-    act_conv_rows<32, false, true, 8, 128>(N, c4, a.c3, n3, nullptr, a.wm.conv[3].w, a.wm.conv[3].b, a.c4, n4, xs);
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+    act_conv_rows<32, false, true, 8, 128>(N, c4, sa.c3, n3, nullptr, a.wm.conv[3].w, a.wm.conv[3].b, sa.c4, n4, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 4);
   // ---- stage 5: latent_mapper.0 on cat(features, h') (VAE.py:73) ----
   if (ok)
     act_dense_batch<25, NE>(N, 0u, d.enc_hidden, F + Hd, a.wm.map0.w, a.wm.map0.b, xs, a.pre1, d.enc_hidden,
                             [&](float* dst, int e) {
                               act_stage<19>(dst, F + Hd,
-                                            [&](int i) { return i < F ? a.c4[e * n4 + i] : a.hn[e * Hd + i - F]; });
+                                            [&](int i) { return i < F ? sa.c4[e * n4 + i] : a.hn[e * Hd + i - F]; });
                             });
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 5);
-  // ---- stage 6: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per (row, latent group) ----
-  if (ok)
-    for (int t = gw; t < N * R; t += ACT_NW) {
-      const int e = t / R, grp = t - e * R;
-      act_latent_group(d, a.wm, a.pre1 + e * d.enc_hidden, grp, a.noise.q ? a.noise.q + (long long)e * L : nullptr,
-                       a.noise.rng, a.noise.stream, a.noise.row0 + e, a.z_out + (long long)e * L,
-                       a.logits_out ? a.logits_out + (long long)e * L : nullptr, xs);
-    }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
+  // ---- stage 6: the sampler ----
+  if (ok) act_sample_rows(a, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
   ACT_TS(a, 6);
-  // ---- stage 7: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
+  // ---- stage 7: actor base_net.0 ----
+  if (ok) act_actor_l0<NE>(a, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 7);
+  // ---- stage 8: the failure path, or the actor tails ----
+  act_finish(a, ok, sh, xs);
+}
+
+// ---------------------------------------------------------------------------
+// Vector observations (dr_dims.obs_dim = D > 0, BASELINE configs[4]): the
+// encoder's four conv stages are two small dense layers (conv[0] = Linear(D,
+// F) + SiLU, conv[1] = Linear(F, F) + SiLU, F = 4 * enc_f2),
+// which overlap the two GRU stages, so the step takes five barrier rounds
+// instead of seven.  Both are act_dense_batch like every other dense stage; a
+// layer's SiLU is applied where the next stage stages its input into LDS.
+struct alignas(16) ActVecArgs {
+  ActCommon c;
+  const float* obs;  // [n_env][obs_dim] f32
+  float *y0, *y1;    // the encoder layers' pre-activations [F], one copy per row
+};
+
+__device__ __forceinline__ float act_silu(float v) { return v / (1.0f + expf(-v)); }
+
+template <int NE>
+__global__ __launch_bounds__(ACT_NT) void k_act_vec(ActVecArgs ga) {
+  __shared__ ActVecArgs sa;
+  __shared__ ActShared sh;
+  extern __shared__ __attribute__((aligned(16))) float xs[];
+  const unsigned first = act_prologue(sa, ga, sh);
+  const ActCommon& a = sa.c;
+  const dr_dims& d = a.d;
+  const int N = a.n_env;
+  const int Hd = d.hidden, D = d.obs_dim, F = 4 * d.enc_f2;
+  unsigned round = 0;
+  bool ok = true;
+  ACT_TS(a, 0);
+
+  // ---- stage 1: GRU pre-activations of the continuing rows  ||  encoder layer 0, y0 = W0 x + b0 ----
+  act_gru_pre<NE>(a, first, xs);
+  act_dense_batch<4, NE>(N, 0u, F, D, a.wm.conv[0].w, a.wm.conv[0].b, xs, sa.y0, F, [&](float* dst, int e) {
+    act_stage<2>(dst, D, [&](int i) { return sa.obs[(long long)e * D + i]; });
+  });
+  ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 1);
+  // ---- stage 2: GRU gates  ||  encoder layer 1, y1 = W1 SiLU(y0) + b1 ----
+  if (ok) {
+    act_gru_rows(a, first);
+    act_dense_batch<4, NE>(N, 0u, F, F, a.wm.conv[1].w, a.wm.conv[1].b, xs, sa.y1, F, [&](float* dst, int e) {
+      act_stage<1>(dst, F, [&](int i) { return act_silu(sa.y0[e * F + i]); });
+    });
+  }
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 2);
+  // ---- stage 3: latent_mapper.0 on cat(SiLU(y1), h') (VAE.py:73) ----
   if (ok)
-    act_dense_batch<26, NE>(N, 0u, d.actor_h1, Hd + L, a.ac.l0.w, a.ac.l0.b, xs, a.prea, d.actor_h1,
+    act_dense_batch<14, NE>(N, 0u, d.enc_hidden, F + Hd, a.wm.map0.w, a.wm.map0.b, xs, a.pre1, d.enc_hidden,
                             [&](float* dst, int e) {
-                              act_stage<7>(dst, Hd + L, [&](int i) {
-                                return i < Hd ? a.hn[e * Hd + i] : a.z_out[(long long)e * L + i - Hd];
+                              act_stage<4>(dst, F + Hd, [&](int i) {
+                                return i < F ? act_silu(sa.y1[e * F + i]) : a.hn[e * Hd + i - F];
                               });
                             });
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 7);
-  // Failure path as k_act_step: a timed-out barrier raises the status word and
-  // every failing workgroup writes NaN to all five outputs of every row after
-  // its own writes; the workgroups that run a tail re-read the shared flag.
-  if (blockIdx.x < N) {  // (uniform over the workgroup)
-    __shared__ int s_fail;
-    if (threadIdx.x == 0) s_fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_fail) ok = false;
-  }
-  if (!ok) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    const float qnan = __int_as_float(0x7fc00000);
-    for (int i = threadIdx.x; i < N * A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
-    for (int i = threadIdx.x; i < N * L; i += ACT_NT) a.z_out[i] = qnan;
-    for (int i = threadIdx.x; i < N * Hd; i += ACT_NT) a.h_out[i] = qnan;
-    return;
-  }
-  // ---- stage 8: row e's actor tail in workgroup e ----
-  if (blockIdx.x >= N) return;
-  const int e = blockIdx.x;
-  act_actor_tail(d, a.ac, a.prea + e * d.actor_h1, a.det, a.noise.eps ? a.noise.eps + e * A : nullptr, a.noise.rng,
-                 a.noise.stream + 1, a.noise.row0 + e, a.a_out + e * A, a.mu_out + e * A, a.sig_out + e * A, xs);
-  ACT_TS(a, 15);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 3);
+  // ---- stage 4: the sampler ----
+  if (ok) act_sample_rows(a, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 4);
+  // ---- stage 5: actor base_net.0 ----
+  if (ok) act_actor_l0<NE>(a, xs);
+  if (ok) ok = act_sync(a.bar, round, &sh.ok, a.spin_limit);
+  ACT_TS(a, 5);
+  // ---- stage 6: the failure path, or the actor tails ----
+  act_finish(a, ok, sh, xs);
+}
+
+// ---------------------------------------------------------------------------
+// Host side.
+
+static char* act_take(char* base, size_t& off, size_t bytes) {
+  const size_t o = (off + 255) & ~(size_t)255;
+  off = o + bytes;
+  return base ? base + o : nullptr;
+}
+
+// the shared part of a workspace (base NULL: sizes only); a kernel's encoder scratch follows it
+static void act_carve(char* base, const dr_dims* d, int n_env, ActCommon& c, size_t& off) {
+  const size_t n = (size_t)n_env;
+  c.ts = (long long*)act_take(base, off, 16 * sizeof(long long));  // first: tools read it at offset 0
+  c.bar = (unsigned*)act_take(base, off, ACT_BAR_BYTES);
+  c.fail = (int*)act_take(base, off, 256);
+  c.gi = (float*)act_take(base, off, 4 * n * 3 * d->hidden);
+  c.gh = (float*)act_take(base, off, 4 * n * 3 * d->hidden);
+  c.hn = (float*)act_take(base, off, 4 * n * d->hidden);
+  c.pre1 = (float*)act_take(base, off, 4 * n * d->enc_hidden);
+  c.prea = (float*)act_take(base, off, 4 * n * d->actor_h1);
 }
 
 static void act_batch_carve(char* base, const dr_dims* d, int n_env, ActBatchArgs& a, size_t& off) {
-  auto take = [&](size_t bytes) {
-    const size_t o = (off + 255) & ~(size_t)255;
-    off = o + bytes;
-    return base ? base + o : nullptr;
-  };
-  const size_t n = (size_t)n_env;
+  const size_t n = (size_t)n_env, p1 = (size_t)(d->img_h / 2) * (d->img_w / 2);
   const int c1 = d->enc_f1, c2 = d->enc_f2;
-  const size_t p1 = (size_t)(d->img_h / 2) * (d->img_w / 2);
-  a.ts = (long long*)take(16 * sizeof(long long));  // first, as in dr_act_step's workspace
-  a.bar = (unsigned*)take(ACT_BAR_BYTES);
-  a.fail = (int*)take(256);
-  a.c1 = (float*)take(4 * n * p1 * c1);
-  a.c2 = (float*)take(4 * n * (p1 / 4) * c2);
-  a.c3 = (float*)take(4 * n * (p1 / 16) * 2 * c2);
-  a.c4 = (float*)take(4 * n * (p1 / 64) * 4 * c2);
-  a.gi = (float*)take(4 * n * 3 * d->hidden);
-  a.gh = (float*)take(4 * n * 3 * d->hidden);
-  a.hn = (float*)take(4 * n * d->hidden);
-  a.pre1 = (float*)take(4 * n * d->enc_hidden);
-  a.prea = (float*)take(4 * n * d->actor_h1);
+  act_carve(base, d, n_env, a.c, off);
+  a.c1 = (float*)act_take(base, off, 4 * n * p1 * c1);
+  a.c2 = (float*)act_take(base, off, 4 * n * (p1 / 4) * c2);
+  a.c3 = (float*)act_take(base, off, 4 * n * (p1 / 16) * 2 * c2);
+  a.c4 = (float*)act_take(base, off, 4 * n * (p1 / 64) * 4 * c2);
+}
+
+static void act_vec_carve(char* base, const dr_dims* d, int n_env, ActVecArgs& a, size_t& off) {
+  const size_t n = (size_t)n_env, F = (size_t)4 * d->enc_f2;
+  act_carve(base, d, n_env, a.c, off);
+  a.y0 = (float*)act_take(base, off, 4 * n * F);
+  a.y1 = (float*)act_take(base, off, 4 * n * F);
+}
+
+// the entry points' arguments as the kernels take them (workspace pointers still zero)
+static ActCommon act_common(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int n_env,
+                            const unsigned char* first, unsigned first_mask, const float* z_prev, const float* h,
+                            const float* a_prev, dr_noise noise, int deterministic, float* z_out, float* h_out,
+                            float* a_out, float* mu_out, float* sigma_out, float* logits_out, int* status) {
+  // (ActCommon's members in order, up to status; the workspace members after it are zero)
+  return ActCommon{*d,    *wm,   *ac,   first, first_mask, n_env,     deterministic, z_prev,     h,
+                   a_prev, noise, z_out, h_out, a_out,      mu_out,    sigma_out,     logits_out, status};
+}
+
+// the stage helpers' register batches (KJ) and the LDS staging are sized for the
+// CarRacing encoder (Dreamer.py:20-64 config); other shapes use the unfused calls
+static bool act_dims_ok(const dr_dims* d) {
+  const int F = 4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = d->rows * d->cols;
+  return (d->enc_depth == 0 || d->enc_depth == 4) && d->img_h == 64 && d->img_w == 64 && d->enc_f1 == 32 &&
+         d->enc_f2 == 64 && F + d->hidden <= 64 * 74 && L + d->action <= 64 * 17 && d->hidden <= 64 * 10 &&
+         d->hidden + L <= 64 * 26 && d->cols <= 64 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden <= 256 &&
+         d->actor_h1 <= 256 && d->actor_h2 <= 1024 && d->action <= 64;
+}
+
+// act_dims_ok's bounds on the widths the shared stages are sized for (register batches KJ, the sampler's and the
+// actor tail's LDS areas), F within the latent_mapper.0 batch (F + hidden <= 64 * 14) and the observation cap; the
+// dense helpers loop over K, so obs_dim need not be a multiple of anything
+static bool act_vec_dims_ok(const dr_dims* d) {
+  const int F = 4 * d->enc_f2, L = d->rows * d->cols;
+  return d->obs_dim >= 1 && d->obs_dim <= DR_ACT_VEC_MAX_OBS && F >= 1 && F <= 256 && d->hidden >= 1 &&
+         L + d->action <= 64 * 17 && d->hidden <= 64 * 10 && d->hidden + L <= 64 * 26 && d->cols >= 1 &&
+         d->cols <= 64 && d->rows >= 1 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden >= 1 &&
+         d->enc_hidden <= 256 && d->actor_h1 >= 1 && d->actor_h1 <= 256 && d->actor_h2 >= 1 && d->actor_h2 <= 1024 &&
+         d->action >= 1 && d->action <= 64;
+}
+
+// rows a wave accumulates at once (the instantiation): the batch rounded up to a power of two, at most 8
+static int act_batch_ne(int n_env) { return n_env <= 1 ? 1 : n_env <= 2 ? 2 : n_env <= 4 ? 4 : 8; }
+
+// rows of a dense stage's input that are in LDS at once
+static size_t act_chunk(int n_env, int nout) {
+  const int ne = act_batch_ne(n_env), nsp = act_dense_splits(nout), per = (n_env + nsp - 1) / nsp;
+  return (size_t)(per < ne ? per : ne);
+}
+
+// floats of dynamic LDS: the conv slab, or the widest dense stage's chunk of input rows
+static size_t act_batch_lds(const dr_dims* d, int n_env) {
+  const size_t F = (size_t)4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = (size_t)d->rows * d->cols;
+  size_t n = ACT_BATCH_CONV_LDS;
+  auto need = [&](size_t v) { n = v > n ? v : n; };
+  need(act_chunk(n_env, 3 * d->hidden) * (L + d->action));
+  need(act_chunk(n_env, 3 * d->hidden) * d->hidden);
+  need(act_chunk(n_env, d->enc_hidden) * (F + d->hidden));
+  need(act_chunk(n_env, d->actor_h1) * (d->hidden + L));
+  return n;
+}
+// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_dims_ok admits
+#define ACT_BATCH_LDS_MAX (8 * 64 * 74 * 4)
+
+// floats of dynamic LDS: the widest dense stage's chunk of input rows, and at least what the sampler (1280) and the
+// actor tail (3072 + 2 A) use
+static size_t act_vec_lds(const dr_dims* d, int n_env) {
+  const size_t F = (size_t)4 * d->enc_f2, L = (size_t)d->rows * d->cols;
+  size_t n = 3072 + 2 * (size_t)d->action;
+  auto need = [&](size_t v) { n = v > n ? v : n; };
+  need(act_chunk(n_env, 3 * d->hidden) * (L + d->action));
+  need(act_chunk(n_env, 3 * d->hidden) * d->hidden);
+  need(act_chunk(n_env, (int)F) * d->obs_dim);
+  need(act_chunk(n_env, (int)F) * F);
+  need(act_chunk(n_env, d->enc_hidden) * (F + d->hidden));
+  need(act_chunk(n_env, d->actor_h1) * (d->hidden + L));
+  return n;
+}
+// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_vec_dims_ok admits
+#define ACT_VEC_LDS_MAX (8 * 64 * 26 * 4)
+static_assert(DR_ACT_VEC_MAX_OBS <= 64 * 26 && 3072 + 2 * 64 <= 8 * 64 * 26, "LDS bound covers every stage");
+
+// A kernel family as act_launch needs it.
+struct ActFamily {
+  const void* fn[4];                           // the NE = 1, 2, 4, 8 instantiations
+  size_t lds_max;                              // dynamic LDS an instantiation may be launched with
+  int resident_ok[DR_ACT_MAX_ENVS + 1][64];    // per (n_env, device): 0 unknown, 1 ok, -1 too small
+};
+
+// Zeroes the barrier lines, checks co-residency and launches the instantiation
+// for c.n_env rows with `lds` bytes of dynamic LDS.  name: the entry point,
+// for messages; c: the ActCommon inside *args (the kernel's argument struct).
+//
+// A plain launch whose grid barrier needs all ACT_NB workgroups resident at
+// once.  The cooperative launch would add exactly that check at +15-19 us of
+// host time per env step (MI355X_MICROARCH.md coop-launch), so it is made once
+// per batch size and device here instead, with the dynamic LDS that n_env
+// launches (up to 147 KiB: one workgroup per CU): the occupancy API's blocks
+// per CU (one lower than reported, the guide's sgpr-count margin) times the CU
+// count must cover the grid, else the call fails and the caller runs the
+// unfused path.  What no launch-time check can cover -- other work holding CUs
+// for longer than the bounded spin -- comes back through `status` (and NaN
+// outputs).
+static int act_launch(const char* name, ActFamily& fam, size_t lds, ActCommon& c, void* args, hipStream_t s) {
+  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
+  const bool force_timeout = force && strcmp(force, "timeout") == 0;
+  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
+  // barrier lines + fail flag (a kernel, so a captured graph re-arms them too)
+  static_assert((ACT_BAR_BYTES + 512) % 4 == 0, "barrier bytes");
+  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(c.bar), 0.f, s));
+  const int ne = act_batch_ne(c.n_env);
+  const void* fn = fam.fn[ne == 1 ? 0 : ne == 2 ? 1 : ne == 4 ? 2 : 3];
+  if (lds > fam.lds_max) {
+    dr_set_error("%s: stage input beyond the LDS budget", name);
+    return DR_E_INVALID;
+  }
+  int dev = 0;
+  DR_TRY_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) {
+    dr_set_error("%s: device index", name);
+    return DR_E_INVALID;
+  }
+  int& resident = fam.resident_ok[c.n_env][dev];  // (idempotent, benign race)
+  if (resident == 0) {
+    DR_TRY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fam.lds_max));
+    int per_cu = 0, cus = 0;
+    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ACT_NT, lds));
+    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    resident = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
+  }
+  if (resident != 1 || force_nonres) {
+    dr_set_error("%s: the device cannot hold the acting grid co-resident", name);
+    return DR_E_UNSUPPORTED;
+  }
+  c.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
+  void* kargs[] = {args};
+  DR_TRY_HIP(hipLaunchKernel(fn, dim3(ACT_NB), dim3(ACT_NT), kargs, lds, s));
+  return dr_check_launch(name + 3);  // (without the dr_)
+}
+
+// dr_act_step and dr_act_batch past their argument checks: c.n_env frames through k_act_batch
+static int act_batch_run(const char* name, const ActCommon& c, const unsigned char* frames, void* ws, size_t ws_bytes,
+                         hipStream_t s) {
+  static ActFamily fam = {{(const void*)k_act_batch<1>, (const void*)k_act_batch<2>, (const void*)k_act_batch<4>,
+                           (const void*)k_act_batch<8>},
+                          ACT_BATCH_LDS_MAX};
+  ActBatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.c = c;
+  a.frames = frames;
+  size_t off = 0;
+  act_batch_carve((char*)ws, &c.d, c.n_env, a, off);
+  if (off > ws_bytes) {
+    dr_set_error("%s: workspace too small", name);
+    return DR_E_INVALID;
+  }
+  return act_launch(name, fam, act_batch_lds(&c.d, c.n_env) * 4, a.c, &a, s);
 }
 
 extern "C" size_t dr_act_batch_workspace_bytes(const dr_dims* d, int n_env) {
@@ -1011,27 +990,27 @@ extern "C" size_t dr_act_batch_workspace_bytes(const dr_dims* d, int n_env) {
   return off;
 }
 
-// rows a wave accumulates at once (the instantiation): the batch rounded up to a power of two, at most 8
-static int act_batch_ne(int n_env) { return n_env <= 1 ? 1 : n_env <= 2 ? 2 : n_env <= 4 ? 4 : 8; }
+extern "C" size_t dr_act_step_workspace_bytes(const dr_dims* d) { return dr_act_batch_workspace_bytes(d, 1); }
 
-// floats of dynamic LDS: the conv slab, or the widest dense stage's chunk of input rows
-static size_t act_batch_lds(const dr_dims* d, int n_env) {
-  const int ne = act_batch_ne(n_env);
-  const size_t F = (size_t)4 * d->enc_f2 * (d->img_h / 16) * (d->img_w / 16), L = (size_t)d->rows * d->cols;
-  auto chunk = [&](int nout) {
-    const int nsp = act_dense_splits(nout), per = (n_env + nsp - 1) / nsp;
-    return (size_t)(per < ne ? per : ne);
-  };
-  size_t n = ACT_BATCH_CONV_LDS;
-  auto need = [&](size_t v) { n = v > n ? v : n; };
-  need(chunk(3 * d->hidden) * (L + d->action));
-  need(chunk(3 * d->hidden) * d->hidden);
-  need(chunk(d->enc_hidden) * (F + d->hidden));
-  need(chunk(d->actor_h1) * (d->hidden + L));
-  return n;
+// the one-row call of k_act_batch<1>: has_prev is the row's first flag, on the host
+extern "C" int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, const unsigned char* frame,
+                           int has_prev, const float* z_prev, const float* h, const float* a_prev, dr_noise noise,
+                           int deterministic, float* z_out, float* h_out, float* a_out, float* mu_out,
+                           float* sigma_out, float* logits_out, int* status, void* ws, size_t ws_bytes,
+                           hipStream_t s) {
+  DR_REQUIRE(d && wm && ac && frame && h && z_out && h_out && a_out && mu_out && sigma_out && ws, "null argument");
+  DR_REQUIRE(!has_prev || (z_prev && a_prev), "has_prev needs z_prev and a_prev");
+  DR_REQUIRE(d->obs_dim == 0, "dr_act_step: pixel observations only (vector observations use dr_act_vec)");
+  if (!act_dims_ok(d)) {
+    dr_set_error("dr_act_step: dims outside the acting kernel (64x64 frames, encoder 32/64 filters, widths <= the "
+                 "staging)");
+    return DR_E_UNSUPPORTED;
+  }
+  return act_batch_run("dr_act_step",
+                       act_common(d, wm, ac, 1, nullptr, has_prev ? 0u : 1u, z_prev, h, a_prev, noise, deterministic,
+                                  z_out, h_out, a_out, mu_out, sigma_out, logits_out, status),
+                       frame, ws, ws_bytes, s);
 }
-// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_dims_ok admits
-#define ACT_BATCH_LDS_MAX (8 * 64 * 74 * 4)
 
 extern "C" int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int n_env,
                             const unsigned char* frames, const unsigned char* first, const float* z_prev,
@@ -1051,240 +1030,10 @@ extern "C" int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr
                  "filters, widths <= the staging)");
     return DR_E_UNSUPPORTED;
   }
-  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
-  const bool force_timeout = force && strcmp(force, "timeout") == 0;
-  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
-  ActBatchArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d = *d;
-  a.wm = *wm;
-  a.ac = *ac;
-  a.frames = frames;
-  a.first = first;
-  a.n_env = n_env;
-  a.det = deterministic;
-  a.z_prev = z_prev;
-  a.h = h;
-  a.a_prev = a_prev;
-  a.noise = noise;
-  a.z_out = z_out;
-  a.h_out = h_out;
-  a.a_out = a_out;
-  a.mu_out = mu_out;
-  a.sig_out = sigma_out;
-  a.logits_out = logits_out;
-  a.status = status;
-  size_t off = 0;
-  act_batch_carve((char*)ws, d, n_env, a, off);
-  DR_REQUIRE(off <= ws_bytes, "workspace too small");
-  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(a.bar), 0.f, s));
-  const int ne = act_batch_ne(n_env);
-  const void* fn = ne == 1   ? (const void*)k_act_batch<1>
-                   : ne == 2 ? (const void*)k_act_batch<2>
-                   : ne == 4 ? (const void*)k_act_batch<4>
-                             : (const void*)k_act_batch<8>;
-  const size_t lds = act_batch_lds(d, n_env) * 4;
-  DR_REQUIRE(lds <= ACT_BATCH_LDS_MAX, "stage input beyond the LDS budget");
-  // co-residency as dr_act_step, per batch size: the occupancy query is made
-  // with the dynamic LDS this n_env launches (up to 147 KiB: one workgroup per CU)
-  static int resident_ok[DR_ACT_MAX_ENVS + 1][64];  // 0 unknown, 1 ok, -1 too small (idempotent, benign race)
-  int dev = 0;
-  DR_TRY_HIP(hipGetDevice(&dev));
-  DR_REQUIRE(dev >= 0 && dev < 64, "device index");
-  if (resident_ok[n_env][dev] == 0) {
-    DR_TRY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ACT_BATCH_LDS_MAX));
-    int per_cu = 0, cus = 0;
-    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ACT_NT, lds));
-    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    resident_ok[n_env][dev] = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
-  }
-  if (resident_ok[n_env][dev] != 1 || force_nonres) {
-    dr_set_error("dr_act_batch: the device cannot hold the acting grid co-resident");
-    return DR_E_UNSUPPORTED;
-  }
-  a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
-  switch (ne) {
-    case 1: hipLaunchKernelGGL(k_act_batch<1>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(k_act_batch<2>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    case 4: hipLaunchKernelGGL(k_act_batch<4>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    default: hipLaunchKernelGGL(k_act_batch<8>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-  }
-  return dr_check_launch("act_batch");
-}
-
-// ---------------------------------------------------------------------------
-// Acting on vector observations (dr_dims.obs_dim = D > 0, BASELINE configs[4])
-// in one launch, for n_env = 1 ... DR_ACT_MAX_ENVS rows.  The encoder's four
-// conv stages are two small dense layers (conv[0] = Linear(D, F) + SiLU,
-// conv[1] = Linear(F, F) + SiLU, F = 4 * enc_f2), which overlap
-// the two GRU stages, so the step takes five barrier rounds instead of eight.
-// Every dense stage is act_dense_batch (per row the one-row summation order: k
-// = lane + 64 j, j ascending, then wave_sum), so a row's outputs are the same
-// bits for every n_env, row position and mix of first flags; n_env = 1 is the
-// batch-1 step (no separate kernel).  A layer's SiLU is applied where the next
-// stage stages its input into LDS.  Same grid, barrier, sampler, actor tail and
-// failure path as k_act_batch.
-struct alignas(16) ActVecArgs {
-  dr_dims d;
-  dr_world_model wm;
-  dr_actor ac;
-  const float* obs;            // [n_env][obs_dim] f32
-  const unsigned char* first;  // [n_env]: 1 = episode start (h' = 0)
-  int n_env, det;
-  const float *z_prev, *h, *a_prev;  // [n_env][L], [n_env][hidden], [n_env][A]
-  dr_noise noise;
-  float *z_out, *h_out, *a_out, *mu_out, *sig_out, *logits_out;
-  int* status;
-  // workspace (y0 ... prea: one copy per row)
-  unsigned* bar;
-  float *y0, *y1, *gi, *gh, *hn, *pre1, *prea;  // y0, y1: the encoder layers' pre-activations [F]
-  int* fail;
-  int spin_limit;
-  long long* ts;
-};
-
-__device__ __forceinline__ float act_silu(float v) { return v / (1.0f + expf(-v)); }
-
-template <int NE>
-__global__ __launch_bounds__(ACT_NT) void k_act_vec(ActVecArgs ga) {
-  __shared__ ActVecArgs a;
-  __shared__ int s_ok;
-  __shared__ unsigned s_first;  // bit e: row e starts an episode
-  extern __shared__ __attribute__((aligned(16))) float xs[];
-  static_assert(sizeof(ActVecArgs) / 16 <= ACT_NT, "argument copy");
-  if (threadIdx.x < sizeof(ActVecArgs) / 16)
-    reinterpret_cast<int4*>(&a)[threadIdx.x] = reinterpret_cast<const int4*>(&ga)[threadIdx.x];
-  if (threadIdx.x == 0) {
-    unsigned m = 0;
-    for (int e = 0; e < ga.n_env; ++e)
-      if (ga.first[e]) m |= 1u << e;
-    s_first = m;
-  }
-  __syncthreads();
-  const dr_dims& d = a.d;
-  const int N = a.n_env;
-  const unsigned first = s_first;
-  const int gw = blockIdx.x * (ACT_NT / 64) + (threadIdx.x >> 6);
-  const int Hd = d.hidden, R = d.rows, C = d.cols, L = R * C, A = d.action;
-  const int D = d.obs_dim, F = 4 * d.enc_f2;
-  unsigned round = 0;
-  bool ok = true;
-  ACT_TS(a, 0);
-
-  // ---- stage 1: GRU pre-activations of the continuing rows  ||  encoder layer 0, y0 = W0 x + b0 ----
-  act_dense_batch<17, NE>(N, first, 3 * Hd, L + A, a.wm.w_ih, a.wm.b_ih, xs, a.gi, 3 * Hd, [&](float* dst, int e) {
-    act_stage<5>(dst, L + A, [&](int i) { return i < L ? a.z_prev[(long long)e * L + i] : a.a_prev[e * A + i - L]; });
-  });
-  act_dense_batch<10, NE>(N, first, 3 * Hd, Hd, a.wm.w_hh, a.wm.b_hh, xs, a.gh, 3 * Hd, [&](float* dst, int e) {
-    act_stage<3>(dst, Hd, [&](int i) { return a.h[e * Hd + i]; });
-  });
-  act_dense_batch<4, NE>(N, 0u, F, D, a.wm.conv[0].w, a.wm.conv[0].b, xs, a.y0, F, [&](float* dst, int e) {
-    act_stage<2>(dst, D, [&](int i) { return a.obs[(long long)e * D + i]; });
-  });
-  ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 1);
-  // ---- stage 2: GRU gates; h' = 0 at an episode start  ||  encoder layer 1, y1 = W1 SiLU(y0) + b1 ----
-  if (ok) {
-    const int gt = blockIdx.x * ACT_NT + threadIdx.x;
-    for (int i = gt; i < N * Hd; i += ACT_NB * ACT_NT) {
-      const int e = i / Hd, j = i - e * Hd;
-      const float hn = ((first >> e) & 1u) ? 0.f : act_gru_gates(a.gi + e * 3 * Hd, a.gh + e * 3 * Hd, Hd, j, a.h[i]);
-      a.hn[i] = hn;
-      a.h_out[i] = hn;
-    }
-    act_dense_batch<4, NE>(N, 0u, F, F, a.wm.conv[1].w, a.wm.conv[1].b, xs, a.y1, F, [&](float* dst, int e) {
-      act_stage<1>(dst, F, [&](int i) { return act_silu(a.y0[e * F + i]); });
-    });
-  }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 2);
-  // ---- stage 3: latent_mapper.0 on cat(SiLU(y1), h') (VAE.py:73) ----
-  if (ok)
-    act_dense_batch<14, NE>(N, 0u, d.enc_hidden, F + Hd, a.wm.map0.w, a.wm.map0.b, xs, a.pre1, d.enc_hidden,
-                            [&](float* dst, int e) {
-                              act_stage<4>(dst, F + Hd, [&](int i) {
-                                return i < F ? act_silu(a.y1[e * F + i]) : a.hn[e * Hd + i - F];
-                              });
-                            });
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 3);
-  // ---- stage 4: LN-SiLU, latent_mapper.3 and the categorical sampler: one wave per (row, latent group) ----
-  if (ok)
-    for (int t = gw; t < N * R; t += ACT_NW) {
-      const int e = t / R, grp = t - e * R;
-      act_latent_group(d, a.wm, a.pre1 + e * d.enc_hidden, grp, a.noise.q ? a.noise.q + (long long)e * L : nullptr,
-                       a.noise.rng, a.noise.stream, a.noise.row0 + e, a.z_out + (long long)e * L,
-                       a.logits_out ? a.logits_out + (long long)e * L : nullptr, xs);
-    }
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 4);
-  // ---- stage 5: actor base_net.0 on cat(h', z') (Agent.py:191-200) ----
-  if (ok)
-    act_dense_batch<26, NE>(N, 0u, d.actor_h1, Hd + L, a.ac.l0.w, a.ac.l0.b, xs, a.prea, d.actor_h1,
-                            [&](float* dst, int e) {
-                              act_stage<7>(dst, Hd + L, [&](int i) {
-                                return i < Hd ? a.hn[e * Hd + i] : a.z_out[(long long)e * L + i - Hd];
-                              });
-                            });
-  if (ok) ok = act_sync(a.bar, round, &s_ok, a.spin_limit);
-  ACT_TS(a, 5);
-  // Failure path as k_act_batch: a timed-out barrier raises the status word and
-  // every failing workgroup writes NaN to all five outputs of every row after
-  // its own writes; the workgroups that run a tail re-read the shared flag.
-  if (blockIdx.x < N) {  // (uniform over the workgroup)
-    __shared__ int s_fail;
-    if (threadIdx.x == 0) s_fail = __hip_atomic_load(a.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_fail) ok = false;
-  }
-  if (!ok) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.status) __hip_atomic_store(a.status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    const float qnan = __int_as_float(0x7fc00000);
-    for (int i = threadIdx.x; i < N * A; i += ACT_NT) a.a_out[i] = a.mu_out[i] = a.sig_out[i] = qnan;
-    for (int i = threadIdx.x; i < N * L; i += ACT_NT) a.z_out[i] = qnan;
-    for (int i = threadIdx.x; i < N * Hd; i += ACT_NT) a.h_out[i] = qnan;
-    return;
-  }
-  // ---- stage 6: row e's actor tail in workgroup e ----
-  if (blockIdx.x >= N) return;
-  const int e = blockIdx.x;
-  act_actor_tail(d, a.ac, a.prea + e * d.actor_h1, a.det, a.noise.eps ? a.noise.eps + e * A : nullptr, a.noise.rng,
-                 a.noise.stream + 1, a.noise.row0 + e, a.a_out + e * A, a.mu_out + e * A, a.sig_out + e * A, xs);
-  ACT_TS(a, 15);
-}
-
-static void act_vec_carve(char* base, const dr_dims* d, int n_env, ActVecArgs& a, size_t& off) {
-  auto take = [&](size_t bytes) {
-    const size_t o = (off + 255) & ~(size_t)255;
-    off = o + bytes;
-    return base ? base + o : nullptr;
-  };
-  const size_t n = (size_t)n_env, F = (size_t)4 * d->enc_f2;
-  a.ts = (long long*)take(16 * sizeof(long long));  // first, as in dr_act_step's workspace
-  a.bar = (unsigned*)take(ACT_BAR_BYTES);
-  a.fail = (int*)take(256);
-  a.y0 = (float*)take(4 * n * F);
-  a.y1 = (float*)take(4 * n * F);
-  a.gi = (float*)take(4 * n * 3 * d->hidden);
-  a.gh = (float*)take(4 * n * 3 * d->hidden);
-  a.hn = (float*)take(4 * n * d->hidden);
-  a.pre1 = (float*)take(4 * n * d->enc_hidden);
-  a.prea = (float*)take(4 * n * d->actor_h1);
-}
-
-// act_dims_ok's bounds on the widths the shared stages are sized for (register batches KJ, the sampler's and the
-// actor tail's LDS areas), F within the latent_mapper.0 batch (F + hidden <= 64 * 14) and the observation cap; the
-// dense helpers loop over K, so obs_dim need not be a multiple of anything
-static bool act_vec_dims_ok(const dr_dims* d) {
-  const int F = 4 * d->enc_f2, L = d->rows * d->cols;
-  return d->obs_dim >= 1 && d->obs_dim <= DR_ACT_VEC_MAX_OBS && F >= 1 && F <= 256 && d->hidden >= 1 &&
-         L + d->action <= 64 * 17 && d->hidden <= 64 * 10 && d->hidden + L <= 64 * 26 && d->cols >= 1 &&
-         d->cols <= 64 && d->rows >= 1 && d->rows <= ACT_NB * (ACT_NT / 64) && d->enc_hidden >= 1 &&
-         d->enc_hidden <= 256 && d->actor_h1 >= 1 && d->actor_h1 <= 256 && d->actor_h2 >= 1 && d->actor_h2 <= 1024 &&
-         d->action >= 1 && d->action <= 64;
+  return act_batch_run("dr_act_batch",
+                       act_common(d, wm, ac, n_env, first, 0u, z_prev, h, a_prev, noise, deterministic, z_out, h_out,
+                                  a_out, mu_out, sigma_out, logits_out, status),
+                       frames, ws, ws_bytes, s);
 }
 
 extern "C" size_t dr_act_vec_workspace_bytes(const dr_dims* d, int n_env) {
@@ -1294,29 +1043,6 @@ extern "C" size_t dr_act_vec_workspace_bytes(const dr_dims* d, int n_env) {
   act_vec_carve(nullptr, d, n_env, a, off);
   return off;
 }
-
-// floats of dynamic LDS: the widest dense stage's chunk of input rows, and at least what the sampler (1280) and the
-// actor tail (3072 + 2 A) use
-static size_t act_vec_lds(const dr_dims* d, int n_env) {
-  const int ne = act_batch_ne(n_env);
-  const size_t F = (size_t)4 * d->enc_f2, L = (size_t)d->rows * d->cols;
-  auto chunk = [&](int nout) {
-    const int nsp = act_dense_splits(nout), per = (n_env + nsp - 1) / nsp;
-    return (size_t)(per < ne ? per : ne);
-  };
-  size_t n = 3072 + 2 * (size_t)d->action;
-  auto need = [&](size_t v) { n = v > n ? v : n; };
-  need(chunk(3 * d->hidden) * (L + d->action));
-  need(chunk(3 * d->hidden) * d->hidden);
-  need(chunk((int)F) * d->obs_dim);
-  need(chunk((int)F) * F);
-  need(chunk(d->enc_hidden) * (F + d->hidden));
-  need(chunk(d->actor_h1) * (d->hidden + L));
-  return n;
-}
-// what an instantiation may be launched with (set once): 8 rows of the widest stage input act_vec_dims_ok admits
-#define ACT_VEC_LDS_MAX (8 * 64 * 26 * 4)
-static_assert(DR_ACT_VEC_MAX_OBS <= 64 * 26 && 3072 + 2 * 64 <= 8 * 64 * 26, "LDS bound covers every stage");
 
 extern "C" int dr_act_vec(const dr_dims* d, const dr_world_model* wm, const dr_actor* ac, int n_env, const float* obs,
                           const unsigned char* first, const float* z_prev, const float* h, const float* a_prev,
@@ -1337,62 +1063,16 @@ extern "C" int dr_act_vec(const dr_dims* d, const dr_world_model* wm, const dr_a
                  "<= the staging)");
     return DR_E_UNSUPPORTED;
   }
-  const char* force = getenv("DREAMER_ACT_FORCE");  // test hook (include/dreamer_hip.h)
-  const bool force_timeout = force && strcmp(force, "timeout") == 0;
-  const bool force_nonres = force && strcmp(force, "nonresident") == 0;
+  static ActFamily fam = {{(const void*)k_act_vec<1>, (const void*)k_act_vec<2>, (const void*)k_act_vec<4>,
+                           (const void*)k_act_vec<8>},
+                          ACT_VEC_LDS_MAX};
   ActVecArgs a;
   memset(&a, 0, sizeof(a));
-  a.d = *d;
-  a.wm = *wm;
-  a.ac = *ac;
+  a.c = act_common(d, wm, ac, n_env, first, 0u, z_prev, h, a_prev, noise, deterministic, z_out, h_out, a_out, mu_out,
+                   sigma_out, logits_out, status);
   a.obs = obs;
-  a.first = first;
-  a.n_env = n_env;
-  a.det = deterministic;
-  a.z_prev = z_prev;
-  a.h = h;
-  a.a_prev = a_prev;
-  a.noise = noise;
-  a.z_out = z_out;
-  a.h_out = h_out;
-  a.a_out = a_out;
-  a.mu_out = mu_out;
-  a.sig_out = sigma_out;
-  a.logits_out = logits_out;
-  a.status = status;
   size_t off = 0;
   act_vec_carve((char*)ws, d, n_env, a, off);
   DR_REQUIRE(off <= ws_bytes, "workspace too small");
-  DR_TRY(op_fill((ACT_BAR_BYTES + 512) / 4, reinterpret_cast<float*>(a.bar), 0.f, s));
-  const int ne = act_batch_ne(n_env);
-  const void* fn = ne == 1   ? (const void*)k_act_vec<1>
-                   : ne == 2 ? (const void*)k_act_vec<2>
-                   : ne == 4 ? (const void*)k_act_vec<4>
-                             : (const void*)k_act_vec<8>;
-  const size_t lds = act_vec_lds(d, n_env) * 4;
-  DR_REQUIRE(lds <= ACT_VEC_LDS_MAX, "stage input beyond the LDS budget");
-  // co-residency as dr_act_batch: per batch size, with the dynamic LDS this n_env launches
-  static int resident_ok[DR_ACT_MAX_ENVS + 1][64];  // 0 unknown, 1 ok, -1 too small (idempotent, benign race)
-  int dev = 0;
-  DR_TRY_HIP(hipGetDevice(&dev));
-  DR_REQUIRE(dev >= 0 && dev < 64, "device index");
-  if (resident_ok[n_env][dev] == 0) {
-    DR_TRY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ACT_VEC_LDS_MAX));
-    int per_cu = 0, cus = 0;
-    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, ACT_NT, lds));
-    DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    resident_ok[n_env][dev] = (long long)(per_cu - 1 > 0 ? per_cu - 1 : per_cu) * cus >= ACT_NB ? 1 : -1;
-  }
-  if (resident_ok[n_env][dev] != 1 || force_nonres) {
-    dr_set_error("dr_act_vec: the device cannot hold the acting grid co-resident");
-    return DR_E_UNSUPPORTED;
-  }
-  a.spin_limit = force_timeout ? 0 : ACT_SPIN_LIMIT;
-  switch (ne) {
-    case 1: hipLaunchKernelGGL(k_act_vec<1>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(k_act_vec<2>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    case 4: hipLaunchKernelGGL(k_act_vec<4>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-    default: hipLaunchKernelGGL(k_act_vec<8>, dim3(ACT_NB), dim3(ACT_NT), lds, s, a); break;
-  }
-  return dr_check_launch("act_vec");
+  return act_launch("dr_act_vec", fam, act_vec_lds(d, n_env) * 4, a.c, &a, s);
 }

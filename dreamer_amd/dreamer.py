@@ -464,44 +464,70 @@ class Dreamer(nn.Module):
                 if out is not None:
                     return out
             return self._act_step_unfused(observation, z, h, a, deterministic)
-        if getattr(self, "_act_unfused", False):
-            return self._act_step_unfused(observation, z, h, a, deterministic)
+        if not getattr(self, "_act_unfused", False):
+            out = self._act_fused("dr_act_step", self.__dict__, "_act_bufs", {},
+                                  np.asarray(observation, dtype=np.uint8).reshape(-1), np.full(1, z is None),
+                                  None if z is None else (z, h, a), deterministic)
+            if out is not None:
+                return out
+            # the device cannot hold the one-launch grid, or the widths are not the ones the
+            # kernel's register batches are sized for (e.g. the 5-layer VAE): the unfused launches
+            self._act_unfused = True
+        return self._act_step_unfused(observation, z, h, a, deterministic)
+
+    def _act_fused(self, entry, bufs, key, tag, payload, first, state, deterministic):
+        """The launch path of the three one-launch entry points: dr_act_step
+        (act_step), dr_act_batch (act_step_batch) and dr_act_vec (_act_vec).
+        payload: the N observations as bytes (u8 frames or f32 vectors); first:
+        bool [N]; state: the previous (z, h, a), or None where every row is
+        first.  bufs[key]: the entry point's buffers at this N (pinned and
+        device staging of payload + first flags, zero state, status word,
+        workspace), made on first use; tag: the keys _act_sync names the entry
+        point by.  Returns (a', mu, sigma, z', h') shaped (N, 1, ...), or None
+        where the entry point answered DR_E_UNSUPPORTED: the caller sets its
+        fallback flag and runs the unfused launches."""
+        dev = self.device
+        N, nb = first.shape[0], payload.size
         d = self.world_model.dims(self.agent)
         self.agent._ensure_flat()
         R, C = self.latent_state_dims
         A, Hd = self.action_dims, self.hidden_state_dims
-        st = getattr(self, "_act_bufs", None)
+        st = bufs.get(key)
         if st is None:
-            H_, W_ = self.observation_dims
-            st = self._act_bufs = dict(
-                pin=torch.empty(H_, W_, 3, dtype=torch.uint8).pin_memory(),
-                frame=torch.empty(H_, W_, 3, dtype=torch.uint8, device=dev),
-                h0=torch.zeros(Hd, device=dev),
+            ws = L.query(entry + "_workspace_bytes", d, *(() if entry == "dr_act_step" else (N,)))
+            st = bufs[key] = dict(
+                tag, nb=nb,
+                pin=torch.empty(nb + N, dtype=torch.uint8).pin_memory(),  # the observations, then the first flags
+                dev=torch.empty(nb + N, dtype=torch.uint8, device=dev),
+                z0=torch.zeros(N, R * C, device=dev), h0=torch.zeros(N, Hd, device=dev),
+                a0=torch.zeros(N, A, device=dev),
                 status=torch.zeros(1, dtype=torch.int32, device=dev),
                 status_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                ws=torch.empty(L.query("dr_act_step_workspace_bytes", d), dtype=torch.uint8, device=dev))
+                ws=torch.empty(ws, dtype=torch.uint8, device=dev))
         self._act_sync()  # the previous step's copy out of the pinned staging buffer has run (and it was ok)
-        st["pin"].numpy()[...] = observation
-        st["frame"].copy_(st["pin"], non_blocking=True)
-        has_prev = z is not None
-        zp = z.reshape(-1).float().contiguous() if has_prev else None
-        hp = h.reshape(-1).float().contiguous() if has_prev else st["h0"]
-        ap = a.reshape(-1).float().contiguous() if has_prev else None
-        z2 = torch.empty(1, 1, R, C, device=dev)
-        h2 = torch.empty(1, 1, Hd, device=dev)
-        a2, mu, sg = (torch.empty(1, 1, A, device=dev) for _ in range(3))
+        nb = st["nb"]  # (an observation of another size than the buffers were made for raises here)
+        pin = st["pin"].numpy()
+        pin[:nb] = payload
+        pin[nb:] = first
+        st["dev"].copy_(st["pin"], non_blocking=True)
+        if state is None:
+            zp, hp, ap = st["z0"], st["h0"], st["a0"]
+        else:
+            zp, hp, ap = (t.reshape(N, -1).float().contiguous() for t in state)
+        z2 = torch.empty(N, 1, R, C, device=dev)
+        h2 = torch.empty(N, 1, Hd, device=dev)
+        a2, mu, sg = (torch.empty(N, 1, A, device=dev) for _ in range(3))
+        obs = L.ptr(st["dev"])
+        # dr_act_step takes its row's flag on the host (has_prev); the others read the flags behind the observations
+        rows = (obs, int(not first[0])) if entry == "dr_act_step" else (N, obs, obs + nb)
         try:
-            L.call("dr_act_step", d, self.world_model.packed(), self.agent.actor_struct(), L.ptr(st["frame"]),
-                   int(has_prev), L.ptr(zp), L.ptr(hp), L.ptr(ap), hip.adhoc(dev).noise(), int(deterministic),
-                   L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu), L.ptr(sg), None, L.ptr(st["status"]),
-                   L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
+            L.call(entry, d, self.world_model.packed(), self.agent.actor_struct(), *rows, L.ptr(zp), L.ptr(hp),
+                   L.ptr(ap), hip.adhoc(dev).noise(), int(deterministic), L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu),
+                   L.ptr(sg), None, L.ptr(st["status"]), L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
         except L.HipError as e:
             if e.code != L.DR_E_UNSUPPORTED:
                 raise
-            # the device cannot hold the one-launch grid, or the widths are not the ones the
-            # kernel's register batches are sized for (e.g. the 5-layer VAE): the unfused launches
-            self._act_unfused = True
-            return self._act_step_unfused(observation, z, h, a, deterministic)
+            return None
         # the status word travels back with the step (4 bytes behind the kernel);
         # _act_sync / act_check raise on a timed-out grid barrier
         st["status_host"].copy_(st["status"], non_blocking=True)
@@ -521,11 +547,13 @@ class Dreamer(nn.Module):
     # those where it beat both the batched unfused launches and N sequential
     # act_step calls by more than the run-to-run spread
     # (profiles/act_batch_timing.txt): measured at N =
-    # 1, 2, 4 and 8; at N = 16 the unfused launches are faster, and 9 ... 15
-    # were not measured, so they go with 16.  At the other sizes the faster of
-    # the other two runs (ACT_BATCH_SEQUENTIAL_N: the sizes where that is the
-    # sequential one -- none: the unfused launches cost about the same at
-    # every N, below two act_step calls).
+    # 1, 2, 4 and 8 (at N = 1 act_step is one launch of the same kernel, so
+    # only the unfused launches are a contender there); at N = 16 the unfused
+    # launches are faster, and 9 ... 15 were not measured, so they go with 16.
+    # At the other sizes the faster of the other two runs
+    # (ACT_BATCH_SEQUENTIAL_N: the sizes where that is the sequential one --
+    # none: the unfused launches cost about the same at every N, below three
+    # act_step calls, and the sizes not fused are above 8).
     ACT_BATCH_FUSED_N = frozenset(range(1, 9))
     ACT_BATCH_SEQUENTIAL_N = frozenset()
     # None: dispatch by the table; "fused" / "unfused" / "sequential": that path (tests, timing)
@@ -592,53 +620,14 @@ class Dreamer(nn.Module):
             return self._act_step_batch_unfused(observations, state, first, deterministic)
         if route == "sequential":
             return self._act_step_batch_sequential(observations, state, first, deterministic)
-        d = self.world_model.dims(self.agent)
-        self.agent._ensure_flat()
-        R, C = self.latent_state_dims
-        A, Hd = self.action_dims, self.hidden_state_dims
-        bufs = self.__dict__.setdefault("_act_batch_bufs", {})
-        st = bufs.get(N)
-        if st is None:
-            H_, W_ = self.observation_dims
-            nf = N * H_ * W_ * 3
-            st = bufs[N] = dict(
-                nf=nf,
-                pin=torch.empty(nf + N, dtype=torch.uint8).pin_memory(),  # the frames, then the first flags
-                dev=torch.empty(nf + N, dtype=torch.uint8, device=dev),
-                z0=torch.zeros(N, R * C, device=dev), h0=torch.zeros(N, Hd, device=dev),
-                a0=torch.zeros(N, A, device=dev),
-                status=torch.zeros(1, dtype=torch.int32, device=dev),
-                status_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                ws=torch.empty(L.query("dr_act_batch_workspace_bytes", d, N), dtype=torch.uint8, device=dev))
-        self._act_sync()  # the previous step's copy out of the pinned staging buffer has run (and it was ok)
-        nf = st["nf"]
-        pin = st["pin"].numpy()
-        pin[:nf] = observations.reshape(-1)
-        pin[nf:] = first
-        st["dev"].copy_(st["pin"], non_blocking=True)
-        if state is None:
-            zp, hp, ap = st["z0"], st["h0"], st["a0"]
-        else:
-            zp, hp, ap = (t.reshape(N, -1).float().contiguous() for t in state)
-        z2 = torch.empty(N, 1, R, C, device=dev)
-        h2 = torch.empty(N, 1, Hd, device=dev)
-        a2, mu, sg = (torch.empty(N, 1, A, device=dev) for _ in range(3))
-        try:
-            L.call("dr_act_batch", d, self.world_model.packed(), self.agent.actor_struct(), N, L.ptr(st["dev"]),
-                   L.ptr(st["dev"]) + nf, L.ptr(zp), L.ptr(hp), L.ptr(ap), hip.adhoc(dev).noise(),
-                   int(deterministic), L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu), L.ptr(sg), None,
-                   L.ptr(st["status"]), L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
-        except L.HipError as e:
-            if e.code != L.DR_E_UNSUPPORTED:
-                raise
+        nf = observations.size
+        out = self._act_fused("dr_act_batch", self.__dict__.setdefault("_act_batch_bufs", {}), N, dict(nf=nf),
+                              np.asarray(observations, dtype=np.uint8).reshape(-1), first, state, deterministic)
+        if out is None:
             # the device cannot hold the grid, or the widths are not the kernel's (e.g. the 5-layer VAE)
             self._act_batch_unsupported = True
             return self._act_step_batch_unfused(observations, state, first, deterministic)
-        st["status_host"].copy_(st["status"], non_blocking=True)
-        self._act_last = st
-        self._act_ev = torch.cuda.Event()
-        self._act_ev.record()
-        return a2, mu, sg, z2, h2
+        return out
 
     def _act_vec(self, observations, state, first, deterministic):
         """N rows of vector observations ((N, D) f32) through dr_act_vec in one
@@ -646,54 +635,15 @@ class Dreamer(nn.Module):
         answered DR_E_UNSUPPORTED (observation dim above DR_ACT_VEC_MAX_OBS,
         widths outside the kernel's, a device that cannot hold the grid): the
         caller then runs the unfused launches, and so does every later step."""
-        dev = self.device
-        N, D = observations.shape
-        d = self.world_model.dims(self.agent)
-        self.agent._ensure_flat()
-        R, C = self.latent_state_dims
-        A, Hd = self.action_dims, self.hidden_state_dims
+        N = observations.shape[0]
         bufs = self.__dict__.setdefault("_act_vec_bufs", {})
-        st = bufs.get(N)
-        if st is None:
-            nb = 4 * N * D
-            st = bufs[N] = dict(
-                vec=True, nb=nb,
-                pin=torch.empty(nb + N, dtype=torch.uint8).pin_memory(),  # the N x D floats, then the first flags
-                dev=torch.empty(nb + N, dtype=torch.uint8, device=dev),
-                z0=torch.zeros(N, R * C, device=dev), h0=torch.zeros(N, Hd, device=dev),
-                a0=torch.zeros(N, A, device=dev),
-                status=torch.zeros(1, dtype=torch.int32, device=dev),
-                status_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                ws=torch.empty(L.query("dr_act_vec_workspace_bytes", d, N), dtype=torch.uint8, device=dev))
-        self._act_sync()  # the previous step's copy out of the pinned staging buffer has run (and it was ok)
-        nb = st["nb"]
-        pin = st["pin"].numpy()
-        pin[:nb].view(np.float32)[...] = observations.reshape(-1)
-        pin[nb:] = first
-        st["dev"].copy_(st["pin"], non_blocking=True)
-        if state is None:
-            zp, hp, ap = st["z0"], st["h0"], st["a0"]
-        else:
-            zp, hp, ap = (t.reshape(N, -1).float().contiguous() for t in state)
-        z2 = torch.empty(N, 1, R, C, device=dev)
-        h2 = torch.empty(N, 1, Hd, device=dev)
-        a2, mu, sg = (torch.empty(N, 1, A, device=dev) for _ in range(3))
-        try:
-            L.call("dr_act_vec", d, self.world_model.packed(), self.agent.actor_struct(), N, L.ptr(st["dev"]),
-                   L.ptr(st["dev"]) + nb, L.ptr(zp), L.ptr(hp), L.ptr(ap), hip.adhoc(dev).noise(),
-                   int(deterministic), L.ptr(z2), L.ptr(h2), L.ptr(a2), L.ptr(mu), L.ptr(sg), None,
-                   L.ptr(st["status"]), L.ptr(st["ws"]), st["ws"].numel(), hip.stream())
-        except L.HipError as e:
-            if e.code != L.DR_E_UNSUPPORTED:
-                raise
+        out = self._act_fused("dr_act_vec", bufs, N, dict(vec=True),
+                              np.ascontiguousarray(observations, dtype=np.float32).reshape(-1).view(np.uint8),
+                              np.asarray(first, dtype=bool).reshape(N), state, deterministic)
+        if out is None:
             self._act_vec_unsupported = True
             del bufs[N]
-            return None
-        st["status_host"].copy_(st["status"], non_blocking=True)
-        self._act_last = st
-        self._act_ev = torch.cuda.Event()
-        self._act_ev.record()
-        return a2, mu, sg, z2, h2
+        return out
 
     def _act_step_batch_unfused(self, observations, state, first, deterministic):
         """act_step_batch through the batched launches that exist: dr_gru_cell,

@@ -291,19 +291,27 @@ int dr_actor_act(const dr_dims* d, const dr_actor* actor, int B, const float* h,
                  size_t ws_bytes, hipStream_t stream);
 /* Batch-1 acting step in ONE launch with in-kernel grid barriers (rollout_policy
  * / evaluate_agent / Run, Dreamer.py:177-226, 295-322, 374-401): if has_prev,
- * h' = GRU(z_prev, h, a_prev) (observe_step, WorldModel.py:79-82), else h' = h
- * (episode start, h = 0: Dreamer.py:186-187); z' = Encoder.encode(h', frame)
- * (VAE.py:57-99); a = Actor.act(h', z', deterministic) (Agent.py:202-210).
+ * h' = GRU(z_prev, h, a_prev) (observe_step, WorldModel.py:79-82), else h' = 0
+ * (episode start, Dreamer.py:186-187) and h, z_prev and a_prev are not read (h
+ * must still be non-null; z_prev and a_prev may be NULL);
+ * z' = Encoder.encode(h', frame) (VAE.py:57-99); a = Actor.act(h', z',
+ * deterministic) (Agent.py:202-210).  It is dr_act_batch with one row, the
+ * row's first flag (!has_prev) taken on the host: the same kernel, the same
+ * bits, no extra launch or copy.
  * frame: the env observation [H][W][3] u8 on the device.  Noise: the sampler
  * draws stream `noise.stream`, the actor `noise.stream + 1` (explicit q [R*C],
  * eps [A] when given).  logits_out may be NULL.  Inputs and outputs may alias
  * (h / h_out, z_prev / z_out, a_prev / a_out).
+ * dr_act_step_workspace_bytes(d) == dr_act_batch_workspace_bytes(d, 1); the
+ * workspace starts with workgroup 0's stage clock (16 int64 of 100 MHz ticks:
+ * words 0 ... 7 the stage ends, 15 the end of the kernel).
+ * DR_E_INVALID: null pointers, obs_dim != 0 (vector observations: dr_act_vec).
  * Co-residency of the grid is checked once per device (occupancy query); the
  * call returns DR_E_UNSUPPORTED when the device cannot hold it, or for dims
  * outside the kernel's staging (callers then use the unfused entry points).
  * status (device int, may be NULL; the caller zeroes it): set to 1 if a grid
- * barrier timed out at run time; it is the authoritative signal -- the outputs
- * then hold NaN whenever workgroup 0 saw the failure, and must not be used.
+ * barrier timed out at run time; it is the authoritative signal -- all five
+ * outputs then hold NaN and must not be used.
  * Test hook: the environment variable DREAMER_ACT_FORCE=timeout (every grid
  * barrier times out at once) or =nonresident (the co-residency check fails),
  * read at each call. */
@@ -324,7 +332,8 @@ int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_actor* acto
  * outputs are row-major [n_env][...].  Noise: explicit q [n_env*R][C] and eps
  * [n_env][A]; Philox draws row e as dr_act_step would with row0 + e (sampler
  * stream `noise.stream`, actor `noise.stream + 1`).  Row e's outputs depend on
- * row e's inputs and noise alone and are the bits dr_act_step gives on them.
+ * row e's inputs and noise alone and are the same bits for every n_env and row
+ * position: the bits dr_act_step, its one-row call, gives on them.
  * h / h_out, z_prev / z_out and a_prev / a_out may alias.
  * DR_E_UNSUPPORTED: n_env > DR_ACT_MAX_ENVS, the dims dr_act_step rejects, or
  * a device that cannot hold the grid (checked per n_env with the dynamic LDS
@@ -351,7 +360,8 @@ int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr_actor* act
  * device.  Noise, aliasing, status and DREAMER_ACT_FORCE as dr_act_batch; row
  * e's outputs depend on row e's inputs and noise alone and are the same bits
  * for every n_env, row position and mix of first flags (n_env = 1 is the
- * batch-1 step: there is no separate kernel).
+ * batch-1 step).  The kernel shares everything but its encoder stages with
+ * dr_act_batch's (act.hip).
  * DR_E_INVALID: n_env < 1, null pointers, obs_dim == 0 (pixel models use
  * dr_act_step / dr_act_batch).  DR_E_UNSUPPORTED: n_env > DR_ACT_MAX_ENVS,
  * obs_dim > DR_ACT_VEC_MAX_OBS, 4*enc_f2 > 256 or the other widths dr_act_step

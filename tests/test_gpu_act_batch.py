@@ -6,7 +6,10 @@ The kernel's contract is row independence: row e's outputs depend on row e's
 inputs and noise alone and are the bits dr_act_step gives on them, so the
 kernel tests compare rows with ``torch.equal`` against Dreamer.act_step and
 pin the one-launch path with ``act_batch_path = "fused"`` (the default
-dispatch follows the timing table).  Against the CPU
+dispatch follows the timing table).  dr_act_step is the
+one-row launch of the same kernel, so those comparisons are about the batch a
+row travels in (size, position, first flags, instantiation); what the kernel
+computes is checked against the CPU oracle.  Against the CPU
 oracle the tolerances are test_act_step_matches_oracle's: latent indices
 exact (inputs are tie-guarded), |d| <= 1e-6 + 1e-4 |ref| on h', mu, sigma
 and the action, 1e-6 on the straight-through latent values."""

@@ -457,3 +457,87 @@ def test_act_step_failure_paths(gpu, monkeypatch):
         close(mu_f, mu_o, 1e-4, 1e-6, "mu (unfused fallback)")
         close(sg_f, sg_o, 1e-4, 1e-6, "sigma (unfused fallback)")
         close(a_f, a_o, 1e-4, 1e-6, "action (unfused fallback)")
+
+
+def test_act_step_episode_start_contract(gpu):
+    """dr_act_step with has_prev = 0: z_prev and a_prev may be NULL and h is
+    not read (it holds NaN here); h' is exactly 0, status stays 0, and all five
+    outputs are the bits Dreamer.act_step(frame) gives under the same noise."""
+    from dreamer_amd import _lib as L
+    from dreamer_amd import hip
+    d, _ = _dreamer(gpu)
+    g = torch.Generator().manual_seed(52)
+    frame = torch.randint(0, 256, (64, 64, 3), generator=g, dtype=torch.uint8)
+    q = torch.empty(1, R, C).exponential_(generator=g).to(gpu)
+    eps = torch.randn(1, 1, A, generator=g).to(gpu)
+    dims = d.world_model.dims(d.agent)
+    d.agent._ensure_flat()
+    z2, h2 = torch.empty(R * C, device=gpu), torch.empty(HD, device=gpu)
+    a2, mu, sg = (torch.empty(A, device=gpu) for _ in range(3))
+    h_nan = torch.full((HD,), float("nan"), device=gpu)
+    status = torch.zeros(1, dtype=torch.int32, device=gpu)
+    ws = torch.empty(L.query("dr_act_step_workspace_bytes", dims), dtype=torch.uint8, device=gpu)
+    frame_dev = frame.to(gpu)
+    with torch.no_grad():
+        L.call("dr_act_step", dims, d.world_model.packed(), d.agent.actor_struct(), L.ptr(frame_dev), 0, None,
+               L.ptr(h_nan), None, hip.explicit_noise(q=q, eps=eps, device=gpu), 0, L.ptr(z2), L.ptr(h2), L.ptr(a2),
+               L.ptr(mu), L.ptr(sg), None, L.ptr(status), L.ptr(ws), ws.numel(), hip.stream())
+        torch.cuda.synchronize()
+        with hip.noise_override(q=q, eps=eps):
+            ref = d.act_step(frame.numpy())
+        d.act_check()
+    assert int(status.item()) == 0
+    assert bool((h2 == 0).all()), "h' at an episode start must be exactly 0"
+    for name, got, want in zip(("a", "mu", "sigma", "z", "h"), (a2, mu, sg, z2, h2), ref):
+        assert bool(torch.isfinite(got).all()), name
+        assert torch.equal(got, want.reshape(got.shape)), f"{name}: dr_act_step differs from Dreamer.act_step"
+
+
+def test_act_step_workspace_and_clock(gpu):
+    """dr_act_step's workspace is the one-row batch workspace, and workgroup
+    0's stage clock sits at its start: after one act_step the int64 words 0 ...
+    7 and 15 are non-zero and strictly increasing (bench.py reads them there)."""
+    from dreamer_amd import _lib as L
+    d, _ = _dreamer(gpu)
+    dims = d.world_model.dims(d.agent)
+    assert L.query("dr_act_step_workspace_bytes", dims) == L.query("dr_act_batch_workspace_bytes", dims, 1)
+    frame = torch.randint(0, 256, (64, 64, 3), generator=torch.Generator().manual_seed(53), dtype=torch.uint8).numpy()
+    with torch.no_grad():
+        d.act_step(frame)
+        d.act_check()
+    ts = d._act_bufs["ws"][0:128].view(torch.int64).cpu().tolist()
+    marks = [ts[m] for m in (0, 1, 2, 3, 4, 5, 6, 7, 15)]
+    assert all(t != 0 for t in marks), marks
+    assert all(b > a for a, b in zip(marks, marks[1:])), marks
+
+
+def test_act_step_error_codes(gpu, monkeypatch):
+    """dr_act_step's argument checks: DR_E_INVALID on vector-observation dims,
+    DR_E_UNSUPPORTED on 128 x 128 frames, both before any pointer is used; under
+    DREAMER_ACT_FORCE=nonresident DR_E_UNSUPPORTED with a message that names
+    the entry point."""
+    from dreamer_amd import _lib as L
+    from dreamer_amd import hip
+    d, _ = _dreamer(gpu)
+    d.agent._ensure_flat()
+    buf = torch.zeros(64, device=gpu)
+
+    def call(dims, ws, ws_bytes):
+        L.call("dr_act_step", dims, d.world_model.packed(), d.agent.actor_struct(), L.ptr(buf), 0, None, L.ptr(buf),
+               None, hip.explicit_noise(device=gpu), 0, *([L.ptr(buf)] * 5), None, None, ws, ws_bytes, hip.stream())
+
+    vec, big = d.world_model.dims(d.agent), d.world_model.dims(d.agent)
+    vec.obs_dim = 8
+    big.img_h = big.img_w = 128
+    for dims, code in ((vec, L.DR_E_INVALID), (big, L.DR_E_UNSUPPORTED)):
+        with pytest.raises(L.HipError) as ei:  # rejected before any pointer is used
+            call(dims, L.ptr(buf), 256)
+        assert ei.value.code == code
+    dims = d.world_model.dims(d.agent)
+    ws = torch.empty(L.query("dr_act_step_workspace_bytes", dims), dtype=torch.uint8, device=gpu)
+    monkeypatch.setenv("DREAMER_ACT_FORCE", "nonresident")
+    with pytest.raises(L.HipError) as ei:  # (the barrier lines of ws are zeroed; nothing else is touched)
+        call(dims, L.ptr(ws), ws.numel())
+    torch.cuda.synchronize()
+    assert ei.value.code == L.DR_E_UNSUPPORTED
+    assert str(ei.value).split("): ", 1)[1].startswith("dr_act_step:"), str(ei.value)
