@@ -31,7 +31,7 @@ int op_conv_repack_split3(int cout, int cin, const float* w, void* wr, hipStream
 bool op_conv_split3_supported(int n, int cin, int ih, int iw, int cout);
 // bf16 perf mode's conv3..: the split-conv tiling with one bf16 term (bf16 NHWC in,
 // bf16 NHWC / NCHW out, weights in op_conv_repack_split3 planes)
-// bf16 perf mode's conv1 + conv2: k_enc12_split3 with one bf16 term (64 x 64,
+// bf16 perf mode's conv1 + conv2: k_enc12_s1, one bf16 term (64 x 64,
 // 32 -> 64 channels, u8 ring only; DR_E_INVALID, nothing launched, otherwise)
 int op_enc12_s1_bf16(int n, int nb, int h, int w, int c1, int c2, const dr_frames* src, const float* w1,
                      const float* b1, const float* w2, const float* b2, void* wr1, void* wr2, void* out,
@@ -40,8 +40,8 @@ int op_conv_s1_bf16(int n, int cin, int ih, int iw, int cout, const void* in, co
                     void* out, int out_nchw, hipStream_t s);
 // the same convolution with LDS-DMA staged operands, four stages deep (conv_glds.hip; cout % 128 == 0)
 bool op_conv_glds_bf16_supported(int n, int cin, int ih, int iw, int cout);
-// fp32 (six split3 products) on the LDS-DMA staging: f32 NHWC in, CONV_EPI_FWD / CONV_EPI_DSILU epilogues
-bool op_conv_glds_s3_supported(int n, int cin, int ih, int iw, int cout);
+// fp32 (six split3 products) on the LDS-DMA staging: f32 NHWC in, CONV_EPI_FWD / CONV_EPI_DSILU epilogues;
+// shapes of op_conv_split3_supported, every operand 16-byte aligned (DR_E_INVALID otherwise)
 int op_conv_glds_s3(int n, int cin, int ih, int iw, int cout, const float* in, const void* wr, const float* bias,
                     float* out, int out_nchw, float* pre, int epi, hipStream_t s);
 // bf16 NT GEMM Y = X W^T + bias (X [M][K], W [N][K] bf16; K % 32 == 0, N % 4 == 0) on the same
@@ -56,6 +56,7 @@ int op_conv_split3(int n, int cin, int ih, int iw, int cout, const float* in, co
                    float* out, int out_nchw, hipStream_t s);
 // with the world-model step's epilogues (as op_conv_nhwc_ex): CONV_EPI_FWD +
 // optional pre = acc + bias (NHWC), or CONV_EPI_DSILU: out = acc * SiLU'(pre).
+// terms = 3 is op_conv_glds_s3 (16-byte aligned operands);
 // terms = 1: the bf16 world-model step's form (activations RNE-rounded to one
 // bf16 term as they are staged, the weights' first plane = their RNE bf16, one
 // MFMA per block; f32 in / out and the same epilogues)
@@ -176,7 +177,8 @@ bool op_convT_split3_supported(int n, int cin, int h, int w, int cout, int terms
 // the all-parity-class form op_convT_split3 takes for 64 -> 32 channels (8 x 16 anchor tiles)
 bool op_convT_cls_supported(int n, int cin, int h, int w, int cout);
 int op_convT_split3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s, int terms = 3);
-// the six-product form on the LDS-DMA ping-pong kernel (conv_glds.hip), taken by op_convT_split3 where it applies
+// the six-product form on the LDS-DMA ping-pong kernel (conv_glds.hip): op_convT_split3's terms = 3 route
+// (64 -> 32 channels apart); in, out, out2, bias, pre and wr 16-byte aligned, DR_E_INVALID otherwise
 bool op_convT_glds_s3_supported(const ConvTArgs& a, int epi);
 int op_convT_glds_s3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s);
 

@@ -2,17 +2,17 @@
 // k4 s2 p1 + SiLU) as an implicit GEMM whose operands move global -> LDS by
 // LDS-DMA (global_load_lds_dwordx4), three stages deep, two workgroups per CU.
 //
-// Why a second kernel beside k_conv_split3<.., NT3 = 1>: that tiling was built
-// for the fp32 mode's six products per block.  With ONE bf16 product per block a
-// 32-deep K chunk is 16 MFMAs per wave, ~260 cycles, and its register ring
+// Why a second kernel beside k_conv_s1 (conv_split.hip): that register-staged
+// tiling was built for the fp32 mode's six products per block.  With ONE bf16
+// product per block a 32-deep K chunk is 16 MFMAs per wave, ~260 cycles, and its register ring
 // staged one chunk ahead: every chunk waited on its L2 / HBM loads (the counter
 // pass read 6.2 VALU per MFMA, 45 % of wave time waiting, 0.19 of the bf16 peak
 // for conv3, profiles/r05u_pmc_sq_tcc.txt).  Here the staging costs no VGPRs
 // and no VALU beyond the addresses, and two workgroups share each CU.
 //
 // Tile: 256 pixels x 128 output channels, K = tap x 32 channels per chunk
-// (conv_chunk's tap-parity order, the same chunk sequence as k_conv_split3, so
-// the sums are bitwise the old kernel's), 8 waves as 4 (pixels) x 2 (channels)
+// (conv_chunk's tap-parity order, the same chunk sequence as k_conv_s1, so
+// the sums are bitwise that kernel's), 8 waves as 4 (pixels) x 2 (channels)
 // of 64 x 64, v_mfma_f32_16x16x32_bf16 with f32 accumulation.
 // LDS: one array of STAGES x (256 A rows + 128 B rows) x 64 bytes (72 KB).  An
 // LDS-DMA wave instruction writes 1 KiB contiguously (lane l at base + 16 l:
@@ -214,7 +214,7 @@ static int launch_glds(int n, int ih, int iw, int cout, const void* in, const vo
   // little for the read phase to hide, profiles/r06zb_ab_b16_pingpong.txt)
   // three stages, two workgroups per CU (72 KB of LDS, 100 VGPRs): B = 256 bf16
   // encoder conv3 / conv4 181 / 138 us, against 219 / 180 (four stages, one
-  // workgroup per CU), 229 / 186 (six) and 288 / 173 on k_conv_split3<.., 1>
+  // workgroup per CU), 229 / 186 (six) and 288 / 173 on k_conv_s1
   // (profiles/r06g_ab_conv_glds.txt)
   hipLaunchKernelGGL((k_conv_glds_bf16<C, NCHW, 3>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0, s, n, ih,
                      iw, cout, (const u16*)in, (const u16*)wr, bias, (u16*)out);
@@ -247,8 +247,9 @@ int op_conv_glds_bf16(int n, int cin, int ih, int iw, int cout, const void* in, 
 // f32 NHWC activations moved global -> LDS by LDS-DMA as they are, and split
 // per wave when the fragments are read.
 //
-// Why: k_conv_split3 (256 x 128 tiles, register-staged) splits each staged
-// float4 once per workgroup, but the staging sits between two barriers of the
+// Why: the register-staged six-product tile this replaced (k_conv_s1's tiling
+// with three planes, 256 x 128; removed, in git history) split each staged
+// float4 once per workgroup, but the staging sat between two barriers of the
 // chunk loop -- every wave loads, splits, stores to LDS, waits, then runs its
 // 96 MFMAs -- so the split and the LDS stores never overlap the MFMA pipe:
 // 0.45-0.47 of the split ceiling (conv3 718 us, conv4 692 us at 8192 frames,
@@ -259,8 +260,8 @@ int op_conv_glds_bf16(int n, int cin, int ih, int iw, int cout, const void* in, 
 // waves of a SIMD ping-pong between reading and multiplying (below): conv3 /
 // conv4 627 / 587 us, ~1.3-1.4 PFLOP/s of bf16 MFMA work under the chip's
 // load clock (profiles/r06z4_ab_conv_glds_s3.txt).  The per-accumulator order of
-// the six products and the chunk sequence are k_conv_split3's, so the output
-// is bitwise that kernel's.
+// the six products (smallest terms first) and the chunk sequence are that
+// tile's, so the output is bitwise what it gave.
 // LDS per stage: A 256 rows x 128 B (f32, 8 units a row, unit u of row r at
 // u ^ f[(r >> 1) & 7], f = {0,1,0,1,6,7,6,7}: the two ds_read_b128 of a lane
 // (units 2q, 2q + 1) are conflict-free in every 16-lane group of the b128
@@ -275,7 +276,7 @@ __device__ const float g_zero32[16] = {0.f};
 
 // BN = 128 or 64 output channels per tile, RW = 32 or 64 pixel rows per wave (8 RW per tile); EPI =
 // CONV_EPI_FWD or (NHWC) CONV_EPI_DSILU: out = acc * SiLU'(pre)
-// TR: the upsampling k4 s2 p1 form of conv_split.hip's k_convT_split3 (per output
+// TR: the upsampling k4 s2 p1 form of conv_split.hip's k_convT_s1 (per output
 // parity class a dense K = 4 taps x CIN over input-resolution pixels; weights
 // [class][K/32][3][cout][32]; its CT_EPI_BIAS / CT_EPI_DSILU epilogues), with the
 // same tile, chunk and product order: bitwise that kernel's sums.
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
   const long long tiles = ((M + GS_M - 1) / GS_M) * tiles_n * (TR ? 4 : 1);
   const int lt = dr_xcd_tile(blockIdx.x, (int)tiles);
   if (lt < 0) return;
-  // TR: parity class fastest (the four classes of one pixel tile read the same input, k_convT_split3)
+  // TR: parity class fastest (the four classes of one pixel tile read the same input, k_convT_s1)
   const int cls = TR ? (lt & 3) : 0, py = cls >> 1, px = cls & 1;
   const int lr = TR ? (lt >> 2) : lt;
   const long long m0 = (long long)(lr / tiles_n) * GS_M;
@@ -375,7 +376,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
   // parts: bit 0 = the A rows, bit 1 = the B planes
   auto issue = [&](int c, int parts) __attribute__((always_inline)) {
     int tap, ci0, kc, toff;
-    if constexpr (TR) {  // k_convT_split3's chunk order: tap-major, 32 channels per chunk
+    if constexpr (TR) {  // k_convT_s1's chunk order: tap-major, 32 channels per chunk
       tap = (32 * c) / CIN;
       ci0 = 32 * c - tap * CIN;
       kc = c;
@@ -432,7 +433,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
 #pragma unroll
       for (int j = 0; j < FN; ++j) b[pl][j] = st[GS_AU + (pl * GS_N + 16 * j + r) * 4 + fu];
   };
-  // k_conv_split3's order per accumulator: smallest terms first
+  // per accumulator: smallest terms first (conv_split.hip's header)
   auto multiply = [&]() __attribute__((always_inline)) {
 #define DR_GS3(PA, PB)                                                                                   \
   _Pragma("unroll") for (int i = 0; i < FM; ++i) _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = \
@@ -472,7 +473,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
   if (X) __builtin_amdgcn_s_barrier();
 
   if constexpr (TR) {
-    // k_convT_split3's epilogues at output pixel (2 y + py, 2 x + px): CT_EPI_BIAS out = acc + bias (or its
+    // k_convT_s1's epilogues at output pixel (2 y + py, 2 x + px): CT_EPI_BIAS out = acc + bias (or its
     // SiLU, silu_out), out2 = SiLU(acc + bias); CT_EPI_DSILU out = acc * SiLU'(pre)
     const int OW = 2 * iw, OH = 2 * ih;
 #pragma unroll
@@ -504,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
     }
     return;
   }
-  // k_conv_split3's epilogues: CONV_EPI_FWD out = SiLU(acc + bias), pre = acc + bias (NHWC) when given;
+  // k_conv_s1's epilogues: CONV_EPI_FWD out = SiLU(acc + bias), pre = acc + bias (NHWC) when given;
   // CONV_EPI_DSILU out = acc * SiLU'(pre)
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -547,11 +548,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_glds_s3(GS3Args g) {
     }
 }
 
-bool op_conv_glds_s3_supported(int n, int cin, int ih, int iw, int cout) {
-  return (cin == 32 || cin == 64 || cin == 128 || cin == 256) && cout % 64 == 0 && ih % 2 == 0 && iw % 2 == 0 &&
-         ((ih / 2) * (iw / 2)) % 4 == 0 && (long long)n * ih * iw * cin < (1LL << 31) - (1LL << 20);
-}
-
 template <int C, bool NCHW, int BN, int EPI>
 static int launch_glds_s3(int n, int ih, int iw, int cout, const float* in, const void* wr, const float* bias,
                           float* out, float* pre, hipStream_t s) {
@@ -572,14 +568,18 @@ static int launch_glds_s3(int n, int ih, int iw, int cout, const float* in, cons
 // f32 NHWC in, f32 NHWC / NCHW out (+ optional NHWC pre-activation), weights as
 // op_conv_repack_split3 planes; epi CONV_EPI_FWD (bias given) or, NHWC out only,
 // CONV_EPI_DSILU (pre given, no bias); 128-channel tiles where cout allows, else
-// 64; DR_E_INVALID (nothing launched) for other shapes
+// 64; DR_E_INVALID (nothing launched) for other shapes (op_conv_split3_supported)
+// and for operands that are not 16-byte aligned
 int op_conv_glds_s3(int n, int cin, int ih, int iw, int cout, const float* in, const void* wr, const float* bias,
                     float* out, int out_nchw, float* pre, int epi, hipStream_t s) {
   const bool dsilu = epi == CONV_EPI_DSILU;
-  if (!op_conv_glds_s3_supported(n, cin, ih, iw, cout) || (epi != CONV_EPI_FWD && !dsilu) ||
-      (dsilu && (out_nchw || !pre)) || (!dsilu && !bias) ||
-      (((uintptr_t)in | (uintptr_t)wr | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)pre) & 15)) {
+  if (!op_conv_split3_supported(n, cin, ih, iw, cout) || (epi != CONV_EPI_FWD && !dsilu) ||
+      (dsilu && (out_nchw || !pre)) || (!dsilu && !bias)) {
     dr_set_error("conv_glds_s3: unsupported problem (cin=%d ih=%d iw=%d cout=%d epi=%d)", cin, ih, iw, cout, epi);
+    return DR_E_INVALID;
+  }
+  if (((uintptr_t)in | (uintptr_t)wr | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)pre) & 15) {
+    dr_set_error("conv_glds_s3: in, weight planes, out, bias and pre must be 16-byte aligned");
     return DR_E_INVALID;
   }
 #define DR_GL(C, BN)                                                                                             \
@@ -625,11 +625,12 @@ bool op_convT_glds_s3_supported(const ConvTArgs& a, int epi) {
          (long long)a.n * a.h * a.w * a.cin < (1LL << 31) - (1LL << 20);
 }
 
-// the six-product upsampling conv (k_convT_split3's problems, terms = 3) on the
+// the six-product upsampling conv (op_convT_split3's problems, terms = 3) on the
 // LDS-DMA ping-pong kernel; DR_E_INVALID (nothing launched) where unsupported
 int op_convT_glds_s3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s) {
   if (!op_convT_glds_s3_supported(a, epi) || ((uintptr_t)wr & 15)) {
-    dr_set_error("convT_glds_s3: unsupported problem (cin=%d cout=%d h=%d w=%d epi=%d)", a.cin, a.cout, a.h, a.w, epi);
+    dr_set_error("convT_glds_s3: unsupported problem (cin=%d cout=%d h=%d w=%d epi=%d; in, weight planes, out, out2, "
+                 "bias and pre must be 16-byte aligned)", a.cin, a.cout, a.h, a.w, epi);
     return DR_E_INVALID;
   }
 #define DR_GT(C, BN)                                                                                  \

@@ -23,6 +23,16 @@
 // three bf16 planes [3][cout][K].  LDS holds each plane as rows of 4 16-byte
 // units, unit u of row r at u ^ ((r >> 2) & 3): the 16 rows one MFMA fragment
 // read touches fall on 16 distinct 16-byte bank groups.
+//
+// Which kernel runs what.  Six products (fp32 mode): conv1 + conv2 fused on
+// k_enc12_split3_x8, the 64 -> 32 transposed conv on k_convT_cls<., 3>, the
+// conv weight gradients on k_wgrad_split3_db, the tall NT and the TN GEMMs on
+// k_gemm_split3 / k_gemm_pp_multi -- all in this file; conv3.. and the other
+// (transposed) convs of the world-model step on conv_glds.hip's LDS-DMA kernel
+// (k_conv_glds_s3), which reads the same weight planes and keeps the same
+// product order.  One product (bf16 mode; the same tiles with one bf16 plane):
+// k_conv_s1, k_convT_s1, k_enc12_s1, k_wgrad_s1, k_convT_cls<., 1> here, the
+// 128-channel convs on conv_glds.hip's k_conv_glds_bf16.
 #include "conv.h"
 
 #include <algorithm>
@@ -75,12 +85,13 @@ __device__ __forceinline__ unsigned pack_bf16x2(float x0, float x1) { return b16
 // (NHWC, for the world-model backward); CONV_EPI_DSILU (NHWC only, no bias):
 // out = acc * SiLU'(pre) -- the input gradient of a transposed conv followed by
 // the SiLU backward of the layer below (WorldModel.training_step's decoder)
-// NT3 = 1: the bf16 perf mode's form of the same tile -- bf16 NHWC activations
-// staged as they are (one plane), the weights' first split plane (= their RNE
-// bf16), one MFMA per block, bf16 output (RNE after bias + SiLU); `in` / `out`
-// then point at u16 data.  NT3 = 1 with IO16 = false: the bf16 world-model
-// step's form -- f32 activations rounded (RNE) to one bf16 plane as they are
-// staged, f32 outputs and every epilogue of the three-term form
+// k_conv_s1 is the one-term tile: one bf16 activation plane, the weights'
+// first split plane (= their RNE bf16), one MFMA per block.  (The six-product
+// fp32 convolutions run on conv_glds.hip's LDS-DMA kernels.)  IO16: the bf16
+// perf mode's form -- bf16 NHWC activations staged as they are, bf16 output
+// (RNE after bias + SiLU); `in` / `out` then point at u16 data.  IO16 = false:
+// the bf16 world-model step's form -- f32 activations rounded (RNE) to bf16 as
+// they are staged, f32 outputs, both epilogues
 // K-loop position c -> (tap, first channel, chunk index of the natural
 // tap-major order).  Channel chunks outer; within one, the 16 taps in four
 // parity groups {ky, ky + 2} x {kx, kx + 2}: the four taps of a group read the
@@ -100,13 +111,12 @@ __device__ __forceinline__ void conv_chunk(int c, int& tap, int& ci0, int& kc) {
   kc = tap * CPT + cc;
 }
 
-template <int BM, int BN, int CIN, bool OUT_NCHW, int PIPE, int EPI = CONV_EPI_FWD, int NT3 = 3, bool IO16 = (NT3 == 1)>
-__global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, int iw, int cout,
-                                                         const float* __restrict__ in, const u16* __restrict__ wr,
-                                                         const float* __restrict__ bias, float* __restrict__ out,
-                                                         float* __restrict__ pre) {
-  static_assert(NT3 == 3 || (NT3 == 1 && (EPI == CONV_EPI_FWD || !IO16)), "conv_split3 terms");
-  static_assert(!IO16 || NT3 == 1, "bf16 storage is the one-term form's");
+template <int BM, int BN, int CIN, bool OUT_NCHW, int EPI, bool IO16>
+__global__ __launch_bounds__(BM * 2) void k_conv_s1(int n_frames, int ih, int iw, int cout,
+                                                     const float* __restrict__ in, const u16* __restrict__ wr,
+                                                     const float* __restrict__ bias, float* __restrict__ out,
+                                                     float* __restrict__ pre) {
+  static_assert(EPI == CONV_EPI_FWD || !IO16, "bf16 storage has the forward epilogue only");
   const u16* __restrict__ in16 = reinterpret_cast<const u16*>(in);
   u16* __restrict__ out16 = reinterpret_cast<u16*>(out);
   constexpr int NT = BM * 2;         // WM = BM / 64 waves over pixels x 2 waves over channels
@@ -114,11 +124,11 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
   constexpr int NCH = K / 32;
   constexpr int WTN = BN / 2, FM = 4, FN = WTN / 16;
   constexpr int APT = BM * 8 / NT;   // float4 of A per thread per chunk (= 4)
-  constexpr int BU = NT3 * BN * 4;   // 16-byte B units per chunk (NT3 planes x BN rows x 4)
+  constexpr int BU = BN * 4;         // 16-byte B units per chunk (BN rows x 4)
   constexpr int BPT = (BU + NT - 1) / NT;
-  static_assert(CIN % 32 == 0 && APT == 4 && FN >= 1, "conv_split3 tile");
-  __shared__ __attribute__((aligned(16))) u32x4 As[2][NT3][BM][4];
-  __shared__ __attribute__((aligned(16))) u32x4 Bs[2][NT3][BN][4];
+  static_assert(CIN % 32 == 0 && APT == 4 && FN >= 1, "conv_s1 tile");
+  __shared__ __attribute__((aligned(16))) u32x4 As[2][BM][4];
+  __shared__ __attribute__((aligned(16))) u32x4 Bs[2][BN][4];
 
   const int oh = ih / 2, ow = iw / 2, hw = oh * ow;
   const long long M = (long long)n_frames * hw;
@@ -155,7 +165,7 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
   // two ring slots as separate arrays picked at compile time (one 2-D ring
   // array indexed by slot was left in scratch memory by the compiler)
   f32x4 ra0[APT], ra1[APT];
-  u32x2 rh0[APT], rh1[APT];  // NT3 = 1: 4 bf16 channels
+  u32x2 rh0[APT], rh1[APT];  // IO16: 4 bf16 channels
   u32x4 rb0[BPT], rb1[BPT];
   unsigned ok0 = 0, ok1 = 0;  // per slot: bit i = A row i's tap is inside the frame
   auto load = [&](int c, auto slot) __attribute__((always_inline)) {
@@ -182,9 +192,11 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
     okm = om;
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
-      const int e = tid + NT * j;  // (plane, row, unit)
+      const int e = tid + NT * j;  // (row, unit) of plane 0 of the chunk's three
       if (BU % NT == 0 || e < BU) {
-        const int pl = e / (BN * 4), rem = e - pl * BN * 4, row = rem >> 2, u = rem & 3;
+        // pl = 0, spelled as the three-plane tile's index: it folds away, but the
+        // compiler orders the 128-channel tiles' prologue by it
+        const int pl = e / (BN * 4), row = e >> 2, u = e & 3;
         rb[j] = *reinterpret_cast<const u32x4*>(wr + (((long long)kc * 3 + pl) * cout + n0 + row) * 32 + 8 * u);
       }
     }
@@ -199,26 +211,18 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
       const int row = prow + (NT / 8) * i;
       const int unit = (quad >> 1) ^ swz(row), half = quad & 1;
       if constexpr (IO16) {
-        reinterpret_cast<u32x2*>(&As[buf][0][row][unit])[half] = (okm >> i) & 1u ? rh[i] : (u32x2){0u, 0u};
-      } else if constexpr (NT3 == 1) {
-        const f32x4 v = (okm >> i) & 1u ? ra[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-        reinterpret_cast<u32x2*>(&As[buf][0][row][unit])[half] = pack_bf16x4(v);
+        reinterpret_cast<u32x2*>(&As[buf][row][unit])[half] = (okm >> i) & 1u ? rh[i] : (u32x2){0u, 0u};
       } else {
         const f32x4 v = (okm >> i) & 1u ? ra[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-        unsigned h0, m0_, l0, h1, m1, l1;
-        split3_pair(v[0], v[1], h0, m0_, l0);
-        split3_pair(v[2], v[3], h1, m1, l1);
-        reinterpret_cast<u32x2*>(&As[buf][0][row][unit])[half] = (u32x2){h0, h1};
-        reinterpret_cast<u32x2*>(&As[buf][1][row][unit])[half] = (u32x2){m0_, m1};
-        reinterpret_cast<u32x2*>(&As[buf][2][row][unit])[half] = (u32x2){l0, l1};
+        reinterpret_cast<u32x2*>(&As[buf][row][unit])[half] = pack_bf16x4(v);
       }
     }
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
       const int e = tid + NT * j;
       if (BU % NT == 0 || e < BU) {
-        const int pl = e / (BN * 4), rem = e - pl * BN * 4, row = rem >> 2, u = rem & 3;
-        Bs[buf][pl][row][u ^ swz(row)] = rb[j];
+        const int row = e >> 2, u = e & 3;
+        Bs[buf][row][u ^ swz(row)] = rb[j];
       }
     }
   };
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
   load(1, S1{});
   store(S0{}, 0);
   __syncthreads();
-  // the ring slot of chunk c is c % PIPE; every slot index is a compile-time
+  // the ring slot of chunk c is c % 2; every slot index is a compile-time
   // constant (a run-time index puts the ring in scratch memory)
   auto step = [&](int c, auto slot) __attribute__((always_inline)) {
     constexpr int SL = decltype(slot)::value;
@@ -247,32 +251,22 @@ __global__ __launch_bounds__(BM * 2) void k_conv_split3(int n_frames, int ih, in
     // unconditionally (the last two chunks reload chunk NCH - 1, unused): a
     // conditional refill made the compiler wait for every outstanding load
     // before the next LDS store, a one-deep pipeline
-    load(min(c + PIPE, NCH - 1), slot);
-    u32x4 a[NT3][FM], b[NT3][FN];
+    load(min(c + 2, NCH - 1), slot);
+    u32x4 a[FM], b[FN];
 #pragma unroll
-    for (int pl = 0; pl < NT3; ++pl) {
+    for (int i = 0; i < FM; ++i) a[i] = As[buf][wm0 + 16 * i + r][fu];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) a[pl][i] = As[buf][pl][wm0 + 16 * i + r][fu];
+    for (int j = 0; j < FN; ++j) b[j] = Bs[buf][wn0 + 16 * j + r][fu];
+    // independent accumulators innermost
 #pragma unroll
-      for (int j = 0; j < FN; ++j) b[pl][j] = Bs[buf][pl][wn0 + 16 * j + r][fu];
-    }
-    // smallest terms first; independent accumulators innermost
-#define DR_S3(PA, PB)                                                                                   \
-  _Pragma("unroll") for (int i = 0; i < FM; ++i) _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = \
-      OUT_NCHW ? mfma_b16(a[PA][i], b[PB][j], acc[i][j]) : mfma_b16(b[PB][j], a[PA][i], acc[i][j]);
-    if constexpr (NT3 == 3) {
-      DR_S3(2, 0)
-      DR_S3(1, 1)
-      DR_S3(0, 2)
-      DR_S3(1, 0)
-      DR_S3(0, 1)
-    }
-    DR_S3(0, 0)
-#undef DR_S3
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j)
+        acc[i][j] = OUT_NCHW ? mfma_b16(a[i], b[j], acc[i][j]) : mfma_b16(b[j], a[i], acc[i][j]);
     if (c + 1 < NCH) store(Next{}, buf ^ 1);
     dr_lds_barrier();
   };
-  static_assert(PIPE == 2 && NCH % 2 == 0, "conv_split3 ring");
+  static_assert(NCH % 2 == 0, "conv_s1 ring");
   for (int c = 0; c < NCH; c += 2) {
     step(c, S0{});
     step(c + 1, S1{});
@@ -372,31 +366,28 @@ int op_conv_repack_split3(int cout, int cin, const float* w, void* wr, hipStream
 // space too.  conv1's output (+ bias, SiLU) is split3 once, into three bf16
 // planes in LDS, and conv2 runs the usual six split products from them.
 //
-// A workgroup (4 waves) owns R2 = 8 rows of conv2 output (128 pixels x 64
-// channels, half a frame): it stages the RI = 38 input rows (bf16 [row][x+1][4
-// ch], as k_enc12_bf16), computes the R1 = 18 conv1 rows they feed (2 rows
-// recomputed per frame), then conv2 tap by tap with the tap's weight planes
-// (12 KB) double-buffered through LDS.  Wave w: conv2 rows 4 (w & 1) .. + 3,
-// channels 32 (w >> 1) .. + 31.
-// LDS: conv1 planes [3][4 c8][PS] 16-byte units, PS = 18 * 32 + 1 (odd plane
-// stride: the ds_read_b128 lane groups of a stride-2 pixel fragment fall on
-// distinct bank quads, as in k_enc12_bf16), 110.8 KB; input rows 20 KB;
-// weight ring 2 x 12 KB.  One workgroup per CU.
+// A workgroup owns R2 = 8 rows of conv2 output (128 pixels x 64 channels, half
+// a frame): it stages the RI = 38 input rows (bf16 [row][x+1][4 ch], as
+// k_enc12_bf16), computes the R1 = 18 conv1 rows they feed (2 rows recomputed
+// per frame) into LDS planes, then conv2 tap by tap, one MFMA k-step per tap,
+// with the weight fragments straight from L2.  A wave's conv2 block: rows
+// 4 (w & 1) .. + 3, channels 32 ((w >> 1) & 1) .. + 31.
+// LDS: conv1 planes [terms][4 c8][PS] 16-byte units, PS = 18 * 32 + 1 (odd
+// plane stride: the ds_read_b128 lane groups of a stride-2 pixel fragment fall
+// on distinct bank quads, as in k_enc12_bf16), 36.9 KB a plane; input rows 20 KB.
+// Two kernels: k_enc12_s1 (one term, 4 waves, two workgroups per CU) and
+// k_enc12_split3_x8 (three terms, 8 waves, one workgroup per CU).
 // ---------------------------------------------------------------------------
 #define E12_R2 8
 #define E12_R1 (2 * E12_R2 + 2)
 #define E12_RI (2 * E12_R1 + 2)
 #define E12_PS (E12_R1 * 32 + 1)
 #define E12_LWI 66
-static constexpr size_t e12_lds_bytes(int terms = 3) {
-  return (size_t)terms * 4 * E12_PS * 16 + (size_t)E12_RI * E12_LWI * 8;
-}
+static constexpr size_t e12s1_lds_bytes() { return (size_t)4 * E12_PS * 16 + (size_t)E12_RI * E12_LWI * 8; }
 
 // Phase timestamps (tools/build_e12_ts.sh, tools/enc12_probe.py): compiled in
 // only with -DDR_E12_TS.  Thread 0 of waves 0 and 4 of the first workgroups
 // stamps the 100 MHz clock at the phase boundaries of its first tiles.
-// DR_E12_TS=2 also sends the three-term launch back to the one-schedule form
-// (k_enc12_split3<8>), for a phase table of both on one box.
 #define E12_TS_WGS 4
 #define E12_TS_TILES 4
 #define E12_TS_MARKS 8
@@ -418,36 +409,35 @@ extern "C" int dr_e12_ts_read(long long* host) {
   } while (0)
 #endif
 
-// NW = 8: two waves per SIMD -- waves 0-3 run conv2's taps 0-7 and waves 4-7
-// taps 8-15 over the same 64 x 32 output blocks, the two partial sums meet in
-// LDS (fixed order: taps 0-7 + taps 8-15) before the epilogue
-// Optional saves for the world-model backward (NHWC f32, NULL = none): pre0 /
-// a0 = conv1's pre-activation / output (the tile's own 16 conv1 rows), pre1 =
-// conv2's pre-activation (out receives conv2's output as always).
-// NTM = 1: the bf16 perf mode's form -- the weights' first plane (their RNE
-// bf16) only, conv1's output rounded (RNE) to ONE bf16 plane in LDS, one MFMA
-// per block, conv2's output written as bf16 NHWC (`out` then points at u16
-// data); no saves.  One third of the LDS, so two workgroups fit per CU.
-// one-term form (bf16 mode), measured at B = 256 (profiles/r03za_ab_enc12_s1.txt):
+// k_enc12_s1: the one-term form of the tile above -- the weights' first plane
+// (their RNE bf16) only, conv1's output rounded (RNE) to ONE bf16 plane in LDS,
+// one MFMA per block; a wave runs all 16 taps of its 64 x 32 output block.  One
+// third of the three-term LDS, so two workgroups fit per CU.
+// O16: the bf16 perf mode's form -- conv2's output written as bf16 NHWC (`out`
+// then points at u16 data), no saves.  O16 = false: the bf16 world-model step's
+// form -- f32 output and the optional saves for the backward (NHWC f32, NULL =
+// none): pre0 / a0 = conv1's pre-activation / output (the tile's own 16 conv1
+// rows), pre1 = conv2's pre-activation.
+// Measured at B = 256 (profiles/r03za_ab_enc12_s1.txt):
 // 4 waves, two workgroups per CU (57 KB of LDS each; 164 VGPRs, no spill):
 // encoder 0.936 ms; 8 waves at two workgroups per CU (128 VGPRs, 104 B spilled)
 // 1.01-1.02 ms; 8 waves at one (165 VGPRs) 0.962 ms
 #define DR_E12S1_WAVES 4  // waves per workgroup of the one-term form
 #define DR_E12S1_OCC 2    // min waves per SIMD of the one-term form
-// O16 = false with NTM = 1: the bf16 world-model step's form -- one term, f32
-// output and the saves
-template <int NW, int NTM = 3, bool O16 = (NTM == 1)>
-__global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_split3(int n, int nb, dr_frames src, const u16* __restrict__ wr1,
-                                                          const float* __restrict__ b1, const u16* __restrict__ wr2,
-                                                          const float* __restrict__ b2, float* __restrict__ out,
-                                                          float* __restrict__ pre0, float* __restrict__ a0,
-                                                          float* __restrict__ pre1) {
-  static_assert((NW == 4 || NW == 8) && (NTM == 1 || NTM == 3) && (!O16 || NTM == 1), "enc12 waves / terms");
-  constexpr int NTH = 64 * NW, TAPS = NW == 8 ? 8 : 16;
+template <bool O16>
+__global__ __launch_bounds__(64 * DR_E12S1_WAVES, DR_E12S1_OCC) void k_enc12_s1(
+    int n, int nb, dr_frames src, const u16* __restrict__ wr1, const float* __restrict__ b1,
+    const u16* __restrict__ wr2, const float* __restrict__ b2, float* __restrict__ out, float* __restrict__ pre0,
+    float* __restrict__ a0, float* __restrict__ pre1) {
+  static_assert(DR_E12S1_WAVES == 4, "enc12_s1: one wave per 64 x 32 conv2 block");
+  // NTM: bf16 planes per operand.  The loops over it and kh below keep the
+  // shape of the three-term tile they came from: folding them by hand changes
+  // the compiled kernel (register allocation), which this form does not
+  constexpr int NW = DR_E12S1_WAVES, NTM = 1, NTH = 64 * NW, TAPS = 16;
   constexpr int R2 = E12_R2, R1 = E12_R1, RI = E12_RI, PS = E12_PS, LWI = E12_LWI;
   constexpr int OW1 = 32, OW2 = 16, W = 64, H = 64, C1 = 32, C2 = 64;
   extern __shared__ __attribute__((aligned(16))) u32x4 e12_smem[];
-  u32x4* c1o = e12_smem;                                                       // [3][4][PS]
+  u32x4* c1o = e12_smem;                                                       // [NTM][4][PS]
   uint2* xin = reinterpret_cast<uint2*>(e12_smem + NTM * 4 * PS);             // [RI][LWI]
   u16* xs = reinterpret_cast<u16*>(xin);
   u16* c1h = reinterpret_cast<u16*>(c1o);
@@ -497,9 +487,11 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
   in_store(tile);
   __syncthreads();
 
+  // kh: the wave's tap range, TAPS kh .. + TAPS - 1: 0 at four waves, which the
+  // compiler proves from the launch bound
   const int w4 = wave & 3, kh = wave >> 2, ph = w4 & 1, ch = w4 >> 1;
   // conv2 weight fragments straight from L2 (the 196 KB of split planes stay
-  // resident): lane (r, q) of wf[pl][jj] = row 32 ch + 16 jj + r, k 8 q .. + 7
+  // resident; plane 0 is read): lane (r, q) of wf[pl][jj] = row 32 ch + 16 jj + r, k 8 q .. + 7
   const u16* wbase = wr2 + ((long long)(32 * ch + r)) * 32 + 8 * q;
   auto wld = [&](u32x4 (&wf)[NTM][2], int tap) __attribute__((always_inline)) {
 #pragma unroll
@@ -513,8 +505,8 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
     const int f = tile >> 1, y2_0 = (tile & 1) * R2, y1_0 = 2 * y2_0 - 1;
     const int next = tile + (int)gridDim.x;
     E12_TS(tile, 0);
-    // conv1 weights (A operand: lane -> channel 16 j + r, k = 32 s + 8 q .. + 7), three
-    // planes: re-read per tile (L2) so that they hold no registers during conv2
+    // conv1 weights (A operand: lane -> channel 16 j + r, k = 32 s + 8 q .. + 7), plane
+    // 0: re-read per tile (L2) so that they hold no registers during conv2
     u32x4 wa1[NTM][2][2];
 #pragma unroll
     for (int pl = 0; pl < NTM; ++pl)
@@ -535,10 +527,10 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
     for (int i = wave; i < F1; i += NW) {
       const int p0 = 16 * i, yl = p0 / OW1, x1 = p0 - yl * OW1 + r, p = p0 + r;
       const int y1 = y1_0 + yl;
-      uint2 hv[2], mv[2], lv[2];
+      uint2 hv[2];
       if (y1 < 0 || y1 >= H / 2) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) hv[j] = mv[j] = lv[j] = make_uint2(0u, 0u);
+        for (int j = 0; j < 2; ++j) hv[j] = make_uint2(0u, 0u);
       } else {
         f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
@@ -566,13 +558,8 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
             *reinterpret_cast<f32x4*>(pre0 + o1 + 16 * j + 4 * q) = (f32x4){pv[0], pv[1], pv[2], pv[3]};
             *reinterpret_cast<f32x4*>(a0 + o1 + 16 * j + 4 * q) = (f32x4){v[0], v[1], v[2], v[3]};
           }
-          if constexpr (NTM == 1) {
-            const u32x2 pk = pack_bf16x4((f32x4){v[0], v[1], v[2], v[3]});
-            hv[j] = make_uint2(pk[0], pk[1]);
-          } else {
-            split3_pair(v[0], v[1], hv[j].x, mv[j].x, lv[j].x);
-            split3_pair(v[2], v[3], hv[j].y, mv[j].y, lv[j].y);
-          }
+          const u32x2 pk = pack_bf16x4((f32x4){v[0], v[1], v[2], v[3]});
+          hv[j] = make_uint2(pk[0], pk[1]);
         }
       }
 #pragma unroll
@@ -580,10 +567,6 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
         const int c8 = 2 * j + (q >> 1);
         const int o = (c8 * PS + p) * 8 + (q & 1) * 4;  // u16 offset inside a plane
         *reinterpret_cast<uint2*>(c1h + o) = hv[j];
-        if constexpr (NTM == 3) {
-          *reinterpret_cast<uint2*>(c1h + 4 * PS * 8 + o) = mv[j];
-          *reinterpret_cast<uint2*>(c1h + 2 * 4 * PS * 8 + o) = lv[j];
-        }
       }
     }
     E12_TS(tile, 1);
@@ -615,17 +598,9 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
           pf[pl][i] = xok ? v : (u32x4){0u, 0u, 0u, 0u};
         }
       }
-      // smallest terms first (weight plane x activation plane)
 #define E12_S3(PW, PA)                       \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) acc[i][jj] = \
       mfma_b16(wf[PW][jj], pf[PA][i], acc[i][jj]);
-      if constexpr (NTM == 3) {
-        E12_S3(2, 0)
-        E12_S3(1, 1)
-        E12_S3(0, 2)
-        E12_S3(1, 0)
-        E12_S3(0, 1)
-      }
       E12_S3(0, 0)
 #undef E12_S3
     };
@@ -638,24 +613,6 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
         for (int jj = 0; jj < 2; ++jj) wfa[pl][jj] = wfb[pl][jj];
     }
     E12_TS(tile, 3);
-    if (NW == 8) {
-      // taps 8-15 partials through LDS (c1o is free once every wave is past conv2)
-      f32x4* red = reinterpret_cast<f32x4*>(e12_smem);  // [4 waves][8 blocks][64 lanes]
-      __syncthreads();
-      if (kh == 1) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) red[(w4 * 8 + i * 2 + jj) * 64 + lane] = acc[i][jj];
-      }
-      __syncthreads();
-      if (kh == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) acc[i][jj] += red[(w4 * 8 + i * 2 + jj) * 64 + lane];
-      }
-    }
     E12_TS(tile, 4);
     // lane (r, q) of acc[i][jj]: channels 32 ch + 16 jj + 4 q .. + 3 of conv2 pixel (row 4 ph + i, column r)
 #pragma unroll
@@ -688,10 +645,16 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
 }
 
 // ---------------------------------------------------------------------------
-// The three-term form at 8 waves (the fp32 encoder and, with the saves, the
-// fp32 world-model step): the tile, the wave roles in conv2 and every sum of
-// k_enc12_split3<8> above, bit for bit, on a schedule that keeps less work
-// beside an idle matrix pipe:
+// The three-term form at 8 waves, two per SIMD (the fp32 encoder and, with the
+// saves, the fp32 world-model step).  Sum order, which every schedule change
+// here has kept bit for bit: conv1 accumulates its two k-steps in order, each
+// as weight plane l, m, h (smallest first) times the one input term, then
+// * 1/255 + bias, SiLU, split3 into three planes.  conv2: waves 0-3 sum taps
+// 0-7 and waves 4-7 taps 8-15 of the same 64 x 32 output blocks, taps
+// ascending, each tap's six products smallest first (weight plane x activation
+// plane: l h, m m, h l, m h, h m, h h); the result is (taps 0-7) + (taps
+// 8-15), then + bias.  The schedule keeps little work beside an idle matrix
+// pipe:
 //  - the conv1 planes carry the two out-of-frame columns as zeros (row stride
 //    34, written once), so a conv2 tap reads its fragments without selects;
 //  - conv2 names a tap's fragments and weights one tap ahead of its MFMAs (two
@@ -707,6 +670,7 @@ __global__ __launch_bounds__(64 * NW, NTM == 1 ? DR_E12S1_OCC : 1) void k_enc12_
 //    half), and its weights and bias are read once, not per tile;
 //  - the barriers wait on LDS only (dr_lds_barrier), so the next tile's input
 //    loads and the epilogue's stores stay in flight across them.
+// Optional saves as k_enc12_s1's.
 // LDS: planes [3][4 c8][PS] 117.7 KB + 32 KB (input rows 20 KB / exchange).
 // ---------------------------------------------------------------------------
 #define E12X_OW 34
@@ -1017,14 +981,8 @@ int op_enc12_split3_ex(int n, int nb, int h, int w, int c1, int c2, const dr_fra
     return DR_E_INVALID;
   if (!op_enc12_split3_ok(n, h, w, c1, c2, src)) return DR_E_INVALID;
   static const bool raised = [] {
-    (void)hipFuncSetAttribute((const void*)k_enc12_split3<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)e12_lds_bytes());
     (void)hipFuncSetAttribute((const void*)k_enc12_split3_x8, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)e12x_lds_bytes());
-#if defined(DR_E12_TS) && DR_E12_TS == 2
-    (void)hipFuncSetAttribute((const void*)k_enc12_split3<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)e12_lds_bytes());
-#endif
     return true;
   }();
   (void)raised;
@@ -1038,16 +996,16 @@ int op_enc12_split3_ex(int n, int nb, int h, int w, int c1, int c2, const dr_fra
     int dev = 0;
     DR_TRY_HIP(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return DR_E_INVALID;
-    auto kf = k_enc12_split3<DR_E12S1_WAVES, 1, false>;
+    auto kf = k_enc12_s1<false>;
     if (slots1[dev] == 0) {
-      (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e12_lds_bytes(1));
+      (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e12s1_lds_bytes());
       int cus = 0, per = 0;
       DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kf, 64 * DR_E12S1_WAVES, e12_lds_bytes(1)));
+      DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kf, 64 * DR_E12S1_WAVES, e12s1_lds_bytes()));
       slots1[dev] = std::max(1, per) * std::max(1, cus);
     }
     const int grid = std::min(n * 2, slots1[dev]);
-    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(64 * DR_E12S1_WAVES), e12_lds_bytes(1), s, n, nb, *src,
+    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(64 * DR_E12S1_WAVES), e12s1_lds_bytes(), s, n, nb, *src,
                        (const u16*)wr1, b1, (const u16*)wr2, b2, out, pre0, a0, pre1);
     return dr_check_launch("enc12_split3 (one term)");
   }
@@ -1061,17 +1019,12 @@ int op_enc12_split3_ex(int n, int nb, int h, int w, int c1, int c2, const dr_fra
   if (cus[dev] == 0) DR_TRY_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
   const int grid = std::min(n * 2, std::max(1, cus[dev]));
   // 8 waves (two per SIMD); one wave per SIMD measured 517.0 k against 532.9 k (r03o)
-#if defined(DR_E12_TS) && DR_E12_TS == 2
-  hipLaunchKernelGGL(k_enc12_split3<8>, dim3((unsigned)grid), dim3(512), e12_lds_bytes(), s, n, nb, *src,
-                     (const u16*)wr1, b1, (const u16*)wr2, b2, out, pre0, a0, pre1);
-#else
   hipLaunchKernelGGL(k_enc12_split3_x8, dim3((unsigned)grid), dim3(512), e12x_lds_bytes(), s, n, nb, *src,
                      (const u16*)wr1, b1, (const u16*)wr2, b2, out, pre0, a0, pre1);
-#endif
   return dr_check_launch("enc12_split3");
 }
 
-// bf16 perf mode: k_enc12_split3<DR_E12S1_WAVES, 1> (one bf16 term; out = bf16 NHWC).
+// bf16 perf mode: k_enc12_s1<true> (one bf16 term; out = bf16 NHWC).
 // wr1 / wr2 are the split3 repack slots (c1 * 64 * 6 and c2 * c1 * 16 * 6
 // bytes; plane 0 is read).  DR_E_INVALID (nothing launched) for other shapes.
 int op_enc12_s1_bf16(int n, int nb, int h, int w, int c1, int c2, const dr_frames* src, const float* w1,
@@ -1084,12 +1037,12 @@ int op_enc12_s1_bf16(int n, int nb, int h, int w, int c1, int c2, const dr_frame
   DR_TRY_HIP(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return DR_E_INVALID;
   if (slots[dev] == 0) {
-    (void)hipFuncSetAttribute((const void*)k_enc12_split3<DR_E12S1_WAVES, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)e12_lds_bytes(1));
+    (void)hipFuncSetAttribute((const void*)k_enc12_s1<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)e12s1_lds_bytes());
     int cus = 0, per = 0;
     DR_TRY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_enc12_split3<DR_E12S1_WAVES, 1>,
-                                                            64 * DR_E12S1_WAVES, e12_lds_bytes(1)));
+    DR_TRY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_enc12_s1<true>, 64 * DR_E12S1_WAVES,
+                                                            e12s1_lds_bytes()));
     slots[dev] = std::max(1, per) * std::max(1, cus);
   }
   if (!prepacked) {
@@ -1098,24 +1051,25 @@ int op_enc12_s1_bf16(int n, int nb, int h, int w, int c1, int c2, const dr_frame
     DR_TRY(op_conv_repack_split3(c2, c1, w2, wr2, s));
   }
   const int grid = std::min(n * 2, slots[dev]);
-  hipLaunchKernelGGL((k_enc12_split3<DR_E12S1_WAVES, 1>), dim3((unsigned)grid), dim3(64 * DR_E12S1_WAVES),
-                     e12_lds_bytes(1), s, n, nb, *src,
+  hipLaunchKernelGGL(k_enc12_s1<true>, dim3((unsigned)grid), dim3(64 * DR_E12S1_WAVES), e12s1_lds_bytes(), s, n, nb,
+                     *src,
                      (const u16*)wr1, b1, (const u16*)wr2, b2, (float*)out, nullptr, nullptr, nullptr);
   return dr_check_launch("enc12_s1_bf16");
 }
 
-template <int BM, int BN, int CIN, bool NCHW, int PIPE, int EPI = CONV_EPI_FWD, int TERMS = 3>
-static int launch_s3(int n, int ih, int iw, int cout, const float* in, const void* wr, const float* bias, float* out,
-                     float* pre, hipStream_t s) {
+// the bf16 world-model step's form: f32 in / out, one bf16 term
+template <int BN, int CIN, bool NCHW, int EPI>
+static int launch_s1_f32(int n, int ih, int iw, int cout, const float* in, const void* wr, const float* bias,
+                         float* out, float* pre, hipStream_t s) {
   const long long M = (long long)n * (ih / 2) * (iw / 2);
-  const long long tiles = ((M + BM - 1) / BM) * (cout / BN);
+  const long long tiles = ((M + 255) / 256) * (cout / BN);
   if (tiles >= (1LL << 30)) {
     dr_set_error("conv_split3: too many tiles");
     return DR_E_INVALID;
   }
-  hipLaunchKernelGGL((k_conv_split3<BM, BN, CIN, NCHW, PIPE, EPI, TERMS, false>), dim3((unsigned)dr_xcd_grid((int)tiles)),
-                     dim3(BM * 2), 0, s, n, ih, iw, cout, in, (const u16*)wr, bias, out, pre);
-  return dr_check_launch("conv_split3");
+  hipLaunchKernelGGL((k_conv_s1<256, BN, CIN, NCHW, EPI, false>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0,
+                     s, n, ih, iw, cout, in, (const u16*)wr, bias, out, pre);
+  return dr_check_launch("conv_split3 (one term)");
 }
 
 bool op_conv_split3_supported(int n, int cin, int ih, int iw, int cout) {
@@ -1134,38 +1088,29 @@ int op_conv_split3_ex(int n, int cin, int ih, int iw, int cout, const float* in,
     dr_set_error("conv_split3: the SiLU-backward epilogue needs NHWC output and a pre-activation tensor");
     return DR_E_INVALID;
   }
-  // six products: the LDS-DMA ping-pong kernel (conv_glds.hip) where it applies
-  if (terms == 3 && (epi == CONV_EPI_FWD ? bias != nullptr : pre != nullptr) && op_conv_glds_s3_supported(n, cin, ih, iw, cout) &&
-      !(((uintptr_t)in | (uintptr_t)wr | (uintptr_t)out | (uintptr_t)bias | (uintptr_t)pre) & 15))
-    return op_conv_glds_s3(n, cin, ih, iw, cout, in, wr, bias, out, out_nchw, pre, epi, s);
-  // measured at 8192 frames (tools/conv_ab.py): 256 x 64 tiles
-  // for 64 output channels (980 us; 128 x 64 at two workgroups per CU: 1004),
-  // 256 x 128 for 128 / 256 channels (709 / 658 us; 128 x 128: ~1.1 ms): the
-  // weights are re-read once per pixel tile, so taller tiles pay
-#define DR_S3E(BN, C, NCHW, T)                                                                                         \
-  (epi == CONV_EPI_DSILU ? launch_s3<256, BN, C, NCHW, 2, CONV_EPI_DSILU, T>(n, ih, iw, cout, in, wr, bias, out, pre, s) \
-                         : launch_s3<256, BN, C, NCHW, 2, CONV_EPI_FWD, T>(n, ih, iw, cout, in, wr, bias, out, pre, s))
-#define DR_S3L(C, T)                                                                                                 \
-  if (cin == C) {                                                                                                    \
-    if (cout % 128 == 0)                                                                                             \
-      return out_nchw ? launch_s3<256, 128, C, true, 2, CONV_EPI_FWD, T>(n, ih, iw, cout, in, wr, bias, out, pre, s) \
-                      : DR_S3E(128, C, false, T);                                                                    \
-    return out_nchw ? launch_s3<256, 64, C, true, 2, CONV_EPI_FWD, T>(n, ih, iw, cout, in, wr, bias, out, pre, s)    \
-                    : DR_S3E(64, C, false, T);                                                                       \
+  // six products: the LDS-DMA ping-pong kernel (conv_glds.hip), 16-byte aligned operands
+  if (terms == 3) return op_conv_glds_s3(n, cin, ih, iw, cout, in, wr, bias, out, out_nchw, pre, epi, s);
+  // one term, measured at 8192 frames: 256 x 64 tiles for 64 output
+  // channels (128 x 64 at two workgroups per CU was slower), 256 x 128 for
+  // 128 / 256 channels: the weights are re-read once per pixel tile, so taller
+  // tiles pay
+#define DR_S1E(BN, C)                                                                                      \
+  (epi == CONV_EPI_DSILU ? launch_s1_f32<BN, C, false, CONV_EPI_DSILU>(n, ih, iw, cout, in, wr, bias, out, pre, s) \
+                         : launch_s1_f32<BN, C, false, CONV_EPI_FWD>(n, ih, iw, cout, in, wr, bias, out, pre, s))
+#define DR_S1F(C)                                                                                               \
+  if (cin == C) {                                                                                               \
+    if (cout % 128 == 0)                                                                                        \
+      return out_nchw ? launch_s1_f32<128, C, true, CONV_EPI_FWD>(n, ih, iw, cout, in, wr, bias, out, pre, s)   \
+                      : DR_S1E(128, C);                                                                         \
+    return out_nchw ? launch_s1_f32<64, C, true, CONV_EPI_FWD>(n, ih, iw, cout, in, wr, bias, out, pre, s)      \
+                    : DR_S1E(64, C);                                                                            \
   }
-  if (terms == 1) {
-    DR_S3L(32, 1)
-    DR_S3L(64, 1)
-    DR_S3L(128, 1)
-    DR_S3L(256, 1)
-  } else {
-    DR_S3L(32, 3)
-    DR_S3L(64, 3)
-    DR_S3L(128, 3)
-    DR_S3L(256, 3)
-  }
-#undef DR_S3L
-#undef DR_S3E
+  DR_S1F(32)
+  DR_S1F(64)
+  DR_S1F(128)
+  DR_S1F(256)
+#undef DR_S1F
+#undef DR_S1E
   return DR_E_INVALID;
 }
 
@@ -1174,20 +1119,21 @@ int op_conv_split3(int n, int cin, int ih, int iw, int cout, const float* in, co
   return op_conv_split3_ex(n, cin, ih, iw, cout, in, wr, bias, out, out_nchw, nullptr, CONV_EPI_FWD, s);
 }
 
-// bf16 perf mode: the same tiling with one term (k_conv_split3<..., NT3 = 1>):
+// bf16 perf mode: the one-term tile with bf16 storage (k_conv_s1<..., IO16>):
 // bf16 NHWC in, bf16 NHWC / NCHW out, weights as op_conv_repack_split3 planes
-// (plane 0 read).  Replaces k_conv_bf16 for conv3.. (its 128 x 128 tiles ran
+// (plane 0 read), for cout % 128 != 0 -- 128-channel multiples take
+// op_conv_glds_bf16.  Replaces k_conv_bf16 for conv3.. (its 128 x 128 tiles ran
 // at 0.16 of the bf16 peak).
-template <int BN, int C, bool NCHW>
+template <int C, bool NCHW>
 static int launch_s1(int n, int ih, int iw, int cout, const void* in, const void* wr, const float* bias, void* out,
                      hipStream_t s) {
   const long long M = (long long)n * (ih / 2) * (iw / 2);
-  const long long tiles = ((M + 255) / 256) * (cout / BN);
+  const long long tiles = ((M + 255) / 256) * (cout / 64);
   if (tiles >= (1LL << 30)) {
     dr_set_error("conv_s1_bf16: too many tiles");
     return DR_E_INVALID;
   }
-  hipLaunchKernelGGL((k_conv_split3<256, BN, C, NCHW, 2, CONV_EPI_FWD, 1>), dim3((unsigned)dr_xcd_grid((int)tiles)),
+  hipLaunchKernelGGL((k_conv_s1<256, 64, C, NCHW, CONV_EPI_FWD, true>), dim3((unsigned)dr_xcd_grid((int)tiles)),
                      dim3(512), 0, s, n, ih, iw, cout, (const float*)in, (const u16*)wr, bias, (float*)out, nullptr);
   return dr_check_launch("conv_s1_bf16");
 }
@@ -1200,14 +1146,10 @@ int op_conv_s1_bf16(int n, int cin, int ih, int iw, int cout, const void* in, co
   }
   if (op_conv_glds_bf16_supported(n, cin, ih, iw, cout))
     return op_conv_glds_bf16(n, cin, ih, iw, cout, in, wr, bias, out, out_nchw, s);
-#define DR_S1L(C)                                                                              \
-  if (cin == C) {                                                                              \
-    if (cout % 128 == 0)                                                                       \
-      return out_nchw ? launch_s1<128, C, true>(n, ih, iw, cout, in, wr, bias, out, s)         \
-                      : launch_s1<128, C, false>(n, ih, iw, cout, in, wr, bias, out, s);       \
-    return out_nchw ? launch_s1<64, C, true>(n, ih, iw, cout, in, wr, bias, out, s)            \
-                    : launch_s1<64, C, false>(n, ih, iw, cout, in, wr, bias, out, s);          \
-  }
+#define DR_S1L(C)                                                                  \
+  if (cin == C)                                                                    \
+    return out_nchw ? launch_s1<C, true>(n, ih, iw, cout, in, wr, bias, out, s)    \
+                    : launch_s1<C, false>(n, ih, iw, cout, in, wr, bias, out, s);
   DR_S1L(32)
   DR_S1L(64)
   DR_S1L(128)
@@ -1221,28 +1163,27 @@ int op_conv_s1_bf16(int n, int cin, int ih, int iw, int cout, const void* in, co
 // data gradient of an encoder Conv2d), f32-accurate on the bf16 MFMA: the
 // implicit GEMM of wmconv.hip's k_convT_nhwc -- per output parity class
 // (py, px) a dense K = 4 taps x CIN, tap (dy, dx): input (y + py - dy,
-// x + px - dx), kernel (1 - py + 2 dy, 1 - px + 2 dx) -- with the operands of
-// k_conv_split3: activations split3 as they are staged (truncation split,
-// v_perm packing, swizzled 64-byte plane rows), weights split once per call
-// into [class][K/32][3 planes][cout][32].  Epilogues of the world-model step
-// (NHWC out, ldc == cout): CT_EPI_BIAS (out = acc + bias, out2 / silu_out =
-// SiLU) and CT_EPI_DSILU (out = acc * SiLU'(pre)).  TERMS = 1: the bf16
-// world-model step's form (activations RNE-rounded to one bf16 plane while
-// staged, weight plane 0, one MFMA per block).
+// x + px - dx), kernel (1 - py + 2 dy, 1 - px + 2 dx) -- with the weights
+// split once per call into [class][K/32][3 planes][cout][32].  Epilogues of
+// the world-model step (NHWC out, ldc == cout): CT_EPI_BIAS (out = acc + bias,
+// out2 / silu_out = SiLU) and CT_EPI_DSILU (out = acc * SiLU'(pre)).
+// k_convT_s1 is the bf16 world-model step's one-term tile, k_conv_s1's
+// operands: activations RNE-rounded to one bf16 plane while staged (swizzled
+// 64-byte rows), weight plane 0, one MFMA per block.  The six-product form runs
+// on conv_glds.hip's LDS-DMA kernel and, for 64 -> 32 channels, on k_convT_cls.
 // ---------------------------------------------------------------------------
-template <int BM, int BN, int CIN, int EPI, int TERMS = 3>
-__global__ __launch_bounds__(BM * 2) void k_convT_split3(ConvTArgs a, const u16* __restrict__ wr) {
+template <int BM, int BN, int CIN, int EPI>
+__global__ __launch_bounds__(BM * 2) void k_convT_s1(ConvTArgs a, const u16* __restrict__ wr) {
   constexpr int NT = BM * 2;
   constexpr int K = CIN * 4;
   constexpr int NCH = K / 32;
   constexpr int WTN = BN / 2, FM = 4, FN = WTN / 16;
   constexpr int APT = BM * 8 / NT;
-  constexpr int BU = TERMS * BN * 4;
+  constexpr int BU = BN * 4;
   constexpr int BPT = (BU + NT - 1) / NT;
-  static_assert(CIN % 32 == 0 && APT == 4 && FN >= 1 && NCH % 2 == 0 && (TERMS == 1 || TERMS == 3),
-                "convT_split3 tile");
-  __shared__ __attribute__((aligned(16))) u32x4 As[2][TERMS][BM][4];
-  __shared__ __attribute__((aligned(16))) u32x4 Bs[2][TERMS][BN][4];
+  static_assert(CIN % 32 == 0 && APT == 4 && FN >= 1 && NCH % 2 == 0, "convT_s1 tile");
+  __shared__ __attribute__((aligned(16))) u32x4 As[2][BM][4];
+  __shared__ __attribute__((aligned(16))) u32x4 Bs[2][BN][4];
 
   const int h = a.h, w = a.w, hw = h * w, cout = a.cout;
   const long long M = (long long)a.n * hw;  // input-resolution pixels of one parity class
@@ -1304,7 +1245,7 @@ __global__ __launch_bounds__(BM * 2) void k_convT_split3(ConvTArgs a, const u16*
     for (int j = 0; j < BPT; ++j) {
       const int e = tid + NT * j;
       if (BU % NT == 0 || e < BU) {
-        const int pl = e / (BN * 4), rm = e - pl * BN * 4, row = rm >> 2, u = rm & 3;
+        const int pl = e / (BN * 4), rm = e - pl * BN * 4, row = rm >> 2, u = rm & 3;  // pl = 0, as in k_conv_s1
         rb[j] = *reinterpret_cast<const u32x4*>(wc + (((long long)c * 3 + pl) * cout + n0 + row) * 32 + 8 * u);
       }
     }
@@ -1318,23 +1259,14 @@ __global__ __launch_bounds__(BM * 2) void k_convT_split3(ConvTArgs a, const u16*
       const int row = prow + (NT / 8) * i;
       const f32x4 v = (okm >> i) & 1u ? ra[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
       const int unit = (quad >> 1) ^ swz(row), half = quad & 1;
-      if constexpr (TERMS == 1) {
-        reinterpret_cast<u32x2*>(&As[buf][0][row][unit])[half] = pack_bf16x4(v);
-      } else {
-        unsigned h0, m0_, l0, h1, m1, l1;
-        split3_pair(v[0], v[1], h0, m0_, l0);
-        split3_pair(v[2], v[3], h1, m1, l1);
-        reinterpret_cast<u32x2*>(&As[buf][0][row][unit])[half] = (u32x2){h0, h1};
-        reinterpret_cast<u32x2*>(&As[buf][1][row][unit])[half] = (u32x2){m0_, m1};
-        reinterpret_cast<u32x2*>(&As[buf][2][row][unit])[half] = (u32x2){l0, l1};
-      }
+      reinterpret_cast<u32x2*>(&As[buf][row][unit])[half] = pack_bf16x4(v);
     }
 #pragma unroll
     for (int j = 0; j < BPT; ++j) {
       const int e = tid + NT * j;
       if (BU % NT == 0 || e < BU) {
-        const int pl = e / (BN * 4), rm = e - pl * BN * 4, row = rm >> 2, u = rm & 3;
-        Bs[buf][pl][row][u ^ swz(row)] = rb[j];
+        const int row = e >> 2, u = e & 3;
+        Bs[buf][row][u ^ swz(row)] = rb[j];
       }
     }
   };
@@ -1358,27 +1290,16 @@ __global__ __launch_bounds__(BM * 2) void k_convT_split3(ConvTArgs a, const u16*
     using Next = std::integral_constant<int, 1 - SL>;
     const int buf = c & 1;
     load(min(c + 2, NCH - 1), slot);
-    u32x4 av[TERMS][FM], bv[TERMS][FN];
+    u32x4 av[FM], bv[FN];
 #pragma unroll
-    for (int pl = 0; pl < TERMS; ++pl) {
+    for (int i = 0; i < FM; ++i) av[i] = As[buf][wm0 + 16 * i + r][fu];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) av[pl][i] = As[buf][pl][wm0 + 16 * i + r][fu];
-#pragma unroll
-      for (int j = 0; j < FN; ++j) bv[pl][j] = Bs[buf][pl][wn0 + 16 * j + r][fu];
-    }
+    for (int j = 0; j < FN; ++j) bv[j] = Bs[buf][wn0 + 16 * j + r][fu];
     // weights as the MFMA A operand (lane: 4 consecutive channels of one pixel)
-#define DR_T3(PA, PB)                                                                                   \
-  _Pragma("unroll") for (int i = 0; i < FM; ++i) _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = \
-      mfma_b16(bv[PB][j], av[PA][i], acc[i][j]);
-    if constexpr (TERMS == 3) {
-      DR_T3(2, 0)
-      DR_T3(1, 1)
-      DR_T3(0, 2)
-      DR_T3(1, 0)
-      DR_T3(0, 1)
-    }
-    DR_T3(0, 0)
-#undef DR_T3
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[i][j] = mfma_b16(bv[j], av[i], acc[i][j]);
     if (c + 1 < NCH) store(Next{}, buf ^ 1);
     dr_lds_barrier();
   };
@@ -1449,8 +1370,8 @@ int op_convT_repack_split3(int cin, int cout, const float* wt, void* wr, hipStre
 // VAE.py:37-38).  The per-class kernels stage an im2col row per (class, tap):
 // every input element is fetched and split 16 times, and at 32 output channels
 // that staging outweighs the MFMAs (k_convT_nhwc: 790 / 950 us at B = 256
-// T = 15 on the f32 MFMA, 5.5 VALU per MFMA; k_convT_split3<.., 32, 64, ., 1>:
-// 365 / 450 us).  Here a workgroup owns 8 x 16 input anchors of one frame: it
+// T = 15 on the f32 MFMA, 5.5 VALU per MFMA; the one-term 256 x 32 tile of
+// k_convT_s1: 365 / 450 us).  Here a workgroup owns 8 x 16 input anchors of one frame: it
 // stages their (8 + 2) x (16 + 2) x 64 input patch ONCE -- split3 (or RNE
 // bf16) into LDS planes, pixel rows of 144 bytes (64 bf16 + 16 bytes of pad:
 // the 16 pixels of a fragment read land on distinct bank quads) -- and wave w
@@ -1458,8 +1379,8 @@ int op_convT_repack_split3(int cin, int cout, const float* wt, void* wr, hipStre
 // 32 output channels: per tap (dy, dx) and 32-channel chunk, 8 anchor-row
 // fragments read straight from the patch at offset (py - dy, px - dx), the
 // weight fragments (op_convT_repack_split3 planes, class-major) from L2, one
-// tap-chunk ahead in registers.  Products per chunk in k_convT_split3's order
-// (six for TERMS = 3, f32-accurate; one for TERMS = 1).  WM step B = 256 T = 15:
+// tap-chunk ahead in registers.  Products per chunk smallest terms first
+// (the six of the file header for TERMS = 3, f32-accurate; one for TERMS = 1).  WM step B = 256 T = 15:
 // fp32 13.67 -> 12.71 ms (the two layers 790 / 952 -> ~360 / 410 us), bf16
 // 9.18 -> 8.80 ms (365 / 450 -> ~240 / 267 us; the data-gradient form moves
 // 1.24 GB of input / pre-activation / output: HBM-bound), profiles/r06n_*.
@@ -1620,12 +1541,12 @@ bool op_convT_split3_supported(int n, int cin, int h, int w, int cout, int terms
          4LL * (((long long)n * h * w + 255) / 256) * (cout / 32) < (1LL << 30);
 }
 
-template <int BN, int C, int EPI, int T>
-static int launch_t3(const ConvTArgs& a, const void* wr, hipStream_t s) {
+template <int BN, int C, int EPI>
+static int launch_t1(const ConvTArgs& a, const void* wr, hipStream_t s) {
   const long long tiles = 4 * (((long long)a.n * a.h * a.w + 255) / 256) * (a.cout / BN);
-  hipLaunchKernelGGL((k_convT_split3<256, BN, C, EPI, T>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0, s,
-                     a, (const u16*)wr);
-  return dr_check_launch("convT_split3");
+  hipLaunchKernelGGL((k_convT_s1<256, BN, C, EPI>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0, s, a,
+                     (const u16*)wr);
+  return dr_check_launch("convT_split3 (one term)");
 }
 
 int op_convT_split3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s, int terms) {
@@ -1635,29 +1556,31 @@ int op_convT_split3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s, 
     dr_set_error("convT_split3: unsupported problem (cin=%d cout=%d h=%d w=%d epi=%d)", a.cin, a.cout, a.h, a.w, epi);
     return DR_E_INVALID;
   }
-  if (op_convT_cls_supported(a.n, a.cin, a.h, a.w, a.cout) && ((uintptr_t)a.in & 15) == 0 &&
-      ((uintptr_t)a.out & 15) == 0 && (!a.out2 || ((uintptr_t)a.out2 & 15) == 0) &&
-      (epi != CT_EPI_DSILU || ((uintptr_t)a.pre & 15) == 0) && (epi != CT_EPI_BIAS || ((uintptr_t)a.bias & 15) == 0))
-    return launch_convT_cls(epi, a, wr, s, terms);
-  if (terms == 3 && op_convT_glds_s3_supported(a, epi) && !((uintptr_t)wr & 15)) return op_convT_glds_s3(epi, a, wr, s);
-#define DR_T3E(BN, C, T) \
-  (epi == CT_EPI_DSILU ? launch_t3<BN, C, CT_EPI_DSILU, T>(a, wr, s) : launch_t3<BN, C, CT_EPI_BIAS, T>(a, wr, s))
-#define DR_T3L(C)                                                                          \
-  if (a.cin == C) {                                                                        \
-    if (terms == 1) {                                                                      \
-      if (a.cout % 128 == 0) return DR_T3E(128, C, 1);                                     \
-      if (a.cout % 64 == 0) return DR_T3E(64, C, 1);                                       \
-      return DR_T3E(32, C, 1);                                                             \
-    }                                                                                      \
-    if (a.cout % 128 == 0) return DR_T3E(128, C, 3);                                       \
-    return DR_T3E(64, C, 3);                                                               \
+  if (op_convT_cls_supported(a.n, a.cin, a.h, a.w, a.cout)) {
+    if (((uintptr_t)a.in & 15) == 0 && ((uintptr_t)a.out & 15) == 0 && (!a.out2 || ((uintptr_t)a.out2 & 15) == 0) &&
+        (epi != CT_EPI_DSILU || ((uintptr_t)a.pre & 15) == 0) && (epi != CT_EPI_BIAS || ((uintptr_t)a.bias & 15) == 0))
+      return launch_convT_cls(epi, a, wr, s, terms);
+    if (terms == 3) {
+      dr_set_error("convT_split3: in, out, out2, bias and pre must be 16-byte aligned");
+      return DR_E_INVALID;
+    }
   }
-  DR_T3L(32)
-  DR_T3L(64)
-  DR_T3L(128)
-  DR_T3L(256)
-#undef DR_T3L
-#undef DR_T3E
+  // six products: the LDS-DMA ping-pong kernel (conv_glds.hip), 16-byte aligned operands
+  if (terms == 3) return op_convT_glds_s3(epi, a, wr, s);
+#define DR_T1E(BN, C) \
+  (epi == CT_EPI_DSILU ? launch_t1<BN, C, CT_EPI_DSILU>(a, wr, s) : launch_t1<BN, C, CT_EPI_BIAS>(a, wr, s))
+#define DR_T1L(C)                                  \
+  if (a.cin == C) {                                \
+    if (a.cout % 128 == 0) return DR_T1E(128, C);  \
+    if (a.cout % 64 == 0) return DR_T1E(64, C);    \
+    return DR_T1E(32, C);                          \
+  }
+  DR_T1L(32)
+  DR_T1L(64)
+  DR_T1L(128)
+  DR_T1L(256)
+#undef DR_T1L
+#undef DR_T1E
   return DR_E_INVALID;
 }
 
@@ -1675,29 +1598,27 @@ int op_convT_split3(int epi, const ConvTArgs& a, const void* wr, hipStream_t s, 
 // 2 (a) x 4 (n), partial planes per pixel split reduced by k_wgrad_reduce.
 // Low-resolution sizes are powers of two (shift addressing).
 // ---------------------------------------------------------------------------
-// (Round 6: the six-product form runs on k_wgrad_split3_db below; this kernel
-// keeps the one-term form, whose single buffer is 55-83 KB: on the
-// double-buffered kernel the one-term WM step measured 8.50 -> 8.64 ms with
-// 32-pixel chunks, 8.52 with 64 for the 128-channel layers,
-// profiles/r06x_ab_wgrad_db_one_term.txt -- without the split there is little
-// VALU for the second buffer to overlap.)
-// TERMS = 1: both operands RNE-rounded to one bf16 plane (bf16 world-model
-// step); that form also takes BN = 256 column tiles (the output-gradient rows
-// re-read half as often: 255 -> 209 us for the 128-channel layers, r04r) and
-// BM = 32.  (The 32 x 4-channel layers next to the frames stay on the f32
-// kernel: a BN = 64 one-term form measured 314 us against 311, and with
-// SiLU on load 752 us.)
-template <int BM, int TERMS = 3, int BN = 128>
-__global__ __launch_bounds__(512) void k_wgrad_split3(int n, int lh, int lw, int ca, int cb,
-                                                      const float* __restrict__ lo, int lda,
-                                                      const float* __restrict__ hi, int ldb, int chunk,
-                                                      float* __restrict__ part) {
+// k_wgrad_s1, the single-buffer kernel, is the one-term form: both operands
+// RNE-rounded to one bf16 plane as they are staged (bf16 world-model step).
+// (The six-product form runs on k_wgrad_split3_db below.  The one-term form
+// stays here, its buffer is 18-42 KB: on the double-buffered kernel the
+// one-term WM step measured 8.50 -> 8.64 ms with 32-pixel chunks, 8.52 with 64
+// for the 128-channel layers, profiles/r06x_ab_wgrad_db_one_term.txt --
+// without the split there is little VALU for the second buffer to overlap.)
+// It also takes BN = 256 column tiles (the output-gradient rows re-read half
+// as often: 255 -> 209 us for the 128-channel layers, r04r), BN = 512 for
+// BM = 64 and BM = 32.  (The 32 x 4-channel layers next to the frames stay on
+// the f32 kernel: a BN = 64 one-term form measured 314 us against 311, and
+// with SiLU on load 752 us.)
+template <int BM, int BN>
+__global__ __launch_bounds__(512) void k_wgrad_s1(int n, int lh, int lw, int ca, int cb,
+                                                  const float* __restrict__ lo, int lda,
+                                                  const float* __restrict__ hi, int ldb, int chunk,
+                                                  float* __restrict__ part) {
   constexpr int KC = 64, RP = KC / 8 + 1;
   constexpr int FM = BM / 32, FN = BN / 64;  // wave tile (BM / 2) x (BN / 4)
-  static_assert((TERMS == 1 || TERMS == 3) && FM >= 1 &&
-                    (BN == 128 || BN == 256 || (BN == 512 && TERMS == 1 && BM <= 64)),
-                "wgrad_split3 tile");
-  __shared__ __attribute__((aligned(16))) u32x4 S[TERMS][BM + BN][RP];
+  static_assert(FM >= 1 && (BN == 128 || BN == 256 || (BN == 512 && BM <= 64)), "wgrad_s1 tile");
+  __shared__ __attribute__((aligned(16))) u32x4 S[BM + BN][RP];
   const int N = 16 * cb;
   const int tiles_n = N / BN, tiles = (ca / BM) * tiles_n;
   // XCD-contiguous logical order (dr_xcd_tile), tiles of one pixel split
@@ -1762,25 +1683,10 @@ __global__ __launch_bounds__(512) void k_wgrad_split3(int n, int lh, int lw, int
       if (!active[j]) continue;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        if constexpr (TERMS == 1) {
-          u32x4 ph;
+        u32x4 ph;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) ph[i] = pack_bf16x2(v[j][2 * i][c], v[j][2 * i + 1][c]);
-          S[0][row0[j] + c][oct[j]] = ph;
-        } else {
-          u32x4 ph, pm, pl;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            unsigned hh, mm, ll;
-            split3_pair(v[j][2 * i][c], v[j][2 * i + 1][c], hh, mm, ll);
-            ph[i] = hh;
-            pm[i] = mm;
-            pl[i] = ll;
-          }
-          S[0][row0[j] + c][oct[j]] = ph;
-          S[1][row0[j] + c][oct[j]] = pm;
-          S[2][row0[j] + c][oct[j]] = pl;
-        }
+        for (int i = 0; i < 4; ++i) ph[i] = pack_bf16x2(v[j][2 * i][c], v[j][2 * i + 1][c]);
+        S[row0[j] + c][oct[j]] = ph;
       }
     }
   };
@@ -1801,26 +1707,21 @@ __global__ __launch_bounds__(512) void k_wgrad_split3(int n, int lh, int lw, int
       load(k_begin + (c + 1 < nch ? c + 1 : c) * KC);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        u32x4 av[TERMS][FM], bv[TERMS][FN];
+        // (fragments in k_wgrad_split3_db's plane-loop form, NPL = 1: written as
+        // two flat loops, the 32-row tiles' LDS reads come out in another order)
+        constexpr int NPL = 1;
+        u32x4 av[NPL][FM], bv[NPL][FN];
 #pragma unroll
-        for (int pl = 0; pl < TERMS; ++pl) {
+        for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
-          for (int i = 0; i < FM; ++i) av[pl][i] = S[pl][wm0 + 16 * i + r][4 * ks + q];
+          for (int i = 0; i < FM; ++i) av[pl][i] = S[wm0 + 16 * i + r][4 * ks + q];
 #pragma unroll
-          for (int j = 0; j < FN; ++j) bv[pl][j] = S[pl][BM + wn0 + 16 * j + r][4 * ks + q];
+          for (int j = 0; j < FN; ++j) bv[pl][j] = S[BM + wn0 + 16 * j + r][4 * ks + q];
         }
-#define DR_W3(PA, PB)                                                                                   \
-  _Pragma("unroll") for (int i = 0; i < FM; ++i) _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = \
-      mfma_b16(av[PA][i], bv[PB][j], acc[i][j]);
-        if constexpr (TERMS == 3) {
-          DR_W3(2, 0)
-          DR_W3(1, 1)
-          DR_W3(0, 2)
-          DR_W3(1, 0)
-          DR_W3(0, 1)
-        }
-        DR_W3(0, 0)
-#undef DR_W3
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma_b16(av[0][i], bv[0][j], acc[i][j]);
       }
       __syncthreads();
       if (c + 1 < nch) {
@@ -1847,10 +1748,9 @@ __global__ __launch_bounds__(512) void k_wgrad_split3(int n, int lh, int lw, int
 // channels (4 float4 loads, 2 pixel pairs per channel, 8-byte LDS pieces), and
 // chunk c + 1 is loaded before and stored after chunk c's MFMAs into the other
 // buffer: one barrier per chunk, the split of one wave beside the MFMAs of its
-// SIMD partner.  Per split the products run over the same pixels in the same
-// order as the single-buffer kernel (its 64-pixel chunk = two 32-deep steps),
-// so the partial planes are bitwise the same.
-template <int BM, int TERMS, int BN, int KC>
+// SIMD partner.  Per split the products run over the pixels in 32-deep steps,
+// ascending, each step's six products smallest first.
+template <int BM, int BN, int KC>
 __global__ __launch_bounds__(512) void k_wgrad_split3_db(int n, int lh, int lw, int ca, int cb,
                                                          const float* __restrict__ lo, int lda,
                                                          const float* __restrict__ hi, int ldb, int chunk,
@@ -1858,7 +1758,7 @@ __global__ __launch_bounds__(512) void k_wgrad_split3_db(int n, int lh, int lw, 
   constexpr int RP = KC / 8 + 1, NQ = KC / 4;  // 16-byte units per row (+1 pad), pixel quartets per chunk
   constexpr int FM = BM / 32, FN = BN / 64;
   static_assert((KC == 32 || KC == 64) && FM >= 1 && FN >= 1, "wgrad_split3_db tile");
-  __shared__ __attribute__((aligned(16))) u32x4 S[2][TERMS][BM + BN][RP];
+  __shared__ __attribute__((aligned(16))) u32x4 S[2][3][BM + BN][RP];
   const int N = 16 * cb;
   const int tiles_n = N / BN, tiles = (ca / BM) * tiles_n;
   const int h = 1 << lh, w = 1 << lw, H2 = 2 * h, W2 = 2 * w;
@@ -1920,17 +1820,12 @@ __global__ __launch_bounds__(512) void k_wgrad_split3_db(int n, int lh, int lw, 
       if (!active[j]) continue;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        if constexpr (TERMS == 1) {
-          const u32x2 ph = {pack_bf16x2(v[j][0][c], v[j][1][c]), pack_bf16x2(v[j][2][c], v[j][3][c])};
-          reinterpret_cast<u32x2*>(&S[buf][0][row0[j] + c][0])[qt[j]] = ph;
-        } else {
-          unsigned h0, m0w, l0, h1, m1, l1;
-          split3_pair(v[j][0][c], v[j][1][c], h0, m0w, l0);
-          split3_pair(v[j][2][c], v[j][3][c], h1, m1, l1);
-          reinterpret_cast<u32x2*>(&S[buf][0][row0[j] + c][0])[qt[j]] = (u32x2){h0, h1};
-          reinterpret_cast<u32x2*>(&S[buf][1][row0[j] + c][0])[qt[j]] = (u32x2){m0w, m1};
-          reinterpret_cast<u32x2*>(&S[buf][2][row0[j] + c][0])[qt[j]] = (u32x2){l0, l1};
-        }
+        unsigned h0, m0w, l0, h1, m1, l1;
+        split3_pair(v[j][0][c], v[j][1][c], h0, m0w, l0);
+        split3_pair(v[j][2][c], v[j][3][c], h1, m1, l1);
+        reinterpret_cast<u32x2*>(&S[buf][0][row0[j] + c][0])[qt[j]] = (u32x2){h0, h1};
+        reinterpret_cast<u32x2*>(&S[buf][1][row0[j] + c][0])[qt[j]] = (u32x2){m0w, m1};
+        reinterpret_cast<u32x2*>(&S[buf][2][row0[j] + c][0])[qt[j]] = (u32x2){l0, l1};
       }
     }
   };
@@ -1952,9 +1847,9 @@ __global__ __launch_bounds__(512) void k_wgrad_split3_db(int n, int lh, int lw, 
       if (more) load(k_begin + (c + 1) * KC);
 #pragma unroll
       for (int ks = 0; ks < KC / 32; ++ks) {
-        u32x4 av[TERMS][FM], bv[TERMS][FN];
+        u32x4 av[3][FM], bv[3][FN];
 #pragma unroll
-        for (int pl = 0; pl < TERMS; ++pl) {
+        for (int pl = 0; pl < 3; ++pl) {
 #pragma unroll
           for (int i = 0; i < FM; ++i) av[pl][i] = S[buf][pl][wm0 + 16 * i + r][4 * ks + q];
 #pragma unroll
@@ -1963,13 +1858,12 @@ __global__ __launch_bounds__(512) void k_wgrad_split3_db(int n, int lh, int lw, 
 #define DR_W3(PA, PB)                                                                                   \
   _Pragma("unroll") for (int i = 0; i < FM; ++i) _Pragma("unroll") for (int j = 0; j < FN; ++j) acc[i][j] = \
       mfma_b16(av[PA][i], bv[PB][j], acc[i][j]);
-        if constexpr (TERMS == 3) {
-          DR_W3(2, 0)
-          DR_W3(1, 1)
-          DR_W3(0, 2)
-          DR_W3(1, 0)
-          DR_W3(0, 1)
-        }
+        // smallest terms first
+        DR_W3(2, 0)
+        DR_W3(1, 1)
+        DR_W3(0, 2)
+        DR_W3(1, 0)
+        DR_W3(0, 1)
         DR_W3(0, 0)
 #undef DR_W3
       }
@@ -2054,24 +1948,24 @@ int op_wgrad_split3(int n, int h, int w, int ca, int cb, const float* lo, int ld
   }
   const int tiles = (ca / bm) * (16 * cb / bn);
   const int lh = ilog2_exact(h), lw = ilog2_exact(w);
-#define DR_W3L(BM, T, ...)                                                                                     \
-  hipLaunchKernelGGL((k_wgrad_split3<BM, T, ##__VA_ARGS__>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, lh, lw, \
-                     ca, cb, lo, lda, hi, ldb, ch, ws)
+#define DR_W3L(BM, BN)                                                                                            \
+  hipLaunchKernelGGL((k_wgrad_s1<BM, BN>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, lh, lw, ca, \
+                     cb, lo, lda, hi, ldb, ch, ws)
   if (terms == 1) {
     if (bn == 512) {
-      DR_W3L(64, 1, 512);
+      DR_W3L(64, 512);
     } else if (bn == 256) {
-      if (bm == 128) DR_W3L(128, 1, 256);
-      else if (bm == 64) DR_W3L(64, 1, 256);
-      else DR_W3L(32, 1, 256);
+      if (bm == 128) DR_W3L(128, 256);
+      else if (bm == 64) DR_W3L(64, 256);
+      else DR_W3L(32, 256);
     } else {
-      if (bm == 128) DR_W3L(128, 1);
-      else if (bm == 64) DR_W3L(64, 1);
-      else DR_W3L(32, 1);
+      if (bm == 128) DR_W3L(128, 128);
+      else if (bm == 64) DR_W3L(64, 128);
+      else DR_W3L(32, 128);
     }
   } else {  // six products: the double-buffered kernel (WM step fp32 13.87 -> 13.82 ms, r06l)
 #define DR_W3D(BM, BN)                                                                                            \
-  hipLaunchKernelGGL((k_wgrad_split3_db<BM, 3, BN, 32>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, \
+  hipLaunchKernelGGL((k_wgrad_split3_db<BM, BN, 32>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, \
                      lh, lw, ca, cb, lo, lda, hi, ldb, ch, ws)
     if (bm == 128) DR_W3D(128, 128);
     else if (bn == 256) DR_W3D(64, 256);
@@ -2087,8 +1981,8 @@ int op_wgrad_split3(int n, int h, int w, int ca, int cb, const float* lo, int ld
 // Tall NT products, f32-accurate on the bf16 MFMA: Y[m][n] = act(sum_k A[m][k]
 // W[n][k] + bias[n]) for M in the thousands (the encoder feature projection
 // over B S / 2 frames, K = 4096; the critic's and the reward / continue heads'
-// first layers over B (H + 1) imagined states, K = Hd + L).  The k_conv_split3
-// pipeline with a row-major A (optional second K segment at ksA, k % 4
+// first layers over B (H + 1) imagined states, K = Hd + L).  k_conv_s1's
+// pipeline, six products per block, with a row-major A (optional second K segment at ksA, k % 4
 // aligned) in place of the im2col gather; W split once per call into planes
 // [K/32][3][Np][32] (Np = N rounded up to BN, zero rows past N).
 // ---------------------------------------------------------------------------

@@ -51,7 +51,7 @@ static void enc_carve(Carve& c, const dr_dims* d, int n, EncWs& w) {
   w.x0 = bf ? nullptr : c.f((long long)n * p0 * 4);
   for (int k = 0; k < N; ++k) w.a[k] = act((long long)n * (p0 >> (2 * (k + 1))) * e[k + 1]);
   // conv1 weights: f32 [cout][64] (k_conv1_frames) or three bf16 planes
-  // (k_enc12_split3, both modes; the bf16 repack of k_enc12_bf16 fits in it)
+  // (k_enc12_split3_x8 / k_enc12_s1; the bf16 repack of k_enc12_bf16 fits in it)
   w.wr[0] = (float*)c.raw((size_t)e[1] * 64 * 6);
   // conv2..N weights as three bf16 planes (op_conv_repack_split3, 6 bytes per
   // weight; the f32 / bf16 repacks of the fallbacks fit in the same slot)
@@ -96,7 +96,7 @@ static int encoder_bf16(const dr_dims* d, const dr_world_model* wm, const dr_fra
   }
   rj[nj++] = rj_bf16(d->enc_hidden, F, wm->map0.w, F + d->hidden, w.wproj);
   DR_TRY(op_repack_multi(rj, nj, s));
-  // conv1 + conv2: k_enc12_split3 with one term (64 x 64 from the u8 ring), else
+  // conv1 + conv2: k_enc12_s1, one bf16 term (64 x 64 from the u8 ring), else
   // k_enc12_bf16, else two launches
   // (DR_E_INVALID = shape / source not covered: next form; any other failure is returned)
   const int rc_s1 = e12 ? op_enc12_s1_bf16(n, B, h0, w0, e[1], e[2], src, wm->conv[0].w, wm->conv[0].b, wm->conv[1].w,
@@ -185,7 +185,9 @@ extern "C" int dr_encoder_features(const dr_dims* d, const dr_world_model* wm, c
   bool s3[DR_MAX_DEPTH + 1] = {};
   for (int k = e12 ? 2 : 1; k < N; ++k) {
     s3[k] = op_conv_split3_supported(n, e[k], h0 >> k, w0 >> k, e[k + 1]) && nj < DR_RJ_MAX - 1;
-    if (s3[k]) rj[nj++] = rj_conv(e[k + 1], e[k], wm->conv[k].w, w.wr[k]);
+    if (!s3[k]) continue;
+    DR_TRY(conv_bias_aligned(__func__, "conv", k, wm->conv[k].b));
+    rj[nj++] = rj_conv(e[k + 1], e[k], wm->conv[k].w, w.wr[k]);
   }
   if (s3p) rj[nj++] = rj_nt(d->enc_hidden, F, wm->map0.w, F + d->hidden, w.s3proj);
   DR_TRY(op_repack_multi(rj, nj, s));

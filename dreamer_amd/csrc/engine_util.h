@@ -36,6 +36,15 @@ struct Carve {
     }                                                                                      \
   } while (0)
 
+// The fp32 split-conv kernels (conv_glds.hip, k_convT_cls) read a layer's bias
+// as float4.  The callers check it where they route a layer there, before their
+// first launch (include/dreamer_hip.h, Conventions).
+static inline int conv_bias_aligned(const char* fn, const char* layer, int k, const float* b) {
+  if (((uintptr_t)b & 15) == 0) return DR_OK;
+  dr_set_error("%s: %s[%d].b must be 16-byte aligned (the layer runs on the fp32 split-conv kernels)", fn, layer, k);
+  return DR_E_INVALID;
+}
+
 // kernels, not hipMemcpy2DAsync / hipMemsetAsync: see op_fill in ops.hip
 static inline int copy2d(float* dst, long long dpitch, const float* src, long long spitch, long long width, long long rows,
                   hipStream_t s) {

@@ -2027,25 +2027,6 @@ static bool skinny_offsets_ok(const GemmArgs& g, bool b_kn) {
   return true;
 }
 
-// Microbenchmark A/B knobs (tools/kbench) exist only in the phase-timing
-// debug build; the product library has no process-wide mutable state here.
-#ifdef DR_PHASE_TIMING
-static size_t g_min_lds = 0;       // minimum dynamic LDS per skinny workgroup (bytes)
-static int g_skinny_variant = 0;   // 1 = 64-row tiles for M <= 64, 2 = never 32-column tiles, 5 = 64-row sampler tiles
-static int g_tile_wgs = 512;       // split-K target: workgroups per launch
-static int g_tile_variant = 0;     // tile-GEMM shape variant
-extern "C" void dr_debug_gemm_min_lds(long long bytes) { g_min_lds = (size_t)bytes; }
-extern "C" void dr_debug_skinny_variant(int v) { g_skinny_variant = v; }
-extern "C" void dr_debug_tile_wgs(int v) { g_tile_wgs = v > 0 ? v : 512; }
-extern "C" void dr_debug_tile_variant(int v) { g_tile_variant = v; }
-#else
-static constexpr size_t g_min_lds = 0;
-static constexpr int g_skinny_variant = 0;
-static constexpr int g_tile_wgs = 512;
-static constexpr int g_tile_variant = 0;
-#endif
-static size_t min_lds() { return g_min_lds; }
-
 // floats of dynamic LDS a skinny launch needs (mirrors the kernel's layout)
 template <int MT, int NT, int AMODE, bool B_KN>
 static size_t skinny_lds_floats(const GemmBatch& gb, int count, bool vec) {
@@ -2073,7 +2054,7 @@ static void launch_skinny(const GemmBatch& gb, int count, bool vec, hipStream_t 
     maxt = t > maxt ? t : maxt;
   }
   if (maxt == 0) return;
-  const size_t lds = std::max(skinny_lds_floats<MT, NT, AMODE, B_KN>(gb, count, vec) * sizeof(float), min_lds());
+  const size_t lds = skinny_lds_floats<MT, NT, AMODE, B_KN>(gb, count, vec) * sizeof(float);
   if (lds > 64 * 1024) {  // opt in to more than the default dynamic LDS (once per instantiation)
     static const bool raised = [] {
       (void)hipFuncSetAttribute((const void*)k_gemm_skinny<MT, NT, AMODE, B_KN, true, EPI>,
@@ -2103,7 +2084,7 @@ bool gemm_bwd_rows16(const GemmArgs* p, int count) {
     maxM = std::max(maxM, p[i].M);
     t16 += dr_cdiv(p[i].M, 16) * dr_cdiv(p[i].N, 16);
   }
-  return maxM <= 64 || (g_skinny_variant == 0 && maxM <= 4096 && t16 <= 640);
+  return maxM <= 64 || (maxM <= 4096 && t16 <= 640);
 }
 
 template <int AMODE, bool B_KN>
@@ -2122,16 +2103,12 @@ static bool try_skinny(const GemmBatch& gb, int count, hipStream_t s) {
   // fused row epilogues are validated for M <= 4096 (gemm_launch); plain
   // epilogues take any M the 32-bit offsets allow (64-row tiles past 64 rows)
   if (maxM > (epi == EPI_NONE ? (1 << 20) : 4096)) return false;
-  if (g_skinny_variant == 1 && maxM > 16) maxM = 65;
-  if (g_skinny_variant == 3) maxM = std::min(maxM, 64);  // 16-row tiles at any M
   // 16-row tiles past 64 rows while the grid stays within ~2.5 dispatch
   // rounds: a B = 256 per-step product (N = 200) then spreads over 208
   // workgroups instead of 52 (K = 1624: 19.3 -> 8.4 us, profiles/r02_kbench_B256.txt)
   // (also the staged LayerNorm- and softmax-STE-backward prologues:
   // at 64-row tiles a B = 256 LN-backward product ran on 52 workgroups, 16.5 us)
-  if ((g_skinny_variant == 0 || g_skinny_variant == 5) && maxM > 64 &&
-      (AMODE == AM_PLAIN || AMODE == AM_LNSILU || (AMODE == AM_LNBWD || AMODE == AM_STEBWD)) &&
-      !(g_skinny_variant == 5 && epi == EPI_SAMPLE)) {
+  if (maxM > 64 && (AMODE == AM_PLAIN || AMODE == AM_LNSILU || AMODE == AM_LNBWD || AMODE == AM_STEBWD)) {
     int t16 = 0;
     for (int i = 0; i < count; ++i) t16 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, epi == EPI_SAMPLE ? 32 : 16);
     if (t16 <= 640) maxM = 64;
@@ -2142,7 +2119,7 @@ static bool try_skinny(const GemmBatch& gb, int count, hipStream_t s) {
   int tiles16 = 0;
   for (int i = 0; i < count; ++i)
     tiles16 += dr_cdiv(gb.p[i].M, maxM > 64 ? 64 : 16) * dr_cdiv(gb.p[i].N, 16);
-  bool wide = g_skinny_variant != 2 && maxM <= 64 && tiles16 > 256;
+  bool wide = maxM <= 64 && tiles16 > 256;
   // the backward prologues exist only on the staged path (A and weight rows of
   // the tile in LDS, k_gemm_skinny `staged`): a tile whose rows do not fit
   // would read the raw operand.  At K = 1024 (the STE backward of a 32 x 32
@@ -2469,7 +2446,7 @@ static void launch_tile2(GemmBatch& gb, int count, hipStream_t s) {
   if (ws) {
     // about two workgroups per CU over the problems' real tiles (the grid's
     // surplus blocks of the smaller problems exit at once)
-    splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(g_tile_wgs, tot)));
+    splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(512, tot)));
     splits = std::min(splits, std::max(1, nch / 2));  // at least 2 chunks per split
     for (int i = 0; i < count; ++i)
       while (splits > 1 && (long long)splits * gb.p[i].M * gb.p[i].N > gb.p[i].splitk_floats) --splits;
@@ -2585,38 +2562,18 @@ static void launch_wks3(const GemmBatch& gb, int count, hipStream_t s, bool bf16
   else hipLaunchKernelGGL((k_gemm_wks3<3, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM>), grid, blk, 0, s, gb, npack);
 }
 
-// split-K over workgroups only when the tile grid is under one workgroup per
-// CU and every problem brought scratch for it
-template <int BM, int BN, int NW, int D, int KMAP = 0>
-static void launch_wk(GemmBatch& gb, int count, hipStream_t s, int target = 256) {
-  int maxt = 0, tot = 0, nkb = 1 << 30;
-  long long maxMN = 0;
-  bool ws = true;
+// the wave-K chain kernel on 32 x 32 tiles, 4 waves, ring depth 2, no split-K
+static void launch_wk(const GemmBatch& gb, int count, hipStream_t s) {
+  int maxt = 0, tot = 0;
   for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    const int t = dr_cdiv(g.M, BM) * dr_cdiv(g.N, BN);
+    const int t = dr_cdiv(gb.p[i].M, 32) * dr_cdiv(gb.p[i].N, 32);
     maxt = std::max(maxt, t);
     tot += t;
-    nkb = std::min(nkb, dr_cdiv(g.K, 32));
-    maxMN = std::max(maxMN, (long long)g.M * g.N);
-    ws = ws && g.splitk_ws != nullptr;
   }
   if (maxt == 0) return;
-  int splits = 1;
-  if (ws && tot < target) {
-    splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(target, tot)));
-    splits = std::min(splits, std::max(1, nkb / (2 * NW)));  // at least 2 blocks per wave
-    for (int i = 0; i < count; ++i)
-      while (splits > 1 && (long long)splits * gb.p[i].M * gb.p[i].N > gb.p[i].splitk_floats) --splits;
-  }
-  if (count > 1)
-    hipLaunchKernelGGL((k_gemm_wk<BM, BN, NW, D, KMAP>), dim3(dr_xcd_grid(tot), splits, 1), dim3(64 * NW), 0, s, gb,
-                       splits, count);
-  else
-    hipLaunchKernelGGL((k_gemm_wk<BM, BN, NW, D, KMAP>), dim3(dr_xcd_grid(maxt), splits, 1), dim3(64 * NW), 0, s, gb,
-                       splits, 0);
-  if (splits > 1)
-    hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)((maxMN + 255) / 256), 1, count), dim3(256), 0, s, gb, splits);
+  const int npack = count > 1 ? count : 0;
+  hipLaunchKernelGGL((k_gemm_wk<32, 32, 4, 2, 1>), dim3(dr_xcd_grid(npack ? tot : maxt), 1, 1), dim3(256), 0, s, gb, 1,
+                     npack);
 }
 
 // every problem bf16 and 16-byte-aligned 8-wide k runs (ksplitA on an 8 boundary)
@@ -2706,53 +2663,26 @@ static int launch_pick(const GemmBatch& gb, int count, hipStream_t s) {
     // problems, split-K 4), profiles/r02h_kbench_tile_B256.txt
     // shallow-K products the caller gave weight planes (the BPTT's actor
     // input gradient, K = 200, N = 1624): the wave-K split3 kernel
-    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512 && minK < 512 && g_tile_variant == 0 &&
-        wks3_ok(gb, count)) {
+    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512 && minK < 512 && wks3_ok(gb, count)) {
       launch_wks3(gb, count, s, b16_ok(gb, count));
       return DR_OK;
     }
-    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512 && g_tile_variant != 26) {
+    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512) {
       int tiles32 = 0;
       for (int i = 0; i < count; ++i) tiles32 += dr_cdiv(gb.p[i].M, 32) * dr_cdiv(gb.p[i].N, 32);
       // (f32 under ~112 tiles -- one per-step Linear of 200 outputs, K = 1624 --
       // the 16-row skinny tiles spread wider: 8.4 against 13.0 us)
-      if ((g_tile_variant == 0 || g_tile_variant >= 8) && maxM <= 512 &&
-          ((minK >= 1024 && (tiles32 >= 112 || g_tile_variant != 0 || b16_ok(gb, count))) ||
-           (minK >= 512 && tiles32 >= 256))) {
+      if ((minK >= 1024 && (tiles32 >= 112 || b16_ok(gb, count))) || (minK >= 512 && tiles32 >= 256)) {
         GemmBatch gt = gb;
         if (tiles32 >= 256)
           for (int i = 0; i < count; ++i) gt.p[i].splitk_ws = nullptr;
         // f32: the wave-K kernel (32 x 32 tiles, 4 waves, no split-K: heads
         // 15.8 -> 13.0 us, BPTT 32.2 -> 25.7, GRU hidden product 13.3 -> 12.3,
         // profiles/r03g_kbench_wk.txt); the LDS tile kernel stays for the
-        // shapes the wave-K kernel does not take (and as kbench variant 25)
+        // shapes the wave-K kernel does not take
         if (wks3_ok(gb, count)) launch_wks3(gt, count, s, b16_ok(gb, count));
         else if (b16_ok(gb, count)) launch_tile_b16<32, 32, 4>(gt, count, s);
-        else if (g_tile_variant == 0 && wk_ok(gb, count)) launch_wk<32, 32, 4, 2, 1>(gt, count, s, 0);
-        else if (g_tile_variant >= 12 && g_tile_variant < 25 && wk_ok(gb, count)) {
-          GemmBatch gw = gb;  // (split-K scratch kept: launch_wk splits only under 256 tiles)
-          switch (g_tile_variant) {
-            case 12: launch_wk<32, 32, 4, 4>(gw, count, s); break;
-            case 13: launch_wk<32, 32, 8, 4>(gw, count, s); break;
-            case 14: launch_wk<64, 32, 8, 3>(gw, count, s); break;
-            case 15: launch_wk<32, 64, 8, 3>(gw, count, s); break;
-            case 16: launch_wk<32, 32, 4, 4, 1>(gw, count, s); break;
-            case 18: launch_wk<32, 32, 4, 2>(gw, count, s); break;
-            case 19: launch_wk<32, 32, 4, 2, 1>(gw, count, s); break;
-            case 20: launch_wk<32, 32, 8, 2, 1>(gw, count, s); break;
-            case 21: launch_wk<64, 64, 4, 2, 1>(gw, count, s, g_tile_wgs); break;
-            case 22: launch_wk<64, 32, 4, 2, 1>(gw, count, s, g_tile_wgs); break;
-            case 23: launch_wk<32, 64, 4, 2, 1>(gw, count, s, g_tile_wgs); break;
-            case 24: launch_wk<64, 64, 8, 2, 1>(gw, count, s, g_tile_wgs); break;
-            default:
-              if (tiles32 >= 256) launch_wk<32, 32, 4, 4>(gw, count, s);
-              else launch_wk<32, 32, 8, 4>(gw, count, s);
-              break;
-          }
-        } else if (g_tile_variant == 8) launch_tile2<32, 64, 64, false, false, 4>(gt, count, s);
-        else if (g_tile_variant == 9) launch_tile2<64, 32, 64, false, false, 4>(gt, count, s);
-        else if (g_tile_variant == 10) launch_tile2<64, 64, 64, false, false, 4>(gt, count, s);
-        else if (g_tile_variant == 11) launch_tile2<32, 64, 32, false, false, 4>(gt, count, s);
+        else if (wk_ok(gb, count)) launch_wk(gt, count, s);
         else launch_tile2<32, 32, 64, false, false, 4>(gt, count, s);
         return DR_OK;
       }
@@ -2764,28 +2694,18 @@ static int launch_pick(const GemmBatch& gb, int count, hipStream_t s) {
     // decoder's layers over B (T - 1) rows, the critic's over B (H + 1)): the
     // 64-row skinny tiles re-read the weights per row tile and run 16 columns
     // per workgroup (480 us for the decoder's 3584 x 4096 x 200 product)
-    const bool tall = !A_KM && !B_KN && maxM >= 1024 && tiles >= 256 && g_tile_variant == 0;
-    if (A_KM || (maxM >= 256 && minK >= 512 && (ws || tiles >= 128) && g_tile_variant != 26) || tall ||
-        (g_tile_variant >= 4 && g_tile_variant < 26 && maxM >= 128)) {
+    const bool tall = !A_KM && !B_KN && maxM >= 1024 && tiles >= 256;
+    if (A_KM || (maxM >= 256 && minK >= 512 && (ws || tiles >= 128)) || tall) {
       GemmBatch gt = gb;
       // tall NT products with a deep K (the encoder feature projection, the
       // critic's first layer over B*(H+1) rows): 8 waves as 4 x 2 over 64 x 64
       // with K chunks of 64 -- 198 -> 171 us (M 8192, K 4096), 51 -> 47 us
       // (M 4096, K 1624), profiles/r02m_kbench_tall_tiles.txt
-      if (g_tile_variant == 0 && !A_KM && !B_KN && minK >= 1024) {
+      if (!A_KM && !B_KN && minK >= 1024) {
         if (b16_ok(gb, count)) launch_tile_b16<64, 64, 8>(gt, count, s);
         else launch_tile2<64, 64, 64, false, false, 8>(gt, count, s);
-        return DR_OK;
-      }
-      switch (g_tile_variant) {
-        case 1: launch_tile2<64, 64, 64, A_KM, B_KN>(gt, count, s); break;
-        case 2: launch_tile2<128, 64, 32, A_KM, B_KN>(gt, count, s); break;
-        case 3: launch_tile2<128, 64, 64, A_KM, B_KN>(gt, count, s); break;
-        case 4: launch_tile2<64, 32, 64, A_KM, B_KN, 8>(gt, count, s); break;
-        case 5: launch_tile2<128, 32, 64, A_KM, B_KN, 8>(gt, count, s); break;
-        case 6: launch_tile2<64, 64, 64, A_KM, B_KN, 8>(gt, count, s); break;
-        case 7: launch_tile2<32, 32, 64, A_KM, B_KN, 4>(gt, count, s); break;
-        default: launch_tile2<64, 64, 32, A_KM, B_KN>(gt, count, s); break;
+      } else {
+        launch_tile2<64, 64, 32, A_KM, B_KN>(gt, count, s);
       }
       return DR_OK;
     }
@@ -2822,12 +2742,6 @@ static bool ln_sample_ok(const GemmArgs& g) {
          (long long)g.M * g.ldz < (1LL << 31) && aligned16(g.z_out) && g.ldz % 4 == 0 &&
          (!g.soft_out || (aligned16(g.soft_out) && g.ld_soft % 4 == 0)) && (!g.noise.q || aligned16(g.noise.q));
 }
-#ifdef DR_PHASE_TIMING
-static int g_ln_sample_off = 0;  // kbench A/B: 1 = the skinny kernel's sampler epilogue instead
-extern "C" void dr_debug_ln_sample_off(int v) { g_ln_sample_off = v; }
-#else
-static constexpr int g_ln_sample_off = 0;
-#endif
 
 template <int NK>
 static int launch_ln_sample_nk(const GemmArgs& g, hipStream_t s) {
@@ -2947,7 +2861,7 @@ int gemm_launch(GemmLayout lay, int amode, const GemmArgs* probs, int count, hip
     }
     return gemm_launch(G_NT, AM_PLAIN, pp, count, s);
   }
-  if (lay == G_NT && amode == AM_LNSILU && count == 1 && !g_ln_sample_off && ln_sample_ok(probs[0]))
+  if (lay == G_NT && amode == AM_LNSILU && count == 1 && ln_sample_ok(probs[0]))
     return launch_ln_sample(probs[0], s);
   for (int i = 0; i < count; ++i) {
     const GemmArgs& g = probs[i];

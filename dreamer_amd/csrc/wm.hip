@@ -659,6 +659,12 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
   WS_CHECK(c, ws_bytes);
   const int M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, nb = D.nb, F = D.F, R = d->rows;
   const int IH = D.IH, IW = D.IW, N = D.N;
+  if (D.terms == 3) {  // the biases of the layers routed to the six-product kernels (forward and backward)
+    for (int k = 0; k < N; ++k) {
+      if (w.s3e[k]) DR_TRY(conv_bias_aligned(__func__, "conv", k, wm->conv[k].b));
+      if (w.t3d[k]) DR_TRY(conv_bias_aligned(__func__, "convt", k, dec->convt[k].b));
+    }
+  }
   const float* hB = w.h_all + (long long)B * Hd;
   const float* zB = w.z_all + (long long)B * L;
   float* gHB = w.gH + (long long)B * Hd;
@@ -742,7 +748,7 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
   // (conv1's weight gradient reads it; pad channel = 1: its bias gradient comes
   // out of the same product, enc_bias_fused below)
   DR_TRY(op_frames_nhwc4(M, B, IH, IW, src, w.x0, s, 1.0f));
-  // conv1 + conv2 in one kernel from the u8 ring (k_enc12_split3) with the
+  // conv1 + conv2 in one kernel from the u8 ring (k_enc12_split3_x8; bf16 mode: k_enc12_s1) with the
   // backward's saves; other shapes / sources take the per-layer kernels
   int k0 = 0;
   if (N >= 2 && w.e12w1 && w.s3e[1]) {

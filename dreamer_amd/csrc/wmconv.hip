@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_convT_nhwc(ConvTArgs a) {
   const long long tiles_m = (M + BM - 1) / BM;
   const int lt = dr_xcd_tile(blockIdx.x, (int)(4 * tiles_m * tiles_n));
   if (lt < 0) return;
-  // parity class fastest (as k_convT_split3): the four classes of a pixel
+  // parity class fastest (as k_convT_s1): the four classes of a pixel
   // tile share an XCD's L2 and read their common input from HBM about once
   const int cls = lt & 3;
   const long long rem = lt >> 2;

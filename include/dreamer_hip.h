@@ -19,6 +19,13 @@
  *    whole train_Agent epoch can be captured into one hipGraph.
  *  - parameters are read in PyTorch's own layouts (Linear weight [out][in],
  *    GRUCell weight_ih [3H][in] gate order r,z,n, Conv2d [out][in][4][4]).
+ *  - fp32 mode: the bias of a Conv2d / ConvTranspose2d layer whose shape runs on
+ *    the split-conv kernels (32 / 64 / 128 / 256 input channels, a multiple of
+ *    64 output channels -- 64 -> 32 for a transposed conv too) must be 16-byte
+ *    aligned.  dr_encoder_features and the world-model training step return
+ *    DR_E_INVALID, nothing launched, when it is not; dr_last_error() names the
+ *    pointer.  (A tensor from the PyTorch allocator always is; a view at an
+ *    offset that is no multiple of 4 floats is not.)
  *  - arithmetic is fp32 (parity mode) unless dr_dims.precision selects bf16:
  *    fp32 GEMMs use the exact-f32 MFMA (v_mfma_f32_16x16x4_f32), elementwise
  *    code is built -ffp-contract=off; bf16 mode runs the encoder convolutions

@@ -541,3 +541,45 @@ def test_act_step_error_codes(gpu, monkeypatch):
     torch.cuda.synchronize()
     assert ei.value.code == L.DR_E_UNSUPPORTED
     assert str(ei.value).split("): ", 1)[1].startswith("dr_act_step:"), str(ei.value)
+
+
+def test_conv_bias_alignment_is_an_error(gpu):
+    """fp32 dr_encoder_features, FULL widths, one frame: conv3 (64 -> 128
+    channels) runs on the split-conv kernels, which read the bias as float4.  A
+    conv[2].b that points 4 bytes into a copy of the bias is DR_E_INVALID with a
+    message that names the alignment, decided before anything is launched; the
+    aligned copy then gives the untouched call's features bit for bit."""
+    from dreamer_amd import _lib as L
+    from dreamer_amd import hip
+    d, _ = _dreamer(gpu)
+    wm = d.world_model
+    dims = wm.dims(d.agent)
+    g = torch.Generator().manual_seed(2)
+    frames = torch.randint(0, 256, (1, 3, 64, 64), generator=g, dtype=torch.uint8).to(gpu)
+    starts = torch.zeros(1, dtype=torch.int64, device=gpu)
+    fr = L.dr_frames(L.ptr(frames), 1, L.ptr(starts), None, 0, 0, 1, 0)
+    ws = torch.empty(L.query("dr_encoder_workspace_bytes", dims, 1), dtype=torch.uint8, device=gpu)
+
+    def features(model):
+        feat = torch.full((1, dims.enc_hidden), float("nan"), device=gpu)
+        L.call("dr_encoder_features", dims, model, fr, 1, 1, L.ptr(feat), L.ptr(ws), ws.numel(), hip.stream())
+        torch.cuda.synchronize()
+        return feat
+
+    ref = features(wm.packed())
+    assert torch.isfinite(ref).all()
+    bias = wm.encoder.feature_extractor[4].bias.detach()
+    shifted = torch.zeros(bias.numel() + 4, device=gpu)  # a fresh allocation is 16-byte aligned
+    shifted[1:1 + bias.numel()] = bias
+    assert shifted.data_ptr() % 16 == 0
+    torch.cuda.synchronize()
+    bad = wm.packed()
+    bad.conv[2].b = shifted.data_ptr() + 4
+    with pytest.raises(L.HipError) as ei:
+        features(bad)
+    assert ei.value.code == L.DR_E_INVALID
+    assert "align" in str(ei.value) and "conv[2].b" in str(ei.value), str(ei.value)
+    good = wm.packed()
+    aligned = bias.clone()
+    good.conv[2].b = aligned.data_ptr()
+    assert torch.equal(features(good), ref)

@@ -1,10 +1,9 @@
-"""Phase table and timing of the fp32 conv1 + conv2 kernel (k_enc12_split3*):
+"""Phase table and timing of the fp32 conv1 + conv2 kernel (k_enc12_split3_x8):
 dr_encoder_features over 8192 synthetic 64x64 frames (one train_Agent epoch's
 warm-start frames at B = 256, S = 64).  Prints ms per encode, a sha256 of the
 features (two library variants whose sums are bitwise the same print the same)
-and, with a timestamp build (tools/build_e12_ts.sh; DREAMER_LIB_VARIANT=e12ts
-for the product schedule, e12ts_r3 for the round-3 one), us per phase of the
-first tiles of the first workgroups, for wave 0 and wave 4.
+and, with the timestamp build (tools/build_e12_ts.sh, DREAMER_LIB_VARIANT=e12ts),
+us per phase of the first tiles of the first workgroups, for wave 0 and wave 4.
   DREAMER_LIB_VARIANT=e12ts python tools/enc12_probe.py      (GPU box)"""
 import ctypes as C
 import hashlib
@@ -18,11 +17,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 WGS, TILES, MARKS = 4, 4, 8  # E12_TS_* of conv_split.hip
-PHASES = {
-    # marks 0..6 of the product schedule / of the round-3 schedule
-    "e12ts": ["conv1", "barrier", "conv2", "exchange", "staging", "epilogue"],
-    "e12ts_r3": ["conv1", "barrier", "conv2", "reduce", "epilogue", "staging"],
-}
+PHASES = ["conv1", "barrier", "conv2", "exchange", "staging", "epilogue"]  # between marks 0..6
 
 
 def main():
@@ -62,7 +57,7 @@ def main():
     buf = (C.c_longlong * (WGS * TILES * 2 * MARKS))()
     if lib.dr_e12_ts_read(buf) != 0:
         raise RuntimeError("dr_e12_ts_read failed")
-    names = PHASES.get(var, [f"mark {k}-{k + 1}" for k in range(6)])
+    names = PHASES
     us = lambda a, b: (b - a) / 100.0  # 100 MHz constant clock
     print("us per phase (workgroup, tile ordinal, wave): " + " ".join(f"{p:>9}" for p in names) + "    period")
     tot = [[0.0] * 7 for _ in range(2)]

@@ -18,11 +18,6 @@ static const char* g_filter = nullptr;
 static int g_reps = 200;
 extern "C" int dr_debug_tbuf_gru(long long* out, int n);
 extern "C" int dr_debug_tbuf_gemm(long long* out, int n);
-extern "C" void dr_debug_tile_variant(int v);
-extern "C" void dr_debug_skinny_variant(int v);
-extern "C" void dr_debug_tile_wgs(int v);
-extern "C" void dr_debug_gates_batch(int v);
-extern "C" void dr_debug_ln_sample_off(int v);
 
 // one more launch, then the per-phase times of wave 0 of each workgroup
 // (relative to its own start) averaged over the workgroups that wrote them
@@ -332,21 +327,17 @@ int main(int argc, char** argv) {
   GruArgs gs = ga;
   gs.sr = save; gs.su = save + B * Hd; gs.sn = save + 2 * B * Hd; gs.sghn = save + 3 * B * Hd;
   timeit("gru_fused B64 H600 R32 (saves)", [&](hipStream_t st) { op_gru_fused(gs, st); }, s);
-  {  // split path (tile-GEMM hidden product + gather/gates kernel) by gather batch
+  {  // split path (tile-GEMM hidden product + gather/gates kernel)
     float* ghw = frand((size_t)B * 3 * Hd);
-    for (int gbv : {4, 8, 16, 32}) {
-      dr_debug_gates_batch(gbv);
-      GruArgs gsp = gs;
-      gsp.gh_ws = ghw;
-      char nm[96];
-      snprintf(nm, sizeof nm, "gru split B%d (saves) gather batch %d", B, gbv);
-      timeit(nm, [&](hipStream_t st) { op_gru_fused(gsp, st); }, s);
-      GruArgs gz = gsp;
-      gz.h = nullptr;  // gates kernel alone (no hidden product)
-      snprintf(nm, sizeof nm, "gru split B%d gates only, batch %d", B, gbv);
-      timeit(nm, [&](hipStream_t st) { op_gru_fused(gz, st); }, s);
-    }
-    dr_debug_gates_batch(8);
+    GruArgs gsp = gs;
+    gsp.gh_ws = ghw;
+    char nm[96];
+    snprintf(nm, sizeof nm, "gru split B%d (saves)", B);
+    timeit(nm, [&](hipStream_t st) { op_gru_fused(gsp, st); }, s);
+    GruArgs gz = gsp;
+    gz.h = nullptr;  // gates kernel alone (no hidden product)
+    snprintf(nm, sizeof nm, "gru split B%d gates only", B);
+    timeit(nm, [&](hipStream_t st) { op_gru_fused(gz, st); }, s);
   }
   GruArgs gn = ga;
   gn.h = nullptr;
@@ -405,101 +396,50 @@ int main(int argc, char** argv) {
     timeit("unfused 2x lnsilu M64 200-200-1024", [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &g1, 1, st);
                                                                        gemm_launch(G_NT, AM_LNSILU, &g2, 1, st); }, s);
   }
-  // B = 256 chain products: current routing (variant 0) against the 8-wave
-  // tile variants, without and with split-K scratch
+  // B = 256 chain products on the product route, without and with split-K scratch
   {
     float* skw = frand((size_t)8 * 256 * 2048);
-    // correctness of the wave-K variants against variant 0 (same inputs, own outputs)
-    if (!g_filter || strstr("tv check", g_filter) || strstr(g_filter, "tv")) {
-      float* Yc = frand((size_t)3 * B * 2048);
-      auto run_shapes = [&](int var, std::vector<float>& out) {
-        dr_debug_tile_variant(var);
-        CK(hipMemset(Yc, 0, (size_t)3 * B * 2048 * 4));
-        GemmArgs a = nt_(B, 1027, 1800), b = nt_(B, 600, 1800);
-        a.Y = Yc; a.ldy = 1027; b.Y = Yc + (size_t)B * 1027; b.ldy = 600;
-        GemmArgs p2[2] = {a, b};
-        gemm_launch(G_NT, AM_PLAIN, p2, 2, s);
-        GemmArgs h3[3];
-        for (int i = 0; i < 3; ++i) {
-          h3[i] = nt_(B, 200, 1624);
-          h3[i].A = X; h3[i].lda = 600; h3[i].ksplitA = 600; h3[i].A2 = X + 700000; h3[i].lda2 = 1024;
-          h3[i].W = W + 100 * i; h3[i].Y = Yc + (size_t)B * 1627 + (size_t)B * 200 * i; h3[i].ldy = 200;
-          h3[i].splitk_ws = skw + (size_t)i * 1024 * 1024; h3[i].splitk_floats = 1024LL * 1024;
-        }
-        gemm_launch(G_NT, AM_PLAIN, h3, 3, s);
-        GemmArgs gg = nt_(B, 1800, 600);
-        gg.Y = Yc + (size_t)B * 2227; gg.ldy = 1800;
-        gemm_launch(G_NT, AM_PLAIN, &gg, 1, s);
-        CK(hipStreamSynchronize(s));
-        out.resize((size_t)B * 4027);
-        CK(hipMemcpy(out.data(), Yc, out.size() * 4, hipMemcpyDeviceToHost));
+    for (int sk = 0; sk < 2; ++sk) {
+      auto prep = [&](GemmArgs g) {
+        if (sk) { g.splitk_ws = skw; g.splitk_floats = 8LL * 256 * 2048; }
+        return g;
       };
-      std::vector<float> ref, got;
-      run_shapes(0, ref);
-      for (int var : {19, 25}) {
-        run_shapes(var, got);
-        const size_t cut[4] = {0, (size_t)B * 1627, (size_t)B * 2227, (size_t)B * 4027};
-        for (int rg = 0; rg < 3; ++rg) {
-          double md = 0, mr = 0;
-          for (size_t i = cut[rg]; i < cut[rg + 1]; ++i) {
-            md = std::max(md, (double)fabsf(got[i] - ref[i]));
-            mr = std::max(mr, (double)fabsf(ref[i]));
-          }
-          printf("tv%d check vs tv0 (%s): max|d| %.3e (max|ref| %.3e)\n", var, rg == 0 ? "BPTT" : rg == 1 ? "heads" : "GRU", md, mr);
-        }
-      }
-      dr_debug_tile_variant(0);
+      GemmArgs s1[2] = {prep(nt_(B, 1027, 1800)), prep(nt_(B, 600, 1800))};
+      snprintf(buf, sizeof buf, "chain%s BPTT gZ+gH N1027+600 K1800", sk ? " sk" : "");
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, s1, 2, st); }, s);
+      GemmArgs s2[3] = {prep(nt_(B, 200, 1624)), prep(nt_(B, 200, 1624)), prep(nt_(B, 200, 1624))};
+      snprintf(buf, sizeof buf, "chain%s heads L1 3x N200 K1624", sk ? " sk" : "");
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, s2, 3, st); }, s);
+      GemmArgs s3 = prep(nt_(B, 1800, 600));
+      snprintf(buf, sizeof buf, "chain%s GRU gh N1800 K600", sk ? " sk" : "");
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s3, 1, st); }, s);
+      GemmArgs s5 = prep(nt_(B, 200, 1624));
+      snprintf(buf, sizeof buf, "chain%s actor L1 1x N200 K1624", sk ? " sk" : "");
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s5, 1, st); }, s);
+      GemmArgs s4 = prep(nt_(B, 200, 600));
+      snprintf(buf, sizeof buf, "chain%s prior L1 N200 K600", sk ? " sk" : "");
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s4, 1, st); }, s);
     }
-    for (int var : {0, 13, 20, 25, 26}) {
-      dr_debug_tile_variant(var);
-      for (int sk = 0; sk < 2; ++sk) {
-        if ((var >= 8 && var < 12) && sk) continue;
-        auto prep = [&](GemmArgs g) {
-          if (sk) { g.splitk_ws = skw; g.splitk_floats = 8LL * 256 * 2048; }
-          return g;
-        };
-        GemmArgs s1[2] = {prep(nt_(B, 1027, 1800)), prep(nt_(B, 600, 1800))};
-        snprintf(buf, sizeof buf, "tv%d%s BPTT gZ+gH N1027+600 K1800", var, sk ? " sk" : "");
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, s1, 2, st); }, s);
-        GemmArgs s2[3] = {prep(nt_(B, 200, 1624)), prep(nt_(B, 200, 1624)), prep(nt_(B, 200, 1624))};
-        snprintf(buf, sizeof buf, "tv%d%s heads L1 3x N200 K1624", var, sk ? " sk" : "");
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, s2, 3, st); }, s);
-        GemmArgs s3 = prep(nt_(B, 1800, 600));
-        snprintf(buf, sizeof buf, "tv%d%s GRU gh N1800 K600", var, sk ? " sk" : "");
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s3, 1, st); }, s);
-        GemmArgs s5 = prep(nt_(B, 200, 1624));
-        snprintf(buf, sizeof buf, "tv%d%s actor L1 1x N200 K1624", var, sk ? " sk" : "");
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s5, 1, st); }, s);
-        GemmArgs s4 = prep(nt_(B, 200, 600));
-        snprintf(buf, sizeof buf, "tv%d%s prior L1 N200 K600", var, sk ? " sk" : "");
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &s4, 1, st); }, s);
-      }
-    }
-    dr_debug_tile_variant(0);
   }
   // tall products: the encoder feature projection (M = B*S/2 frames, K = 4096)
-  // and the critic's first layer over B*(H+1) rows, by tile variant
+  // and the critic's first layer over B*(H+1) rows
   {
     float* Xb = frand((size_t)8192 * 4096);
     float* Wb = frand((size_t)256 * 4096);
     float* Yb = frand((size_t)8192 * 256);
     float* skw = frand((size_t)4 * 8192 * 256);
-    for (int var : {0, 4, 5, 6, 7}) {
-      dr_debug_tile_variant(var);
-      int shp[][3] = {{8192, 200, 4096}, {4096, 200, 1624}, {2048, 200, 4096}};
-      for (auto& sh : shp) {
-        GemmArgs g = gemm_args();
-        g.M = sh[0]; g.N = sh[1]; g.K = sh[2]; g.A = Xb; g.lda = sh[2]; g.ksplitA = sh[2]; g.W = Wb; g.ldb = sh[2];
-        g.bias = bias; g.Y = Yb; g.ldy = sh[1];
-        g.splitk_ws = skw; g.splitk_floats = 4LL * 8192 * 256;
-        snprintf(buf, sizeof buf, "tw%d NT M%d N%d K%d (split-K scratch)", var, sh[0], sh[1], sh[2]);
-        timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &g, 1, st); }, s);
-      }
+    int shp[][3] = {{8192, 200, 4096}, {4096, 200, 1624}, {2048, 200, 4096}};
+    for (auto& sh : shp) {
+      GemmArgs g = gemm_args();
+      g.M = sh[0]; g.N = sh[1]; g.K = sh[2]; g.A = Xb; g.lda = sh[2]; g.ksplitA = sh[2]; g.W = Wb; g.ldb = sh[2];
+      g.bias = bias; g.Y = Yb; g.ldy = sh[1];
+      g.splitk_ws = skw; g.splitk_floats = 4LL * 8192 * 256;
+      snprintf(buf, sizeof buf, "tall NT M%d N%d K%d (split-K scratch)", sh[0], sh[1], sh[2]);
+      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &g, 1, st); }, s);
     }
-    dr_debug_tile_variant(0);
   }
   // the prior head's last layer with the sampler epilogue (LN-SiLU prologue,
-  // N = 1024 = 32 groups x 32 classes): default 16-row tiles vs 64-row tiles
+  // N = 1024 = 32 groups x 32 classes) on the sampler-head kernel (k_ln_gemm_sample)
   {
     unsigned long long* rng;
     CK(hipMalloc(&rng, 16));
@@ -507,55 +447,42 @@ int main(int argc, char** argv) {
     float* zo = frand((size_t)B * 1024);
     int* io;
     CK(hipMalloc(&io, (size_t)B * 32 * 8));
-    for (int var : {0, 1, 5}) {
-      // 0: the dedicated sampler-head kernel (k_ln_gemm_sample); 1 / 5: the skinny kernel's
-      // sampler epilogue with 16-row (default) / 64-row tiles
-      dr_debug_ln_sample_off(var != 0);
-      dr_debug_skinny_variant(var == 5 ? 5 : 0);
-      GemmArgs g = nt_(B, 1024, 200);
-      g.ln_g = lng; g.ln_b = lnb;
-      g.epi = EPI_SAMPLE; g.R = 32; g.C = 32; g.unimix = 0.01f / 32;
-      g.noise.rng = rng; g.noise.stream = 7;
-      g.z_out = zo; g.ldz = 1024; g.idx_out = io; g.zval_out = reinterpret_cast<float*>(io + B * 32);
-      g.soft_out = Y; g.ld_soft = 1024; g.Y = nullptr;
-      snprintf(buf, sizeof buf, "ts%d sampler lnsilu M%d N1024 K200", var, B);
-      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &g, 1, st); }, s);
-      phases(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &g, 1, st); }, dr_debug_tbuf_gemm, s);
-      GemmArgs gn = g;
-      gn.epi = EPI_NONE; gn.Y = Y; gn.ldy = 1024;
-      snprintf(buf, sizeof buf, "ts%d same, plain epilogue", var);
-      timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &gn, 1, st); }, s);
-      phases(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &gn, 1, st); }, dr_debug_tbuf_gemm, s);
-    }
-    dr_debug_skinny_variant(0);
-    dr_debug_ln_sample_off(0);
+    GemmArgs g = nt_(B, 1024, 200);
+    g.ln_g = lng; g.ln_b = lnb;
+    g.epi = EPI_SAMPLE; g.R = 32; g.C = 32; g.unimix = 0.01f / 32;
+    g.noise.rng = rng; g.noise.stream = 7;
+    g.z_out = zo; g.ldz = 1024; g.idx_out = io; g.zval_out = reinterpret_cast<float*>(io + B * 32);
+    g.soft_out = Y; g.ld_soft = 1024; g.Y = nullptr;
+    snprintf(buf, sizeof buf, "sampler lnsilu M%d N1024 K200", B);
+    timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &g, 1, st); }, s);
+    phases(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &g, 1, st); }, dr_debug_tbuf_gemm, s);
+    GemmArgs gn2 = g;
+    gn2.epi = EPI_NONE; gn2.Y = Y; gn2.ldy = 1024;
+    snprintf(buf, sizeof buf, "same, plain epilogue");
+    timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &gn2, 1, st); }, s);
+    phases(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &gn2, 1, st); }, dr_debug_tbuf_gemm, s);
   }
-  // per-step shapes of the imagination / BPTT chain, both row-tile variants
-  for (int var = 0; var < 5; ++var) {
-    if (var == 1 || var == 2) continue;
-    dr_debug_skinny_variant(var);
+  // per-step shapes of the imagination / BPTT chain
+  {
     int sh2[][3] = {{B, 1027, 1800}, {B, 600, 1800}, {B, 200, 1624}, {B, 1024, 200}, {B, 200, 1024}, {B, 200, 600}};
     for (auto& sh : sh2) {
       GemmArgs g = nt_(sh[0], sh[1], sh[2]);
-      snprintf(buf, sizeof buf, "s%d NT plain M%d N%d K%d", var, sh[0], sh[1], sh[2]);
+      snprintf(buf, sizeof buf, "step NT plain M%d N%d K%d", sh[0], sh[1], sh[2]);
       timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, &g, 1, st); }, s);
     }
     int sh3[][3] = {{B, 200, 200}, {B, 1024, 200}, {B, 6, 200}, {B, 255, 200}};
     for (auto& sh : sh3) {
       GemmArgs gl = nt_(sh[0], sh[1], sh[2]);
       gl.ln_g = lng; gl.ln_b = lnb;
-      snprintf(buf, sizeof buf, "s%d NT lnsilu M%d N%d K%d", var, sh[0], sh[1], sh[2]);
+      snprintf(buf, sizeof buf, "step NT lnsilu M%d N%d K%d", sh[0], sh[1], sh[2]);
       timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNSILU, &gl, 1, st); }, s);
     }
     GemmArgs gp[2] = {nt_(B, 1027, 1800), nt_(B, 600, 1800)};
-    snprintf(buf, sizeof buf, "s%d NT plain grouped BPTT gZ+gH", var);
-    timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, gp, 2, st); }, s);
+    timeit("step NT plain grouped BPTT gZ+gH", [&](hipStream_t st) { gemm_launch(G_NT, AM_PLAIN, gp, 2, st); }, s);
     GemmArgs gb2 = nt_(64, 1624, 200);
     gb2.ln_g = lng; gb2.ln_b = lnb; gb2.pre = X; gb2.ld_pre = 200;
-    snprintf(buf, sizeof buf, "s%d NT lnbwd M64 N1624 K200", var);
-    timeit(buf, [&](hipStream_t st) { gemm_launch(G_NT, AM_LNBWD, &gb2, 1, st); }, s);
+    timeit("step NT lnbwd M64 N1624 K200", [&](hipStream_t st) { gemm_launch(G_NT, AM_LNBWD, &gb2, 1, st); }, s);
   }
-  dr_debug_skinny_variant(0);
   // mid-size shapes (tile GEMM, split-K scratch when given)
   {
     float* skw = frand((size_t)8 << 20);
@@ -565,10 +492,7 @@ int main(int argc, char** argv) {
     struct Mid { int M, N, K; bool tn; bool sk; } mids[] = {
         {1024, 200, 1624, false, false}, {1024, 200, 1624, false, true}, {2048, 200, 4096, false, true},
         {200, 1624, 960, true, false},   {200, 1624, 960, true, true},   {200, 200, 1024, true, true}};
-    for (int var = 0; var < 6; ++var)
     for (auto& c : mids) {
-      dr_debug_tile_variant(var < 4 ? var : 0);
-      dr_debug_tile_wgs(var == 4 ? 256 : var == 5 ? 1024 : 512);
       GemmArgs g = gemm_args();
       g.M = c.M; g.N = c.N; g.K = c.K;
       if (!c.tn) { g.A = Xm; g.lda = c.K; g.W = Wm; g.ldb = c.K; }
@@ -576,10 +500,9 @@ int main(int argc, char** argv) {
       g.ksplitA = INT_MAX;
       g.Y = Ym; g.ldy = c.N;
       if (c.sk) { g.splitk_ws = skw; g.splitk_floats = (long long)8 << 20; }
-      snprintf(buf, sizeof buf, "v%d %s M%d N%d K%d%s", var, c.tn ? "TN" : "NT", c.M, c.N, c.K, c.sk ? " splitK" : "");
+      snprintf(buf, sizeof buf, "mid %s M%d N%d K%d%s", c.tn ? "TN" : "NT", c.M, c.N, c.K, c.sk ? " splitK" : "");
       timeit(buf, [&](hipStream_t st) { gemm_launch(c.tn ? G_TN : G_NT, AM_PLAIN, &g, 1, st); }, s, 50);
     }
-    dr_debug_tile_variant(0);
   }
   // ln_silu_bwd / colsum
   timeit("ln_silu_bwd M64 K512", [&](hipStream_t st) { op_ln_silu_bwd(64, 512, X, 512, Y, 512, lng, lnb, W, 512, nullptr, nullptr, st); }, s);
