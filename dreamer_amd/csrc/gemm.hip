@@ -309,6 +309,10 @@ extern "C" int dr_debug_tbuf_gemm(long long* out, int n) {  // read, then clear
 #define SK_LN_MAXF 33280  // floats of staged LayerNorm rows (MT * (K + 4)); 130 KB of the 160 KB LDS
 #define SK_LN_MAXK 2048   // LayerNorm width staged with its gamma / beta
 #define SK_STAGE 8        // float4 staging loads in flight per thread
+// float4 per lane per staged row of an MT x NT skinny tile: 4 (K <= 1024) on
+// the 16-row tiles of up to 32 columns; the 48-column tile holds 6 weight rows
+// per wave in registers and stages K <= 256, like the 64-row tiles
+constexpr __host__ __device__ int sk_stage_vecs(int mt, int nt) { return (mt == 16 && nt <= 32) ? 4 : 1; }
 
 // hot operands of a skinny problem as wave-uniform scalars (see dr_uni)
 struct SkOps {
@@ -379,12 +383,12 @@ __device__ __forceinline__ float epi_act(const GemmArgs& g, float v) {
   return v;
 }
 
-// GruBwdEpi: the gru_cell backward of one (row, unit) from the final dL/dh'
-__device__ __noinline__ void gru_bwd_elem(const GruBwdEpi& e, int m, int j, float g) {
+// GruBwdEpi: the gru_cell backward of one (row, unit) from the final dL/dh',
+// on operands already in registers (r, u, n, hn = W_hn h + b_hn, hv = h,
+// o_old = dL/dh before this step's addend)
+__device__ __forceinline__ void gru_bwd_apply(const GruBwdEpi& e, int m, int j, float g, float r, float u, float n,
+                                              float hn, float hv, float o_old) {
   const int Hd = e.Hd;
-  const long long i = (long long)m * Hd + j;
-  const float r = dr_g(e.r)[i], u = dr_g(e.u)[i], n = dr_g(e.n)[i], hn = dr_g(e.ghn)[i];
-  const float hv = e.h ? dr_g(e.h)[(long long)m * e.ldh + j] : 0.0f;
   // h' = (h - n)*u + n
   const float g_hmn = g * u;
   const float g_u = g * (hv - n);
@@ -413,8 +417,15 @@ __device__ __noinline__ void gru_bwd_elem(const GruBwdEpi& e, int m, int j, floa
     gh16[Hd + j] = __builtin_bit_cast(unsigned short, (__bf16)g_pu);
     gh16[2 * Hd + j] = __builtin_bit_cast(unsigned short, (__bf16)g_hn);
   }
-  DR_GLOBAL float* o = dr_g(e.ho) + (long long)m * e.ldo + j;
-  *o = *o + g_hmn;
+  dr_g(e.ho)[(long long)m * e.ldo + j] = o_old + g_hmn;
+}
+
+// ... loading them itself (the epilogues that do not prefetch)
+__device__ __noinline__ void gru_bwd_elem(const GruBwdEpi& e, int m, int j, float g) {
+  const long long i = (long long)m * e.Hd + j;
+  const float r = dr_g(e.r)[i], u = dr_g(e.u)[i], n = dr_g(e.n)[i], hn = dr_g(e.ghn)[i];
+  const float hv = e.h ? dr_g(e.h)[(long long)m * e.ldh + j] : 0.0f;
+  gru_bwd_apply(e, m, j, g, r, u, n, hn, hv, dr_g(e.ho)[(long long)m * e.ldo + j]);
 }
 
 __device__ __forceinline__ void epilogue_store_b(const GemmArgs& g, int m, int n, float acc, float bias) {
@@ -428,6 +439,49 @@ __device__ __forceinline__ void epilogue_store_b(const GemmArgs& g, int m, int n
   const float fin = g.accumulate ? *dst + v : v;
   *dst = fin;
   if (g.gb.Hd > 0 && n < g.gb.Hd) gru_bwd_elem(g.gb, m, n, fin);
+}
+
+// epilogue_store_b with its memory operands read ahead of the K loop
+// (k_gemm_skinny, AM_LNBWD): the same arithmetic on the same values.  Nothing
+// else in the launch writes them -- element (m, n) of Y and of dL/dh belongs to
+// this thread alone; should dL/dh alias the output element, the stored value
+// is taken, as a read after the store would see it
+struct SkEpiPf {
+  float dst, r, u, n, hn, h, o;
+};
+__device__ __forceinline__ DR_GLOBAL float* sk_epi_dst(const GemmArgs& g, int m, int n) {
+  if (n < g.nsplitY) return dr_g(g.Y) + (long long)m * g.ldy + n;
+  return dr_g(g.Y2) + (long long)m * g.ldy2 + (n - g.nsplitY);
+}
+__device__ __forceinline__ SkEpiPf sk_epi_prefetch(const GemmArgs& g, int m, int n, bool ok) {
+  SkEpiPf p = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (!ok) return p;
+  if (g.accumulate) p.dst = *sk_epi_dst(g, m, n);
+  const GruBwdEpi& e = g.gb;
+  if (e.Hd > 0 && n < e.Hd) {
+    const long long i = (long long)m * e.Hd + n;
+    p.r = dr_g(e.r)[i];
+    p.u = dr_g(e.u)[i];
+    p.n = dr_g(e.n)[i];
+    p.hn = dr_g(e.ghn)[i];
+    if (e.h) p.h = dr_g(e.h)[(long long)m * e.ldh + n];
+    p.o = dr_g(e.ho)[(long long)m * e.ldo + n];
+  }
+  return p;
+}
+__device__ __forceinline__ void epilogue_store_pf(const GemmArgs& g, int m, int n, float acc, float bias,
+                                                  const SkEpiPf& p) {
+  float v = (g.alpha == 1.0f) ? acc : g.alpha * acc;
+  if (g.bias) v = v + bias;
+  if (g.addend) v = v + dr_g(g.addend)[(long long)m * g.ld_add + n];
+  v = epi_act(g, v);
+  DR_GLOBAL float* dst = sk_epi_dst(g, m, n);
+  const float fin = g.accumulate ? p.dst + v : v;
+  *dst = fin;
+  if (g.gb.Hd > 0 && n < g.gb.Hd) {
+    const DR_GLOBAL float* o = dr_g(g.gb.ho) + (long long)m * g.gb.ldo + n;
+    gru_bwd_apply(g.gb, m, n, fin, p.r, p.u, p.n, p.hn, p.h, o == dst ? fin : p.o);
+  }
 }
 
 #define DR_SKW 8  // waves per skinny-GEMM workgroup (K split over them; 4 measured slower, r05)
@@ -479,6 +533,22 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
       ebias[i] = ok ? v : 0.f;
     }
   }
+  // LayerNorm-backward products (the BPTT's hidden-state gradient): what the
+  // epilogue reads per output element -- the accumulate read of dst and the
+  // fused GRU backward's saves (r, u, n, hn, h) and dL/dh -- issued now as
+  // well, so the epilogue pays no memory round trip after the K loop
+  constexpr bool PFE = (AMODE == AM_LNBWD) && (EPI == EPI_NONE);
+  SkEpiPf pf[PFE ? NEPI : 1];
+  if (PFE) {
+#pragma unroll
+    for (int i = 0; i < NEPI; ++i) {
+      const int x = tid + NTH * i;
+      const int l = x & 63, e = (x >> 6) & 3, tj = x >> 8;
+      const int t = tj / FN, j = tj - t * FN;
+      const int m = m0 + t * 16 + 4 * (l >> 4) + e, n = n0 + j * 16 + (l & 15);
+      pf[i] = sk_epi_prefetch(g, m, n, x < FT * FN * 256 && m < M && n < N);
+    }
+  }
 
   // Philox state of the sampler / actor epilogues, fetched now (not after the K loop)
   unsigned long long rng_seed = 0, rng_off = 0;
@@ -503,7 +573,7 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
   const int K4 = K >> 2;
   constexpr int RPW = MT / NWAVE;                    // A rows per wave
   constexpr int BPW = (NT + NWAVE - 1) / NWAVE;      // weight rows per wave
-  constexpr int SV = (MT == 16) ? 4 : 1;             // float4 per lane per staged row (K <= 256 * SV)
+  constexpr int SV = sk_stage_vecs(MT, NT);          // float4 per lane per staged row (K <= 256 * SV)
   float* a_out = dr_uni(g.a_out);
   const int ld_aout = dr_uni((int)g.ld_aout);
   const bool store_a = (a_out != nullptr) && (tn == 0);
@@ -745,7 +815,7 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
 #pragma unroll
         for (int j = 0; j < FN; ++j) ac[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t].w, fb[j].w, ac[t][j], 0, 0, 0);
     }
-  } else {
+  } else if (AMODE != AM_LNBWD) {  // (the LayerNorm-backward prologue exists only staged: try_skinny's guard)
     // K loop in batches of PRE 16-k chunks: every load of a batch is issued
     // before its first MFMA, so a wave pays one memory round trip per batch
     // (one in total for K <= PRE*16*8 = 1024).  The first batch of weights (and
@@ -961,7 +1031,9 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
     const int t = tj / FN, j = tj - t * FN;
     const int ml = t * 16 + 4 * (l >> 4) + e, nl = j * 16 + (l & 15);
     const int m = m0 + ml, n = n0 + nl;
-    if (EPI == EPI_NONE || g.epi == EPI_NONE) {
+    if (PFE) {
+      if (m < M && n < N) epilogue_store_pf(g, m, n, v, ebias[i], pf[i]);
+    } else if (EPI == EPI_NONE || g.epi == EPI_NONE) {
       if (m < M && n < N) epilogue_store_b(g, m, n, v, ebias[i]);
     } else {
       if (m < M && n < N) {
@@ -2037,7 +2109,7 @@ static size_t skinny_lds_floats(const GemmBatch& gb, int count, bool vec) {
     const size_t K = gb.p[i].K, KP = K + ((8 - (K & 15)) & 15);
     const size_t staged = (size_t)(MT + NT) * KP, rows = (size_t)MT * KP;
     if ((AMODE == AM_LNSILU || AMODE == AM_LNBWD || AMODE == AM_STEBWD) && !B_KN &&
-        K / 4 <= 64 * (MT == 16 ? 4 : 1) &&
+        K / 4 <= 64 * (size_t)sk_stage_vecs(MT, NT) &&
         staged <= SK_LN_MAXF)
       need = std::max(need, staged);  // kernel's `staged`
     else if (AMODE == AM_LNSILU && rows <= SK_LN_MAXF && K / 4 <= 64 * (MT == 16 ? 8 : 2))
@@ -2078,6 +2150,8 @@ static void launch_skinny(const GemmBatch& gb, int count, bool vec, hipStream_t 
 // The staged backward prologues (AM_LNBWD, AM_STEBWD) run on 16-row tiles
 // (K <= 1024) when the problem has at most 64 rows or its 16 x 16 grid stays
 // within ~2.5 dispatch rounds (try_skinny), else on 64-row tiles (K <= 256).
+// (The 16 x 48 LayerNorm-backward tile try_skinny picks for a grid between one
+// and two rounds stages K <= 256 as well; wider K keeps 32 columns.)
 bool gemm_bwd_rows16(const GemmArgs* p, int count) {
   int maxM = 0, t16 = 0;
   for (int i = 0; i < count; ++i) {
@@ -2120,6 +2194,25 @@ static bool try_skinny(const GemmBatch& gb, int count, hipStream_t s) {
   for (int i = 0; i < count; ++i)
     tiles16 += dr_cdiv(gb.p[i].M, maxM > 64 ? 64 : 16) * dr_cdiv(gb.p[i].N, 16);
   bool wide = maxM <= 64 && tiles16 > 256;
+  // The staged LayerNorm-backward tile holds one workgroup per CU, so its grid
+  // is never left between one and two dispatch rounds: where the 32-column
+  // grid has more than 256 and fewer than 512 tiles (a full round plus a tail
+  // that costs a whole second one) and 48 columns bring it to at most 256,
+  // the tile is 16 x 48.  B = 256, N = 600 (the BPTT's hidden-state gradient
+  // with the GRU backward in its epilogue): 304 tiles -> 208.  The tile stages
+  // K <= 256 (sk_stage_vecs); a shape it cannot stage keeps 32 columns.
+  bool wide48 = false;
+  if (AMODE == AM_LNBWD && epi == EPI_NONE && wide && vec) {
+    int t32 = 0, t48 = 0;
+    bool fits = true;
+    for (int i = 0; i < count; ++i) {
+      const int K = gb.p[i].K, KP = K + ((8 - (K & 15)) & 15);
+      t32 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, 32);
+      t48 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, 48);
+      fits = fits && (16 + 48) * KP <= SK_LN_MAXF && K / 4 <= 64 * sk_stage_vecs(16, 48);
+    }
+    wide48 = fits && t32 > 256 && t32 < 512 && t48 <= 256;
+  }
   // the backward prologues exist only on the staged path (A and weight rows of
   // the tile in LDS, k_gemm_skinny `staged`): a tile whose rows do not fit
   // would read the raw operand.  At K = 1024 (the STE backward of a 32 x 32
@@ -2142,8 +2235,11 @@ static bool try_skinny(const GemmBatch& gb, int count, hipStream_t s) {
     if (maxM > 64) launch_skinny<64, 16, AMODE, B_KN, EPI_ACTOR>(gb, count, vec, s);
     else launch_skinny<16, 16, AMODE, B_KN, EPI_ACTOR>(gb, count, vec, s);
   } else {
-    if (maxM > 64) launch_skinny<64, 16, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
-    else if (wide) launch_skinny<16, 32, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
+    if (maxM > 64) {
+      launch_skinny<64, 16, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
+    } else if (wide48) {
+      if constexpr (AMODE == AM_LNBWD) launch_skinny<16, 48, AM_LNBWD, B_KN, EPI_NONE>(gb, count, vec, s);
+    } else if (wide) launch_skinny<16, 32, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
     else launch_skinny<16, 16, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
   }
   return true;
