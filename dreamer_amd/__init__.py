@@ -13,6 +13,7 @@ from .closed_loop import ClosedLoopResult  # noqa: F401
 from .futures import FuturesResult  # noqa: F401
 from .open_loop import OpenLoopResult  # noqa: F401
 from .plan import PlanResult, check_plan  # noqa: F401
+from .saliency import SaliencyResult  # noqa: F401
 from .networks import (ContinuePredictor, Decoder, DynamicsPredictor, Encoder, RewardPredictor,  # noqa: F401
                        SequenceModel)
 from .world_model import WorldModel  # noqa: F401

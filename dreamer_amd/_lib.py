@@ -158,6 +158,11 @@ _SIGS = {
     "dr_frame_metrics": (_i, [_P(dr_dims), _i, _i, fp, _P(dr_frames), fp, fp, fp, fp]),
     "dr_frame_ssim": (_i, [_P(dr_dims), _i, _i, fp, _P(dr_frames), fp, fp, fp]),
     "dr_ensemble_metrics": (_i, [_P(dr_dims), _i, _i, _i, fp, _P(dr_frames), fp, fp, fp, fp, fp, fp]),
+    "dr_occlude_workspace_bytes": (_sz, [_P(dr_dims), _i]),
+    "dr_occlude_frames": (_i, [_P(dr_dims), _P(dr_frames), _i, _i, _i, fp, _i, fp, fp, fp, _sz, fp]),
+    "dr_saliency_scores": (_i, [_i, _i, _i, _i, _i, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
+    "dr_saliency_map": (_i, [_P(dr_dims), _i, _i, fp, fp, _P(dr_frames), _i, fp, fp, fp]),
+    "dr_saliency_draws": (_i, [_i, _i, dr_noise, fp, fp]),
     "dr_wm_train_phase": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_decoder), _i, _i, _P(dr_frames),
                                _P(dr_wm_batch), dr_noise, dr_wm_loss_cfg, _i, fp, _i, fp, fp, _P(dr_world_model),
                                _P(dr_decoder), fp, fp, fp, fp, _sz, fp]),
@@ -196,6 +201,8 @@ DR_ACT_VEC_MAX_OBS = 1023  # include/dreamer_hip.h: widest observation vector dr
 DR_PLAN_MAX_CANDIDATES = 2048  # include/dreamer_hip.h: candidates per environment of dr_plan_sample / dr_plan_update
 DR_ENSEMBLE_MAX_SAMPLES = 64  # include/dreamer_hip.h: futures per window of dr_ensemble_metrics
 DR_PLAN_MAX_ELEMS = 1024  # include/dreamer_hip.h: H * A of one planned action sequence
+DR_SALIENCY_MAX_CELLS = 1024  # include/dreamer_hip.h: cells of one frame's saliency grid
+DR_SALIENCY_MAX_RADIUS = 15  # include/dreamer_hip.h: widest blur radius of dr_occlude_frames
 
 
 class HipError(RuntimeError):

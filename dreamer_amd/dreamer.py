@@ -307,6 +307,51 @@ class Dreamer(nn.Module):
         from .agent_trace import evaluate_values
         return evaluate_values(self, batches=batches, batch_size=batch_size, length=length, sample=sample)
 
+    def saliency_frames(self, frames, hiddens, stride=4, fill="blur", blur_sigma=3.0, mask_sigma=None, sample=False,
+                        noise=None, _mark=None):
+        """Perturbation saliency of N frames (saliency.py; Greydanus et al. 2018):
+        per cell of a stride-`stride` grid, how far the actor's mean, the
+        critic's value and the posterior move when a blurred (fill="blur",
+        Gaussian of blur_sigma) or averaged (fill="mean") copy of the frame is
+        blended in around the cell under a Gaussian mask of mask_sigma (default
+        5 * H / 80).  include/dreamer_hip.h "perturbation saliency" has the
+        definitions.  Pixel models only (ValueError otherwise).
+
+        frames: u8 (N, H, W, 3) numpy as the env gives them, or a u8 (N, 3, H, W)
+        device tensor.  hiddens (N, hidden): the hidden state about to encode
+        each frame, e.g. the h' act_step_batch returned.  All variants of a
+        frame share one block of Exp(1) draws: sample=False (the default) takes
+        the mode of every categorical, noise (N*R, C) gives them, sample=True
+        draws one block per frame from the ad-hoc Philox stream.  Runs in passes
+        of at most 8192 variant frames on the current stream without a sync.
+        Returns a SaliencyResult with lead (N,).  _mark: stage hook of
+        tools/saliency_timing.py."""
+        from .saliency import saliency_frames
+        return saliency_frames(self, frames, hiddens, stride=stride, fill=fill, blur_sigma=blur_sigma,
+                               mask_sigma=mask_sigma, sample=sample, noise=noise, _mark=_mark)
+
+    def saliency(self, starts=None, batch_size=None, length=None, steps=None, **kw):
+        """Perturbation saliency on replay windows: run closed_loop's filter
+        (as agent_trace does) over the first `length` frames (default S) of each
+        window, then saliency_frames on the ring's frames of the window steps
+        `steps` (default: all) with the filter's hidden states -- hiddens[t] is
+        the state about to encode frame t.  Returns a SaliencyResult with lead
+        (B, K = len(steps)).  Keywords as saliency_frames; noise, if given, is
+        the pair (the trace's draws (T, B*R, C), the variants' draws (B*K*R, C)),
+        and sample applies to both.  Every argument check fires before np.random
+        is drawn from."""
+        from .saliency import saliency
+        return saliency(self, starts=starts, batch_size=batch_size, length=length, steps=steps, **kw)
+
+    def evaluate_saliency(self, batches=1, batch_size=None, length=None, steps=None, **kw):
+        """Saliency averaged over `batches` sampled batches of windows: a dict
+        with the mean actor, value and posterior_kl grids (Gy x Gx nested
+        lists, over frames and batches) and "concentration", the mean share of
+        each score in its top 10 % of cells (top=...).  Leaves np.random's state
+        and the Philox {seed, offset} and stream counter as it found them."""
+        from .saliency import evaluate_saliency
+        return evaluate_saliency(self, batches=batches, batch_size=batch_size, length=length, steps=steps, **kw)
+
     # --------------------------------------------------------------- training
     @property
     def engine(self):

@@ -669,6 +669,89 @@ int dr_action_logprob(int B, int T, int A, const float* mu, const float* sigma, 
                       long long act_sb, long long act_st, float* logp, float* logp_dims, float* base_entropy,
                       hipStream_t stream);
 
+/* ---- perturbation saliency (Dreamer.saliency, dreamer_amd/saliency.py;
+ *      Greydanus et al. 2018, "Visualizing and Understanding Atari Agents"):
+ *      blend a blurred copy of the frame into one small region, run the agent
+ *      again, score how far its outputs moved; repeated over a grid of regions.
+ *      No reference counterpart: the definitions are these.  Pixel models only
+ *      (obs_dim > 0: DR_E_UNSUPPORTED). ------------------------------------------
+ * Grid: stride s with H % s == 0 and W % s == 0; Gy = H / s, Gx = W / s, G = Gy Gx
+ * <= 1024.  Cell (i, j) has the integer centre cy = i s + s / 2, cx = j s + s / 2
+ * (integer division).  Variant 0 of a frame is the frame itself, variant
+ * 1 + i Gx + j is perturbed at cell (i, j).
+ * Tables, made on the host in double, rounded to f32 and passed as device
+ * arrays (the kernels call no expf):
+ *   wb[0 .. 2 rb]            blur taps exp(-k^2 / (2 sigma_b^2)), k = -rb .. rb, normalised
+ *                            to sum 1; rb = ceil(3 sigma_b) <= 15
+ *   gm[0 .. max(H, W) - 1]   mask profile exp(-k^2 / (2 sigma_m^2))
+ * Fill A, f32 per channel:
+ *   fill = 0 (blur)  Hh[c][y][x] = sum_k wb[k + rb] I[c][y][clamp(x + k, 0, W - 1)], then the
+ *                    same over y on Hh; each sum an explicit fmaf(w, v, acc) chain
+ *                    from acc = 0.0f in ascending k
+ *   fill = 1 (mean)  A[c] = (float)(exact integer sum of channel c) / (float)(H W)
+ * Perturbed pixel: m = gm[|y - cy|] * gm[|x - cx|] (one f32 multiply),
+ *   v = fmaf(m, A - I, I) with A - I one f32 subtraction,
+ *   out = (u8) min(255, max(0, rintf(v))).
+ *
+ * dr_occlude_frames: src is a u8 ring source (dr_frames); frame f of the call is
+ * src's frame (b = f, t = 0), t0 honoured -- a plain u8 array of N frames is a
+ * ring with ring_cap = N and starts = 0 .. N-1.  out u8 [F][G+1][3][H][W].
+ * Two stages: the fill into the workspace (blur: row strips through LDS; mean:
+ * one workgroup per channel), then the blend -- a thread keeps I and A - I of
+ * its 16 pixels in registers, loops over 32 variants of its frame and writes 16
+ * bytes per store, so A is read once per workgroup; a width that is no multiple
+ * of 16 (or a base that is not 16-byte aligned) takes a one-pixel-per-thread
+ * path with the same arithmetic.
+ * DR_E_INVALID, nothing launched: rb > 15, G > 1024, a stride that does not
+ * divide the frame, a NULL table (wb is not read with fill = 1 and may be NULL
+ * then).  DR_E_UNSUPPORTED, nothing launched: a src in f32 form, vector
+ * observations, rows so wide that the blur's strip ((8 + 2 rb) rows of W floats)
+ * does not fit 64 KiB of LDS.  F <= 65535.
+ * Asynchronous, capturable, no atomics; a frame's variants are the same bits at
+ * every F and position, and from run to run. */
+size_t dr_occlude_workspace_bytes(const dr_dims* d, int F);
+int dr_occlude_frames(const dr_dims* d, const dr_frames* src, int F, int s, int fill, const float* wb, int rb,
+                      const float* gm, unsigned char* out, void* ws, size_t ws_bytes, hipStream_t stream);
+/* Scores of variant g >= 1 of frame f against variant 0 of the same frame; rows
+ * f (G + 1) + g of mu [.][A] (Actor.forward's mean), V [.] (critic.value), logits
+ * and z [.][R*C] (the posterior's raw logits and its straight-through sample).
+ * Outputs [F][G], entry g - 1, any of them may be NULL (then its input may be too):
+ *   actor        = 1/2 sum_i (mu_g,i - mu_0,i)^2
+ *   value_delta  = V_g - V_0 (one f32 subtraction);  value = 1/2 value_delta^2
+ *   posterior_kl = sum_r KL(Cat(logits_0,r) || Cat(logits_g,r)) on raw logits as
+ *                  dr_latent_stats defines kl: max-subtracted log-sum-exp,
+ *                  lp = (x - max) - log(sum), a class whose p underflows adds 0
+ *   latent_flips = the number of the R categoricals whose selected class (the
+ *                  lowest index holding the maximum of z's group) differs, int32
+ * One 256-thread workgroup per (f, g).  actor: a thread takes the elements tid,
+ * tid + 256, ... in ascending order.  posterior_kl and latent_flips (C <= 64,
+ * else DR_E_INVALID): a categorical takes W lanes, W the power of two >= C, one
+ * class per lane and fixed trees inside the group as in dr_latent_stats; the
+ * group's first lane adds its categoricals in ascending order.  Then
+ * dr_frame_metrics' wave reduction and the four wave sums in wave order: the
+ * same bits at every F and position and from run to run.  Identical rows give
+ * exactly 0 everywhere. */
+int dr_saliency_scores(int F, int G, int A, int R, int C, const float* mu, const float* V, const float* logits,
+                       const float* z, float* actor, float* value, float* value_delta, float* posterior_kl,
+                       int* latent_flips, hipStream_t stream);
+/* Heat map of a score grid, scores [F][Gy][Gx], scale [F].  For pixel (y, x):
+ *   fy = min(max(((float)(y - s/2)) / (float)s, 0), Gy - 1), i0 = floor(fy),
+ *   i1 = min(i0 + 1, Gy - 1), wy = fy - i0; the same in x;
+ *   map[f][y][x] = scale[f] * ((((1-wy)(1-wx)) S[i0][j0] + ((1-wy) wx) S[i0][j1])
+ *                              + (wy (1-wx)) S[i1][j0]) + (wy wx) S[i1][j1])
+ *   in f32, products and sums as written, no contraction: a cell's centre pixel
+ *   gives scale[f] * S[i][j] exactly.
+ * overlay u8 [F][3][H][W] (may be NULL; `frames`, a u8 ring source read as
+ * dr_occlude_frames reads src, is needed only with it): heat = min(1, max(0, map)),
+ * channel ch becomes (u8) rintf(fmaf(heat, 255 - I, I)), the others are copied.
+ * One thread per pixel. */
+int dr_saliency_map(const dr_dims* d, int F, int s, const float* scores, const float* scale,
+                    const dr_frames* frames, int ch, float* map, unsigned char* overlay, hipStream_t stream);
+/* q[row][c], row < rows, c < C: the Exp(1) Philox variate of (noise.stream,
+ * noise.row0 + row, c), written out so that every variant of a frame can be
+ * given its frame's draws as explicit noise (common random numbers). */
+int dr_saliency_draws(int rows, int C, dr_noise noise, float* q, hipStream_t stream);
+
 /* ---- latent planning: CEM / MPPI action search over world-model rollouts ----
  * (dreamer_amd/plan.py, Dreamer.plan; no reference counterpart: the reference's
  * only controller is the actor's forward pass, Dreamer.py:295-322.)
