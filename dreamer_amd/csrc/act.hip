@@ -31,6 +31,7 @@
 // NaN outputs instead of a hung GPU.
 #include "common.h"
 #include "ops.h"
+#include "engine_util.h"
 
 #include <string.h>
 
@@ -1006,6 +1007,7 @@ extern "C" int dr_act_step(const dr_dims* d, const dr_world_model* wm, const dr_
                  "staging)");
     return DR_E_UNSUPPORTED;
   }
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
   return act_batch_run("dr_act_step",
                        act_common(d, wm, ac, 1, nullptr, has_prev ? 0u : 1u, z_prev, h, a_prev, noise, deterministic,
                                   z_out, h_out, a_out, mu_out, sigma_out, logits_out, status),
@@ -1030,6 +1032,7 @@ extern "C" int dr_act_batch(const dr_dims* d, const dr_world_model* wm, const dr
                  "filters, widths <= the staging)");
     return DR_E_UNSUPPORTED;
   }
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
   return act_batch_run("dr_act_batch",
                        act_common(d, wm, ac, n_env, first, 0u, z_prev, h, a_prev, noise, deterministic, z_out, h_out,
                                   a_out, mu_out, sigma_out, logits_out, status),
@@ -1063,6 +1066,7 @@ extern "C" int dr_act_vec(const dr_dims* d, const dr_world_model* wm, const dr_a
                  "<= the staging)");
     return DR_E_UNSUPPORTED;
   }
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
   static ActFamily fam = {{(const void*)k_act_vec<1>, (const void*)k_act_vec<2>, (const void*)k_act_vec<4>,
                            (const void*)k_act_vec<8>},
                           ACT_VEC_LDS_MAX};

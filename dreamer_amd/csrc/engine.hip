@@ -301,6 +301,7 @@ extern "C" int dr_observe_scan(const dr_dims* d, const dr_world_model* wm, int B
                                const float* z_init, dr_noise noise, float* z_out, float* h_out, float* logits_out,
                                void* ws, size_t ws_bytes, hipStream_t s) {
   DR_REQUIRE(d && wm && feat && z_out && h_out && B > 0 && T > 0, "null argument or empty batch");
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER));
   GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
   DR_REQUIRE(T == 1 || (z_init == nullptr ? T > 1 : true), "bad T");
   DR_REQUIRE(actions || (z_init == nullptr && T == 1), "actions required");
@@ -677,6 +678,7 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
   DR_REQUIRE(d && wm && ac && z0 && h0 && latents && hiddens && actions && rewards && continues && mus && sigmas &&
                  tape && B > 0 && H > 0,
              "null argument or empty batch");
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
   GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
   Carve c(ws);
   ImWs w;
@@ -750,11 +752,12 @@ static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int 
                   d->buckets);
     p[1] = lin_ln(M1, 1, d->cont_h2, w.p2c, d->cont_h2, wm->cont.n4, wm->cont.l6.w, wm->cont.l6.b, w.clog, 1);
     p[1].act = 2;  // sigmoid
-    if (std::max(std::max(d->rew_h1, d->rew_h2), std::max(d->cont_h1, d->cont_h2)) <= 208) {
-      // LN-SiLU, Linear, LN-SiLU, Linear of both heads in one launch (k_mlp2_tail:
-      // 16 rows per workgroup, the 200-wide middle layer recomputed per
-      // 128-column block); the two-launch form below is the general path
-      Mlp2Args m2[2];
+    // LN-SiLU, Linear, LN-SiLU, Linear of both heads in one launch (k_mlp2_tail:
+    // 16 rows per workgroup, the 200-wide middle layer recomputed per
+    // 128-column block) where both heads fit it (widths % 4 == 0, <= 208:
+    // mlp2_ok); the two-launch form below is the general path
+    Mlp2Args m2[2];
+    {
       const float* x1[2] = {w.p1r, w.p1c};
       const dr_mlp3* hm[2] = {&wm->reward, &wm->cont};
       const int k1[2] = {d->rew_h1, d->cont_h1}, k2[2] = {d->rew_h2, d->cont_h2};
@@ -768,6 +771,8 @@ static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int 
         m2[i].e = p[i];
         m2[i].e.A = nullptr;
       }
+    }
+    if (mlp2_ok(m2[0]) && mlp2_ok(m2[1])) {
       DR_TRY(mlp2_launch(m2, 2, s));
     } else {
       GemmArgs q[2];
@@ -838,6 +843,7 @@ extern "C" int dr_imagine_actions(const dr_dims* d, const dr_world_model* wm, in
   DR_REQUIRE(d && wm && z0 && h0 && actions && latents && hiddens && rewards && continues && ws && B > 0 && H > 0,
              "null argument or empty batch");
   DR_REQUIRE(wm->w_ih && wm->w_hh && wm->b_ih && wm->b_hh, "GRU weights required");
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER));
   GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
   Carve c(ws);
   ImActWs a;
@@ -938,6 +944,7 @@ static int imagine_bwd_impl(const dr_dims* d, const dr_world_model* wm, const dr
                             const void* tape, const dr_actor* gr, void* ws, size_t ws_bytes, hipStream_t s,
                             bool do_prep, bool do_main) {
   DR_REQUIRE(d && wm && ac && B > 0 && H > 0, "null argument or empty batch");
+  DR_TRY(dims_envelope("dr_imagine_bwd", d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
   GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
   DR_REQUIRE(!do_main || (latents && hiddens && actions && tape && gr), "null argument");
   Carve c(ws);
@@ -1399,6 +1406,7 @@ extern "C" int dr_observe_trace(const dr_dims* d, const dr_world_model* wm, int 
   DR_REQUIRE((long long)B * T <= 0x7fffffffLL, "too many states");
   DR_REQUIRE((rewards == nullptr) == (continues == nullptr), "rewards and continues: both or neither");
   DR_REQUIRE(actions || (z_init == nullptr && T == 1), "actions required");
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER));
   GemmBf16Scope bf16_scope(d->precision == DR_PREC_BF16);
   Carve c(ws);
   TraceWs a;
@@ -1435,6 +1443,7 @@ extern "C" int dr_imagine_step(const dr_dims* d, const dr_world_model* wm, int B
                                const float* a, dr_noise noise, float* h_out, float* z_out, float* r_out,
                                float* c_out, void* ws, size_t ws_bytes, hipStream_t s) {
   DR_REQUIRE(d && wm && z && a && h_out && z_out && B > 0, "null argument");
+  DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER));
   const int L = latent(d), Hd = d->hidden;
   Carve c(ws);
   float* gi = c.f((long long)B * 3 * Hd);
@@ -1479,6 +1488,7 @@ extern "C" int dr_actor_act(const dr_dims* d, const dr_actor* ac, int B, const f
                             dr_noise noise, int deterministic, float* a_out, float* mu_out, float* sigma_out,
                             void* ws, size_t ws_bytes, hipStream_t s) {
   DR_REQUIRE(d && ac && h && z && a_out && mu_out && sigma_out && B > 0, "null argument");
+  DR_TRY(dims_envelope(__func__, d, ENV_ACTOR));
   const int L = latent(d), Hd = d->hidden, A = d->action, a1 = d->actor_h1, a2 = d->actor_h2;
   Carve c(ws);
   ActWs w;

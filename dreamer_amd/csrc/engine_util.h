@@ -45,6 +45,49 @@ static inline int conv_bias_aligned(const char* fn, const char* layer, int k, co
   return DR_E_INVALID;
 }
 
+// The supported widths ("Supported widths"): the limits the
+// kernels behind the composite entry points check deep inside a call --
+// op_gru_fused (hidden % 4, rows % 4, rows <= 32, action <= 8), the sampler
+// epilogue of gemm_launch (cols divides 32; op_sample's cols <= 64 follows), the
+// actor-head epilogue (2 action <= 16), dr_encoder_features (filter counts and
+// obs_dim % 4, image size a multiple of 2^depth) -- stated once and checked
+// before an entry point's first launch.  parts: what the entry point runs.
+// The deep checks stay where they are.
+enum { ENV_GRU = 1, ENV_SAMPLER = 2, ENV_ACTOR = 4, ENV_ENCODER = 8 };
+static inline int dims_envelope(const char* fn, const dr_dims* d, int parts) {
+#define DR_ENVELOPE(ok, field, value, limit)                                                                  \
+  do {                                                                                                        \
+    if (!(ok)) {                                                                                              \
+      dr_set_error("%s: %s = %d is outside the supported widths: %s (INTEGRATION.md, Supported widths)", fn, \
+                   field, (int)(value), limit);                                                               \
+      return DR_E_INVALID;                                                                                    \
+    }                                                                                                         \
+  } while (0)
+  if (parts & ENV_GRU) {
+    DR_ENVELOPE(d->hidden > 0 && d->hidden % 4 == 0, "hidden", d->hidden, "must be a positive multiple of 4");
+    DR_ENVELOPE(d->rows > 0 && d->rows % 4 == 0, "rows", d->rows, "must be a positive multiple of 4");
+    DR_ENVELOPE(d->rows <= 32, "rows", d->rows, "must be at most 32");
+  }
+  if (parts & (ENV_GRU | ENV_ACTOR))
+    DR_ENVELOPE(d->action >= 0 && d->action <= 8, "action", d->action, "must be at most 8");  // (0: encode-only dims)
+  if (parts & ENV_SAMPLER)
+    DR_ENVELOPE(d->cols >= 1 && d->cols <= 32 && 32 % d->cols == 0, "cols", d->cols,
+                "must divide 32 (1, 2, 4, 8, 16 or 32)");
+  if ((parts & ENV_ENCODER) && d->obs_dim > 0)
+    DR_ENVELOPE(d->obs_dim % 4 == 0, "obs_dim", d->obs_dim, "must be a multiple of 4");
+  if ((parts & ENV_ENCODER) && d->obs_dim <= 0) {
+    const int depth = d->enc_depth == 5 ? 5 : 4;
+    DR_ENVELOPE(d->enc_f1 > 0 && d->enc_f1 % 4 == 0, "enc_f1", d->enc_f1, "must be a positive multiple of 4");
+    DR_ENVELOPE(d->enc_f2 > 0 && d->enc_f2 % 4 == 0, "enc_f2", d->enc_f2, "must be a positive multiple of 4");
+    DR_ENVELOPE(d->img_h > 0 && d->img_h % (1 << depth) == 0, "img_h", d->img_h,
+                "must be a multiple of 2^depth (16, or 32 for the 5-layer encoder)");
+    DR_ENVELOPE(d->img_w > 0 && d->img_w % (1 << depth) == 0, "img_w", d->img_w,
+                "must be a multiple of 2^depth (16, or 32 for the 5-layer encoder)");
+  }
+#undef DR_ENVELOPE
+  return DR_OK;
+}
+
 // kernels, not hipMemcpy2DAsync / hipMemsetAsync: see op_fill in ops.hip
 static inline int copy2d(float* dst, long long dpitch, const float* src, long long spitch, long long width, long long rows,
                   hipStream_t s) {

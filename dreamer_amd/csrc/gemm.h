@@ -116,4 +116,5 @@ struct alignas(16) Mlp2Args {
   float* a2_out; long long ld_a2;    // optional y2
   GemmArgs e;                        // last Linear: e.N, e.W [N][K2] (e.ldb), e.bias, epilogue
 };
+bool mlp2_ok(const Mlp2Args& a);  // the shapes and alignments mlp2_launch takes
 int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s);

@@ -2486,6 +2486,20 @@ __global__ __launch_bounds__(512) void k_mlp2_tail(Mlp2Batch mb) {
   }
 }
 
+// what k_mlp2_tail takes: both hidden widths staged as float4 rows of at most
+// MLP2_KMAX floats, 16-byte aligned operands, a plain, sampler or actor epilogue
+bool mlp2_ok(const Mlp2Args& a) {
+  const GemmArgs& g = a.e;
+  const bool al = !(((uintptr_t)a.X | (uintptr_t)a.W3 | (uintptr_t)g.W | (uintptr_t)a.ln1_g | (uintptr_t)a.ln1_b |
+                     (uintptr_t)a.ln4_g | (uintptr_t)a.ln4_b) & 15) &&
+                  !((uintptr_t)a.a1_out & 15) && !((uintptr_t)a.a2_out & 15);
+  return !(a.M < 1 || a.K1 < 4 || a.K2 < 4 || a.K1 > MLP2_KMAX || a.K2 > MLP2_KMAX || a.K1 % 4 || a.K2 % 4 ||
+           a.ldx % 4 || g.ldb % 4 || a.ld_a1 % 4 || a.ld_a2 % 4 || g.K != a.K2 || g.N < 1 || !al ||
+           (g.epi == EPI_SAMPLE && (g.C < 1 || g.C > 32 || 32 % g.C != 0 || MLP2_NC % g.C != 0)) ||
+           (g.epi == EPI_ACTOR && (g.N != 2 * g.na || g.N > 16)) || (g.epi == EPI_NONE && !g.Y) ||
+           g.accumulate || g.addend || g.alpha != 1.0f);
+}
+
 int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s) {
   if (count < 1 || count > 3) {
     dr_set_error("mlp2_launch: bad problem count %d", count);
@@ -2496,14 +2510,7 @@ int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s) {
   for (int i = 0; i < count; ++i) {
     const Mlp2Args& a = probs[i];
     const GemmArgs& g = a.e;
-    const bool al = !(((uintptr_t)a.X | (uintptr_t)a.W3 | (uintptr_t)g.W | (uintptr_t)a.ln1_g | (uintptr_t)a.ln1_b |
-                       (uintptr_t)a.ln4_g | (uintptr_t)a.ln4_b) & 15) &&
-                    !((uintptr_t)a.a1_out & 15) && !((uintptr_t)a.a2_out & 15);
-    if (a.M < 1 || a.K1 < 4 || a.K2 < 4 || a.K1 > MLP2_KMAX || a.K2 > MLP2_KMAX || a.K1 % 4 || a.K2 % 4 ||
-        a.ldx % 4 || g.ldb % 4 || a.ld_a1 % 4 || a.ld_a2 % 4 || g.K != a.K2 || g.N < 1 || !al ||
-        (g.epi == EPI_SAMPLE && (g.C < 1 || g.C > 32 || 32 % g.C != 0 || MLP2_NC % g.C != 0)) ||
-        (g.epi == EPI_ACTOR && (g.N != 2 * g.na || g.N > 16)) || (g.epi == EPI_NONE && !g.Y) ||
-        g.accumulate || g.addend || g.alpha != 1.0f) {
+    if (!mlp2_ok(a)) {
       dr_set_error("mlp2_launch: unsupported problem (M=%d K1=%d K2=%d N=%d epi=%d)", a.M, a.K1, a.K2, g.N, g.epi);
       return DR_E_INVALID;
     }

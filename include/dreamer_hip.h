@@ -26,6 +26,14 @@
  *    DR_E_INVALID, nothing launched, when it is not; dr_last_error() names the
  *    pointer.  (A tensor from the PyTorch allocator always is; a view at an
  *    offset that is no multiple of 4 floats is not.)
+ *  - supported widths ("Supported widths"): hidden % 4 == 0;
+ *    rows % 4 == 0, rows <= 32; cols divides 32; action <= 8; pixel
+ *    encoders enc_f1, enc_f2 % 4 == 0 and img_h, img_w multiples of 2^depth,
+ *    vector encoders obs_dim % 4 == 0.  The dr_imagine_*, dr_observe_*,
+ *    dr_wm_train_*, dr_act_* entry points and dr_actor_act check the ones
+ *    they depend on first and return DR_E_INVALID, nothing launched,
+ *    outside them; dr_last_error() names the field, its value and the limit.
+ *    The MLP widths and the bucket count are free.
  *  - arithmetic is fp32 (parity mode) unless dr_dims.precision selects bf16:
  *    fp32 GEMMs use the exact-f32 MFMA (v_mfma_f32_16x16x4_f32), elementwise
  *    code is built -ffp-contract=off; bf16 mode runs the encoder convolutions

@@ -117,38 +117,12 @@ def _baseline_wm_case(gpu, B, T=15, seed=0, precision="fp32"):
     """CarRacing widths at 64 x 64, reference default init under
     torch.manual_seed(0), SURVEY 8d synthetic replay (bench.synthetic_replay),
     B windows of T = horizon steps; the oracle's step on the CPU with a
-    tie-guarded posterior noise draw."""
+    tie-guarded posterior noise draw (widths_cases.wm_case at CAR)."""
     import bench
-    from baseline_case import TieGuard
-    from dreamer_amd import Dreamer
     from test_gpu_baseline import CAR
-    cfg = dict(CAR)
-    cfg.update(batch_size=B, sequence_length=64, horizon=T, precision=precision)
-    torch.manual_seed(0)
-    d = Dreamer(cfg, gpu)
-    wm = d.world_model
-    R, C = wm.latent_num_rows, wm.latent_num_columns
-    n = 4096
-    frames, acts, rews, conts = bench.synthetic_replay(n, (64, 64), 3, seed=seed)
-    starts = np.random.RandomState(300 + B).randint(0, n - T + 1, size=B)
-    idx = starts[:, None] + np.arange(T)[None, :]
-    obs = torch.tensor(frames[idx], dtype=torch.float32)
-    act = torch.tensor(acts[idx])
-    rew = torch.tensor(rews[idx]).unsqueeze(-1)
-    cont = torch.tensor(conts[idx]).unsqueeze(-1)
-    q = torch.empty(T, B * R, C).exponential_(generator=torch.Generator().manual_seed(400 + B))
-    names = [nm for nm, _ in wm.named_parameters()]
-    P0 = {("world_model." + k): v.detach().cpu().clone() for k, v in wm.state_dict().items()}
-    P = {k: v.clone().requires_grad_(True) for k, v in P0.items()}
-    torch.set_num_threads(16)
-    with TieGuard() as tg:  # widens near-tie margins of q in place, the oracle's draws unchanged
-        ref = O.wm_train_step(obs, act, rew, cont, P, q, R, C, T, ["world_model." + nm for nm in names],
-                              betas=(wm.beta_pred, wm.beta_dyn, wm.beta_rep))
-    out = {}
-    wm.train_step_hip(obs.to(gpu), act.to(gpu), rew.to(gpu), cont.to(gpu), noise_q=q.to(gpu), outputs=out,
-                      step=True)
-    torch.cuda.synchronize()
-    return d, wm, out, ref, q, names, P0, tg
+    from widths_cases import wm_case
+    return wm_case(dict(CAR, sequence_length=64), B, T, gpu, bench.synthetic_replay(4096, (64, 64), 3, seed=seed),
+                   precision)
 
 
 @pytest.mark.parametrize("B", [64, 256])
