@@ -1020,16 +1020,15 @@ static int imagine_bwd_impl(const dr_dims* d, const dr_world_model* wm, const dr
     if (state_grad) {
       // z_{t+1} = STE(prior(h_{t+1}))   (DynamicsPredictors.py:31-40)
       const int h1 = d->prior_h1, h2 = d->prior_h2;
-      const int gl = d->cols / 4;
-      GemmArgs gs = bwd_nt(B, h2, L, gZ_n, ldL, w.tl6p, w.gx2, h2, 0);
-      if (L <= 1024 && d->cols % 4 == 0 && gl <= 64 && (gl & (gl - 1)) == 0 && gemm_bwd_rows16(&gs, 1)) {
+      GemmArgs g = bwd_nt(B, h2, L, gZ_n, ldL, w.tl6p, w.gx2, h2, 0);
+      g.pre = tp.soft + (long long)t * B * L;
+      g.ld_pre = L;
+      g.C = d->cols;
+      const GemmPlan pl = gemm_plan(G_NT, AM_STEBWD, &g, 1);
+      if (gemm_bwd_fusable(pl)) {
         // straight-through softmax backward fused into the prior head's
         // input-gradient GEMM (its A-operand prologue)
-        GemmArgs g = bwd_nt(B, h2, L, gZ_n, ldL, w.tl6p, w.gx2, h2, 0);
-        g.pre = tp.soft + (long long)t * B * L;
-        g.ld_pre = L;
-        g.C = d->cols;
-        DR_TRY(run(G_NT, AM_STEBWD, g, s));
+        DR_TRY(gemm_run(pl, &g, 1, s));
       } else {
         DR_TRY(op_softmax_ste_bwd(B, d->rows, d->cols, gZ_n, ldL, tp.soft + (long long)t * B * L, L, w.glog, s));
         DR_TRY(run(G_NT, AM_PLAIN, bwd_nt(B, h2, L, w.glog, L, w.tl6p, w.gx2, h2, 0), s));

@@ -197,21 +197,19 @@ static inline int lnbwd_nt(int M, int N, int K, const float* gx, long long ldgx,
   GemmArgs g = bwd_nt(M, N, K, gx, ldgx, WT, Y, ldy, accumulate);
   g.Y2 = Y2; g.ldy2 = ldy2; g.nsplitY = nsplitY;
   if (gru_epi) g.gb = *gru_epi;
-  const bool r16 = gemm_bwd_rows16(&g, 1);
-  const bool ok = K % 4 == 0 && K <= (r16 ? 1024 : 256) && M <= 4096 && ldgx % 4 == 0 && ld_pre % 4 == 0 &&
-                  ((((uintptr_t)gx | (uintptr_t)pre | (uintptr_t)WT | (uintptr_t)ln.w | (uintptr_t)ln.b) & 15) == 0);
+  GemmArgs f = g;
+  f.pre = pre; f.ld_pre = ld_pre; f.ln_g = ln.w; f.ln_b = ln.b;
+  f.a_out = gpre; f.ld_aout = ld_gpre; f.sv_gy = gy; f.sv_xh = xh; f.ld_sv = ld_gpre;
+  const GemmPlan pl = gemm_plan(G_NT, AM_LNBWD, &f, 1);
+  const int rows = gemm_bwd_fusable(pl);  // the fused product's tile rows, 0: not fusable
+  const bool ok = rows && M <= 4096, r16 = rows == 16;
   // on 64-row tiles (tall problems) the staged prologue, recomputed by every
   // column tile, costs more than one elementwise pass + a plain GEMM (B = 256,
   // N = 1624: 26.5 us fused vs the two launches; the 200-wide layers 16.5 us
   // against 5.0 + 6.3, profiles/r03x_epoch_kernel_table.txt); on 16-row tiles
   // (per-step products up to ~2.5 dispatch rounds) the prologue is fused
   const bool split = gpre != nullptr && M >= 128 && !r16;
-  if (ok && !split) {
-    g.pre = pre; g.ld_pre = ld_pre; g.ln_g = ln.w; g.ln_b = ln.b;
-    g.a_out = gpre; g.ld_aout = ld_gpre;
-    g.sv_gy = gy; g.sv_xh = xh; g.ld_sv = ld_gpre;
-    return run(G_NT, AM_LNBWD, g, s);
-  }
+  if (ok && !split) return gemm_run(pl, &f, 1, s);
   DR_REQUIRE(gpre != nullptr, "LN-backward fallback needs a g_pre buffer");
   DR_TRY(op_ln_silu_bwd(M, K, gx, ldgx, pre, ld_pre, ln.w, ln.b, gpre, ld_gpre, gy, xh, s));
   g.A = gpre; g.lda = ld_gpre;

@@ -94,8 +94,38 @@ struct GemmBf16Scope {
 };
 // Launch up to 4 problems sharing layout/A-mode in one dispatch.
 int gemm_launch(GemmLayout lay, int amode, const GemmArgs* probs, int count, hipStream_t s);
-// true when AM_LNBWD / AM_STEBWD problems run on 16-row skinny tiles (K <= 1024)
-bool gemm_bwd_rows16(const GemmArgs* p, int count);
+
+// The route of a batch, decided on the host before anything is launched (gemm_launch: validate, plan, run the steps)
+enum GemmFamily {     // kernel<template selector from GemmStep>
+  GF_LEGACY = 0,      // k_gemm<bm, bn, amode, a_km, b_kn>
+  GF_SKINNY,          // k_gemm_skinny<bm, bn, amode, b_kn, vec, epi>
+  GF_TILE,            // k_gemm_tile<bm, bn, kc, a_km, b_kn, vec, nw>
+  GF_TILE_B16,        // k_gemm_tile_b16<bm, bn, nw>
+  GF_WK,              // k_gemm_wk<bm, bn, nw, 2, 1>
+  GF_WKS3,            // k_gemm_wks3<bf16 ? 1 : 3 planes, 1, nw, bm / 16, a16>
+  GF_LN_SAMPLE,       // k_ln_gemm_sample<kc> (kc = 16-k chunks)
+  GF_S3_TALL,         // conv_split.hip's split3 tall GEMM, one problem
+  GF_LN_ROWS,         // k_ln_silu_rows<kc> pre-pass of one problem (kc = float4 per lane)
+  GF_SPLITK_FINISH    // k_splitk_finish over the preceding tile step's partials
+};
+struct GemmStep {     // all int: dr_internal_gemm_plan copies it out as it is
+  int family, bm, bn, kc, nw, amode, a_km, b_kn, vec, epi, bf16, a16;
+  int mask;           // problems of the batch it covers (bit i), passed in batch order
+  int gx, gy, gz, block, lds;  // grid, block, dynamic LDS bytes
+  int splits, npack, no_ws;    // no_ws: the problems' split-K scratch withheld from the kernel
+};
+struct GemmPlan {
+  int rc; char err[192];  // DR_OK, or the error gemm_launch reports with `err`
+  int ln_pre, nsteps; // ln_pre: GF_LN_ROWS steps first; every later step reads their a_out as A (AM_PLAIN)
+  GemmStep step[10];  // <= 4 LN pre-passes, 4 tall split3, 1 batch, 1 split-K finish
+};
+// Pure host code: no HIP call, no pointer dereferenced (alignment and null tests only).
+GemmPlan gemm_plan(GemmLayout lay, int amode, const GemmArgs* probs, int count);
+// Runs a plan of these problems (gemm_launch = gemm_plan + gemm_run; a caller that asks the plan first runs that one).
+int gemm_run(const GemmPlan& pl, const GemmArgs* probs, int count, hipStream_t s);
+// Rows of the skinny tile (16 or 64) the plan of one AM_LNBWD / AM_STEBWD problem, all its fields set, runs it on;
+// 0 where the planner rejects the fused prologue.
+int gemm_bwd_fusable(const GemmPlan& pl);
 
 // The tail of the reference's 3-layer heads (Linear, LN, SiLU, Linear, LN,
 // SiLU, Linear -- DynamicsPredictors.py:15-23, Agent.py:180-190) from the

@@ -8,6 +8,8 @@
 // exact f32 fma (v_mfma_f32_16x16x4_f32), so results differ from the CPU
 // oracle only by summation order.
 #include <limits.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <stdint.h>
 #include <string.h>
@@ -45,11 +47,6 @@ __device__ __forceinline__ int dr_pack_tile(const GemmBatch& gb, int npack, int&
     z = i + 1;
   }
   return lt;
-}
-static int pack_tiles(const GemmBatch& gb, int count, int bm, int bn) {
-  int tot = 0;
-  for (int i = 0; i < count; ++i) tot += ((gb.p[i].M + bm - 1) / bm) * ((gb.p[i].N + bn - 1) / bn);
-  return tot;
 }
 
 static thread_local int g_gemm_bf16 = 0;
@@ -307,13 +304,10 @@ extern "C" int dr_debug_tbuf_gemm(long long* out, int n) {  // read, then clear
 }
 #endif
 #define SK_LN_MAXF 33280  // floats of staged LayerNorm rows (MT * (K + 4)); 130 KB of the 160 KB LDS
-#define SK_LN_MAXK 2048   // LayerNorm width staged with its gamma / beta
-#define SK_STAGE 8        // float4 staging loads in flight per thread
 // float4 per lane per staged row of an MT x NT skinny tile: 4 (K <= 1024) on
 // the 16-row tiles of up to 32 columns; the 48-column tile holds 6 weight rows
 // per wave in registers and stages K <= 256, like the 64-row tiles
 constexpr __host__ __device__ int sk_stage_vecs(int mt, int nt) { return (mt == 16 && nt <= 32) ? 4 : 1; }
-
 // hot operands of a skinny problem as wave-uniform scalars (see dr_uni)
 struct SkOps {
   const float *A, *A2, *W, *W2;
@@ -485,6 +479,26 @@ __device__ __forceinline__ void epilogue_store_pf(const GemmArgs& g, int m, int 
 }
 
 #define DR_SKW 8  // waves per skinny-GEMM workgroup (K split over them; 4 measured slower, r05)
+// k_gemm_skinny's tile predicates, one definition for the kernel and the planner (which sizes the dynamic LDS).
+#define SK_FN constexpr __host__ __device__
+SK_FN int sk_kpad(int K) { return K + ((8 - (K & 15)) & 15); }  // LDS row stride, 8 mod 16 dwords
+// staged: the tile's A and weight rows in LDS, prologue on the way (the K test first: the product stays an int)
+SK_FN bool sk_staged(int amode, int mt, int nt, int K, bool vec, bool b_kn) {
+  return (amode == AM_LNSILU || amode == AM_LNBWD || amode == AM_STEBWD) && vec && !b_kn &&
+         ((K >> 2) <= 64 * sk_stage_vecs(mt, nt)) && ((mt + nt) * sk_kpad(K) <= SK_LN_MAXF);
+}
+// direct path: float4 per lane per LayerNorm row held in LDS, and whether the rows are
+SK_FN int sk_ln_vecs(int mt) { return (mt == 16) ? 8 : 2; }
+SK_FN bool sk_ln_lds(int amode, int mt, int K, bool vec) {
+  return (amode == AM_LNSILU) && vec && ((K >> 2) <= 64 * sk_ln_vecs(mt)) && (mt * sk_kpad(K) <= SK_LN_MAXF);
+}
+// floats of the wave-partial reduction slab; of a tile's dynamic LDS: max(slab, staged tile or LN rows)
+SK_FN int sk_red_floats(int mt, int nt) { return DR_SKW * (mt / 16) * (nt / 16) * 4 * 64; }
+SK_FN int sk_lds_floats(int amode, int mt, int nt, int K, bool vec, bool b_kn) {
+  const int rows = sk_staged(amode, mt, nt, K, vec, b_kn) ? (mt + nt) * sk_kpad(K)
+                                                          : sk_ln_lds(amode, mt, K, vec) ? mt * sk_kpad(K) : 0;
+  return rows > sk_red_floats(mt, nt) ? rows : sk_red_floats(mt, nt);
+}
 template <int MT, int NT, int AMODE, bool B_KN, bool VEC, int EPI>
 __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int npack) {
   constexpr int NWAVE = DR_SKW, NTH = 64 * DR_SKW, FT = MT / 16, FN = NT / 16;
@@ -512,9 +526,9 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
   const int r = lane & 15, q = lane >> 4;
   DR_TS(dr_tbuf_gemm, 0);
 
-  // dynamic LDS, sized by the host for this launch (skinny_lds_floats):
+  // dynamic LDS, sized by the host for this launch (sk_lds_floats):
   // [ max(reduction slab, staged LN rows) | LN gamma (K) | LN beta (K) ]
-  constexpr int RED = NWAVE * FT * FN * 4 * 64;
+  constexpr int RED = sk_red_floats(MT, NT);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   __shared__ float s_mean[MT], s_rstd[MT];
   __shared__ float s_out[MT][NT + 1];
@@ -569,7 +583,7 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
   // with a padded stride (K + 4 floats: the 16 rows an MFMA fragment reads
   // fall in distinct banks); the K loop then reads fragments from LDS.
   // Direct (otherwise): each lane loads its MFMA fragments from global memory.
-  const int KP = K + ((8 - (K & 15)) & 15);  // row stride = 8 mod 16 dwords: ds_read_b128 fragments conflict-free
+  const int KP = sk_kpad(K);  // row stride = 8 mod 16 dwords: ds_read_b128 fragments conflict-free
   const int K4 = K >> 2;
   constexpr int RPW = MT / NWAVE;                    // A rows per wave
   constexpr int BPW = (NT + NWAVE - 1) / NWAVE;      // weight rows per wave
@@ -579,9 +593,7 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
   const bool store_a = (a_out != nullptr) && (tn == 0);
   // (measured: staging pays only where the LayerNorm needs the barrier anyway;
   // a plain GEMM is faster with direct fragment loads, profiles/r01_v5_kbench.txt)
-  const bool staged = (AMODE == AM_LNSILU || AMODE == AM_LNBWD || AMODE == AM_STEBWD) && VEC && !B_KN &&
-                     (K4 <= 64 * SV) &&
-                     ((MT + NT) * KP <= SK_LN_MAXF);
+  const bool staged = sk_staged(AMODE, MT, NT, K, VEC, B_KN);
   // with few accumulator tiles, alternate 16-k chunks between two accumulator
   // sets so consecutive MFMAs are independent (40-cycle result latency)
   constexpr bool DUAL = FT * FN < 4;
@@ -815,7 +827,7 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
 #pragma unroll
         for (int j = 0; j < FN; ++j) ac[t][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t].w, fb[j].w, ac[t][j], 0, 0, 0);
     }
-  } else if (AMODE != AM_LNBWD) {  // (the LayerNorm-backward prologue exists only staged: try_skinny's guard)
+  } else if (AMODE != AM_LNBWD) {  // (the LayerNorm-backward prologue exists only staged: plan_skinny's guard)
     // K loop in batches of PRE 16-k chunks: every load of a batch is issued
     // before its first MFMA, so a wave pays one memory round trip per batch
     // (one in total for K <= PRE*16*8 = 1024).  The first batch of weights (and
@@ -855,8 +867,8 @@ __global__ __launch_bounds__(64 * DR_SKW) void k_gemm_skinny(GemmBatch gb, int n
 
     // direct path: LayerNorm (when K > 1024) from global memory; large-K rows
     // staged (K <= 256 * LNV) like the staged path's A tile
-    constexpr int LNV = (MT == 16) ? 8 : 2;
-    const bool ln_lds = (AMODE == AM_LNSILU) && VEC && (MT * KP <= SK_LN_MAXF) && (K4 <= 64 * LNV);
+    constexpr int LNV = sk_ln_vecs(MT);
+    const bool ln_lds = sk_ln_lds(AMODE, MT, K, VEC);
     if (AMODE == AM_LNSILU) {
       if (ln_lds) {
         const float* lg = dr_uni(g.ln_g);
@@ -1347,7 +1359,6 @@ __global__ __launch_bounds__(256) void k_ln_gemm_sample(GemmArgs ga) {
 // applies the epilogue.
 // ---------------------------------------------------------------------------
 #define DR_TILE_SPLITS 4  // = DR_SPLITK_MAX (engine_util.h): scratch sized for it
-#define TBK 32  // k-chunk granularity of the split-K ranges (kernel chunks are a multiple)
 
 __device__ __forceinline__ float tile_b_kn(const GemmArgs& g, const float* W, int ldb, int n, int k) {
   if (k >= g.ksplitB) return dr_g(g.W2)[(long long)(k - g.ksplitB) * g.ldb2 + n];
@@ -2080,182 +2091,6 @@ __global__ __launch_bounds__(256) void k_splitk_finish(GemmBatch gb, int splits)
   epilogue_store(g, m, n, v);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static bool skinny_vec_ok(const GemmArgs& g, bool b_kn) {
-  if (g.K % 4 != 0 || !aligned16(g.A) || g.lda % 4 != 0) return false;
-  if (g.ksplitA < g.K && (!aligned16(g.A2) || g.lda2 % 4 != 0 || g.ksplitA % 4 != 0)) return false;
-  if (!b_kn && (!aligned16(g.W) || g.ldb % 4 != 0)) return false;
-  return true;
-}
-
-// the skinny kernel addresses A, A2, W and a_out with 32-bit element offsets
-static bool skinny_offsets_ok(const GemmArgs& g, bool b_kn) {
-  const long long lim = 1LL << 30;
-  if ((long long)g.M * g.lda >= lim || (long long)g.M * g.lda2 >= lim) return false;
-  if ((b_kn ? (long long)g.K * g.ldb : (long long)g.N * g.ldb) >= lim) return false;
-  if (g.W2 && (long long)(g.K + g.N) * g.ldb2 >= lim) return false;
-  if (g.a_out && (long long)g.M * g.ld_aout >= lim) return false;
-  return true;
-}
-
-// floats of dynamic LDS a skinny launch needs (mirrors the kernel's layout)
-template <int MT, int NT, int AMODE, bool B_KN>
-static size_t skinny_lds_floats(const GemmBatch& gb, int count, bool vec) {
-  const size_t red = (size_t)DR_SKW * (MT / 16) * (NT / 16) * 4 * 64;  // the kernel's RED
-  size_t need = red;
-  if (!vec) return need;
-  for (int i = 0; i < count; ++i) {
-    const size_t K = gb.p[i].K, KP = K + ((8 - (K & 15)) & 15);
-    const size_t staged = (size_t)(MT + NT) * KP, rows = (size_t)MT * KP;
-    if ((AMODE == AM_LNSILU || AMODE == AM_LNBWD || AMODE == AM_STEBWD) && !B_KN &&
-        K / 4 <= 64 * (size_t)sk_stage_vecs(MT, NT) &&
-        staged <= SK_LN_MAXF)
-      need = std::max(need, staged);  // kernel's `staged`
-    else if (AMODE == AM_LNSILU && rows <= SK_LN_MAXF && K / 4 <= 64 * (MT == 16 ? 8 : 2))
-      need = std::max(need, rows);  // direct path, LN rows in LDS
-  }
-  return need;
-}
-
-template <int MT, int NT, int AMODE, bool B_KN, int EPI>
-static void launch_skinny(const GemmBatch& gb, int count, bool vec, hipStream_t s) {
-  int maxt = 0;
-  for (int i = 0; i < count; ++i) {
-    const int t = dr_cdiv(gb.p[i].M, MT) * dr_cdiv(gb.p[i].N, NT);
-    maxt = t > maxt ? t : maxt;
-  }
-  if (maxt == 0) return;
-  const size_t lds = skinny_lds_floats<MT, NT, AMODE, B_KN>(gb, count, vec) * sizeof(float);
-  if (lds > 64 * 1024) {  // opt in to more than the default dynamic LDS (once per instantiation)
-    static const bool raised = [] {
-      (void)hipFuncSetAttribute((const void*)k_gemm_skinny<MT, NT, AMODE, B_KN, true, EPI>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      (void)hipFuncSetAttribute((const void*)k_gemm_skinny<MT, NT, AMODE, B_KN, false, EPI>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-      return true;
-    }();
-    (void)raised;
-  }
-  const int npack = count > 1 ? count : 0;
-  const dim3 grid(dr_xcd_grid(npack ? pack_tiles(gb, count, MT, NT) : maxt), 1, npack ? 1 : count);
-  if (vec)
-    hipLaunchKernelGGL((k_gemm_skinny<MT, NT, AMODE, B_KN, true, EPI>), grid, dim3(64 * DR_SKW), lds, s, gb, npack);
-  else
-    hipLaunchKernelGGL((k_gemm_skinny<MT, NT, AMODE, B_KN, false, EPI>), grid, dim3(64 * DR_SKW), lds, s, gb, npack);
-}
-
-
-
-// The staged backward prologues (AM_LNBWD, AM_STEBWD) run on 16-row tiles
-// (K <= 1024) when the problem has at most 64 rows or its 16 x 16 grid stays
-// within ~2.5 dispatch rounds (try_skinny), else on 64-row tiles (K <= 256).
-// (The 16 x 48 LayerNorm-backward tile try_skinny picks for a grid between one
-// and two rounds stages K <= 256 as well; wider K keeps 32 columns.)
-bool gemm_bwd_rows16(const GemmArgs* p, int count) {
-  int maxM = 0, t16 = 0;
-  for (int i = 0; i < count; ++i) {
-    maxM = std::max(maxM, p[i].M);
-    t16 += dr_cdiv(p[i].M, 16) * dr_cdiv(p[i].N, 16);
-  }
-  return maxM <= 64 || (maxM <= 4096 && t16 <= 640);
-}
-
-template <int AMODE, bool B_KN>
-static bool try_skinny(const GemmBatch& gb, int count, hipStream_t s) {
-  int maxM = 0, epi = EPI_NONE;
-  bool vec = true;
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    if (g.out_conv) return false;
-    if ((g.epi == EPI_SAMPLE) != (gb.p[0].epi == EPI_SAMPLE)) return false;  // 32-column tiles for all or none
-    if (g.epi != EPI_NONE) epi = g.epi;
-    maxM = g.M > maxM ? g.M : maxM;
-    if (!skinny_offsets_ok(g, B_KN)) return false;
-    vec = vec && skinny_vec_ok(g, B_KN);
-  }
-  // fused row epilogues are validated for M <= 4096 (gemm_launch); plain
-  // epilogues take any M the 32-bit offsets allow (64-row tiles past 64 rows)
-  if (maxM > (epi == EPI_NONE ? (1 << 20) : 4096)) return false;
-  // 16-row tiles past 64 rows while the grid stays within ~2.5 dispatch
-  // rounds: a B = 256 per-step product (N = 200) then spreads over 208
-  // workgroups instead of 52 (K = 1624: 19.3 -> 8.4 us, profiles/r02_kbench_B256.txt)
-  // (also the staged LayerNorm- and softmax-STE-backward prologues:
-  // at 64-row tiles a B = 256 LN-backward product ran on 52 workgroups, 16.5 us)
-  if (maxM > 64 && (AMODE == AM_PLAIN || AMODE == AM_LNSILU || AMODE == AM_LNBWD || AMODE == AM_STEBWD)) {
-    int t16 = 0;
-    for (int i = 0; i < count; ++i) t16 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, epi == EPI_SAMPLE ? 32 : 16);
-    if (t16 <= 640) maxM = 64;
-  }
-  // 16-column tiles by default; 32-column tiles when the 16-column grid would
-  // exceed one workgroup per CU (these 512-thread tiles hold 1 per CU by VGPRs,
-  // so a second dispatch round costs more than the wider tile's extra MFMAs)
-  int tiles16 = 0;
-  for (int i = 0; i < count; ++i)
-    tiles16 += dr_cdiv(gb.p[i].M, maxM > 64 ? 64 : 16) * dr_cdiv(gb.p[i].N, 16);
-  bool wide = maxM <= 64 && tiles16 > 256;
-  // The staged LayerNorm-backward tile holds one workgroup per CU, so its grid
-  // is never left between one and two dispatch rounds: where the 32-column
-  // grid has more than 256 and fewer than 512 tiles (a full round plus a tail
-  // that costs a whole second one) and 48 columns bring it to at most 256,
-  // the tile is 16 x 48.  B = 256, N = 600 (the BPTT's hidden-state gradient
-  // with the GRU backward in its epilogue): 304 tiles -> 208.  The tile stages
-  // K <= 256 (sk_stage_vecs); a shape it cannot stage keeps 32 columns.
-  bool wide48 = false;
-  if (AMODE == AM_LNBWD && epi == EPI_NONE && wide && vec) {
-    int t32 = 0, t48 = 0;
-    bool fits = true;
-    for (int i = 0; i < count; ++i) {
-      const int K = gb.p[i].K, KP = K + ((8 - (K & 15)) & 15);
-      t32 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, 32);
-      t48 += dr_cdiv(gb.p[i].M, 16) * dr_cdiv(gb.p[i].N, 48);
-      fits = fits && (16 + 48) * KP <= SK_LN_MAXF && K / 4 <= 64 * sk_stage_vecs(16, 48);
-    }
-    wide48 = fits && t32 > 256 && t32 < 512 && t48 <= 256;
-  }
-  // the backward prologues exist only on the staged path (A and weight rows of
-  // the tile in LDS, k_gemm_skinny `staged`): a tile whose rows do not fit
-  // would read the raw operand.  At K = 1024 (the STE backward of a 32 x 32
-  // latent) the 32-column tile does not fit (48 x 1032 floats), so a B = 512
-  // grid (416 16-column tiles) stays on 16 columns
-  if (AMODE == AM_LNBWD || AMODE == AM_STEBWD) {
-    const int mt = maxM > 64 ? 64 : 16;
-    for (int i = 0; i < count; ++i) {
-      const int K = gb.p[i].K, KP = K + ((8 - (K & 15)) & 15);
-      const int nt = (epi == EPI_SAMPLE || wide) ? 32 : 16;
-      if ((mt + nt) * KP > SK_LN_MAXF && nt == 32 && epi != EPI_SAMPLE) wide = false;
-      if ((mt + (wide || epi == EPI_SAMPLE ? 32 : 16)) * KP > SK_LN_MAXF || K / 4 > 64 * (mt == 16 ? 4 : 1) || !vec)
-        return false;
-    }
-  }
-  if (epi == EPI_SAMPLE) {
-    if (maxM > 64) launch_skinny<64, 32, AMODE, B_KN, EPI_SAMPLE>(gb, count, vec, s);
-    else launch_skinny<16, 32, AMODE, B_KN, EPI_SAMPLE>(gb, count, vec, s);
-  } else if (epi == EPI_ACTOR) {
-    if (maxM > 64) launch_skinny<64, 16, AMODE, B_KN, EPI_ACTOR>(gb, count, vec, s);
-    else launch_skinny<16, 16, AMODE, B_KN, EPI_ACTOR>(gb, count, vec, s);
-  } else {
-    if (maxM > 64) {
-      launch_skinny<64, 16, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
-    } else if (wide48) {
-      if constexpr (AMODE == AM_LNBWD) launch_skinny<16, 48, AM_LNBWD, B_KN, EPI_NONE>(gb, count, vec, s);
-    } else if (wide) launch_skinny<16, 32, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
-    else launch_skinny<16, 16, AMODE, B_KN, EPI_NONE>(gb, count, vec, s);
-  }
-  return true;
-}
-
-template <int BM, int BN, int AMODE, bool A_KM, bool B_KN>
-static void launch_tile(const GemmBatch& gb, int count, hipStream_t s) {
-  int maxt = 0;
-  for (int i = 0; i < count; ++i) {
-    const int t = dr_cdiv(gb.p[i].M, BM) * dr_cdiv(gb.p[i].N, BN);
-    maxt = t > maxt ? t : maxt;
-  }
-  if (maxt == 0) return;
-  hipLaunchKernelGGL((k_gemm<BM, BN, AMODE, A_KM, B_KN>), dim3(maxt, 1, count), dim3(256), 0, s, gb);
-}
-
 // ---------------------------------------------------------------------------
 // k_mlp2_tail: LN-SiLU -> Linear -> LN-SiLU -> Linear (+ epilogue), one launch
 // ---------------------------------------------------------------------------
@@ -2523,360 +2358,6 @@ int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s) {
 }
 
 
-// mid-size GEMMs: LDS double-buffered tile kernel, split-K when the tile grid
-// is too small to fill the chip and every problem brought scratch for it
-template <int BM, int BN, int KC, bool A_KM, bool B_KN, int NW = 4>
-static void launch_tile2(GemmBatch& gb, int count, hipStream_t s) {
-  int maxt = 0, nch = 1 << 30, tot = 0;
-  long long maxMN = 0;
-  bool vec = true, ws = true;
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    const int t = dr_cdiv(g.M, BM) * dr_cdiv(g.N, BN);
-    maxt = std::max(maxt, t);
-    tot += t;
-    nch = std::min(nch, dr_cdiv(g.K, KC));
-    maxMN = std::max(maxMN, (long long)g.M * g.N);
-    if (!A_KM) {
-      vec = vec && g.K % 4 == 0 && g.lda % 4 == 0 && aligned16(g.A);
-      if (g.ksplitA < g.K) vec = vec && g.lda2 % 4 == 0 && g.ksplitA % 4 == 0 && aligned16(g.A2);
-    }
-    if (!B_KN) vec = vec && g.ldb % 4 == 0 && aligned16(g.W);
-    ws = ws && g.splitk_ws != nullptr;
-  }
-  if (maxt == 0) return;
-  int splits = 1;
-  if (ws) {
-    // about two workgroups per CU over the problems' real tiles (the grid's
-    // surplus blocks of the smaller problems exit at once)
-    splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(512, tot)));
-    splits = std::min(splits, std::max(1, nch / 2));  // at least 2 chunks per split
-    for (int i = 0; i < count; ++i)
-      while (splits > 1 && (long long)splits * gb.p[i].M * gb.p[i].N > gb.p[i].splitk_floats) --splits;
-  }
-  const int npack = count > 1 ? count : 0;
-  dim3 grid(dr_xcd_grid(npack ? tot : maxt), splits, npack ? 1 : count);
-  if (vec) hipLaunchKernelGGL((k_gemm_tile<BM, BN, KC, A_KM, B_KN, true, NW>), grid, dim3(64 * NW), 0, s, gb, splits, npack);
-  else hipLaunchKernelGGL((k_gemm_tile<BM, BN, KC, A_KM, B_KN, false, NW>), grid, dim3(64 * NW), 0, s, gb, splits, npack);
-  if (splits > 1)
-    hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)((maxMN + 255) / 256), 1, count), dim3(256), 0, s, gb, splits);
-}
-
-
-// bf16 tile launcher: split-K as launch_tile2 (partials + k_splitk_finish)
-template <int BM, int BN, int NW>
-static void launch_tile_b16(GemmBatch& gb, int count, hipStream_t s) {
-  int maxt = 0, nch = 1 << 30, tot = 0;
-  long long maxMN = 0;
-  bool ws = true;
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    const int t = dr_cdiv(g.M, BM) * dr_cdiv(g.N, BN);
-    maxt = std::max(maxt, t);
-    tot += t;
-    nch = std::min(nch, dr_cdiv(g.K, 64));
-    maxMN = std::max(maxMN, (long long)g.M * g.N);
-    ws = ws && g.splitk_ws != nullptr;
-  }
-  if (maxt == 0) return;
-  int splits = 1;
-  if (ws && tot < 256) {
-    splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(512, tot)));
-    splits = std::min(splits, std::max(1, nch / 2));
-    for (int i = 0; i < count; ++i)
-      while (splits > 1 && (long long)splits * gb.p[i].M * gb.p[i].N > gb.p[i].splitk_floats) --splits;
-  }
-  dim3 grid(dr_xcd_grid(maxt), splits, count);
-  hipLaunchKernelGGL((k_gemm_tile_b16<BM, BN, NW>), grid, dim3(64 * NW), 0, s, gb, splits);
-  if (splits > 1)
-    hipLaunchKernelGGL(k_splitk_finish, dim3((unsigned)((maxMN + 255) / 256), 1, count), dim3(256), 0, s, gb, splits);
-}
-
-// wave-K chain kernel: 8-wide k runs on 16-byte boundaries in every operand
-static bool wk_ok(const GemmBatch& gb, int count) {
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    if (g.K % 8 || g.K < 8 || g.lda % 4 || g.ldb % 4 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return false;
-    if (g.ksplitA < g.K && (g.ksplitA % 8 || g.lda2 % 4 || ((uintptr_t)g.A2 & 15))) return false;
-    if (g.W2 || g.epi != EPI_NONE || g.out_conv || g.M < 1 || g.N < 1) return false;
-  }
-  return true;
-}
-
-// every problem with pre-split weight planes and the wave-K shape (NT, no second
-// A segment or B segment, K % 8 == 0, 16-byte aligned rows, 32-bit offsets)
-static bool wks3_ok(const GemmBatch& gb, int count) {
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    if (!g.wsplit || g.wsplit_np < ((g.N + 31) & ~31) || g.K % 8 || g.K < 8 || g.lda % 4 || ((uintptr_t)g.A & 15) ||
-        ((uintptr_t)g.wsplit & 15) || g.ksplitA < g.K || g.W2 || g.epi != EPI_NONE || g.out_conv || g.M < 1 || g.N < 1 ||
-        (long long)g.M * g.lda >= (1LL << 30) || (long long)((g.K + 31) / 32) * 3 * g.wsplit_np * 32 >= (1LL << 30))
-      return false;
-  }
-  return true;
-}
-// 4 waves per 32 x 32 (bf16: 16 x 32) tile, each over its own run of
-// k-chunks through a register ring (r04g: 8 waves, whole-wave prefetch and A
-// planes measured slower, profiles/r04g_ab_wks3.txt, r04t_ab_aplanes.txt)
-// (r06o / r06p: the K loop fully unrolled -- the rolled loop's back edge makes
-// the compiler wait for every outstanding load at each chunk, so the ring never
-// overlaps loads with MFMAs; unrolled, the waits are per slot -- bitwise the
-// same epoch, and no faster: B = 256 fp32 596 -> 596 k, bf16 909 -> 900 k (864 k
-// unrolled for short K too), B = 128 fp32 446 -> 454 k; not kept,
-// profiles/r06p_ab_wks3_unroll.txt.  The per-wave latency chain is not what
-// bounds these launches.)
-// (r05w: 64-row tiles, each weight plane read by half as many row tiles,
-// measured slower -- 548 k vs 566 k fp32, 776 k vs 803 k bf16 at B = 256)
-// register-ring depth (K chunks in flight per wave).  1: the fp32 kernel at 83
-// VGPRs (4 waves per SIMD) instead of 140 (3), bf16 48 instead of 86 (7 / 4):
-// fp32 headline 581 -> 592 k, bf16 818 -> 828 k; depth 3 / 4 slower still
-// than 2 (profiles/r05zf_ab_wks3_depth.txt)
-#define DR_WKS3_D 1
-// 16-row fragments per tile: 2 (32 x 32 tiles) for the fp32 products, 1 for
-// bf16 mode's (16 x 32 tiles: 828 -> 838 k bf16 headline; fp32 595 -> 587 k,
-// kept at 2; 8 or 2 waves per tile: +0.2 % / -6 %, profiles/r05zh_ab_wks3_shape.txt)
-// (64-column tiles, half the A re-reads: fp32 32 x 64 596 -> 567 k, 16 x 64
-// 567 k, bf16 16 x 64 917 -> 899 k; not kept, profiles/r06w_ab_wks3_columns.txt)
-#define DR_WKS3_NW 4  // waves per tile (each a 1/NW share of K)
-#define DR_WKS3_FM 2
-#define DR_WKS3_FM_B16 1
-static void launch_wks3(const GemmBatch& gb, int count, hipStream_t s, bool bf16) {
-  const int fm = bf16 ? DR_WKS3_FM_B16 : DR_WKS3_FM;
-  int tot = 0, maxt = 0;
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    const int t = dr_cdiv(g.M, 16 * fm) * dr_cdiv(g.N, 32);
-    tot += t;
-    maxt = std::max(maxt, t);
-  }
-  const int npack = count > 1 ? count : 0;
-  const dim3 grid(dr_xcd_grid(npack ? tot : maxt));
-  const dim3 blk(64 * DR_WKS3_NW);
-  // bf16 A copies from the producers where every problem of the batch has one
-  // (bitwise the same epoch; bf16 headline B = 256 891 -> 909 k, profiles/r06n_ab_a16_convT_cls.txt)
-  bool a16 = bf16;
-  for (int i = 0; i < count && a16; ++i) {
-    const GemmArgs& g = gb.p[i];
-    a16 = g.A16 && ((uintptr_t)g.A16 & 15) == 0 && g.lda % 8 == 0;
-  }
-  if (a16)
-    hipLaunchKernelGGL((k_gemm_wks3<1, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM_B16, true>), grid, blk, 0, s, gb, npack);
-  else if (bf16) hipLaunchKernelGGL((k_gemm_wks3<1, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM_B16>), grid, blk, 0, s, gb, npack);
-  else hipLaunchKernelGGL((k_gemm_wks3<3, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM>), grid, blk, 0, s, gb, npack);
-}
-
-// the wave-K chain kernel on 32 x 32 tiles, 4 waves, ring depth 2, no split-K
-static void launch_wk(const GemmBatch& gb, int count, hipStream_t s) {
-  int maxt = 0, tot = 0;
-  for (int i = 0; i < count; ++i) {
-    const int t = dr_cdiv(gb.p[i].M, 32) * dr_cdiv(gb.p[i].N, 32);
-    maxt = std::max(maxt, t);
-    tot += t;
-  }
-  if (maxt == 0) return;
-  const int npack = count > 1 ? count : 0;
-  hipLaunchKernelGGL((k_gemm_wk<32, 32, 4, 2, 1>), dim3(dr_xcd_grid(npack ? tot : maxt), 1, 1), dim3(256), 0, s, gb, 1,
-                     npack);
-}
-
-// every problem bf16 and 16-byte-aligned 8-wide k runs (ksplitA on an 8 boundary)
-static bool b16_ok(const GemmBatch& gb, int count) {
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    if (!g.bf16 || g.K % 8 || g.lda % 4 || g.ldb % 4 || ((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return false;
-    if (g.ksplitA < g.K && (g.ksplitA % 8 || g.lda2 % 4 || ((uintptr_t)g.A2 & 15))) return false;
-    if (g.W2 || g.epi != EPI_NONE || g.out_conv) return false;
-  }
-  return true;
-}
-
-static bool tile_offsets_ok(const GemmBatch& gb, int count) {
-  const long long lim = 1LL << 30;
-  for (int i = 0; i < count; ++i) {
-    const GemmArgs& g = gb.p[i];
-    const long long arows = std::max((long long)g.M, (long long)g.K), brows = std::max((long long)g.N, (long long)g.K);
-    if (arows * g.lda >= lim || arows * g.lda2 >= lim || brows * g.ldb >= lim) return false;
-    if (g.epi != EPI_NONE || g.out_conv) return false;
-  }
-  return true;
-}
-
-// tall NT products (>= 1024 rows) whose caller split the weights into planes,
-// f32 mode: the split3 tall GEMM of conv_split.hip (k_gemm_split3) with the
-// data-gradient epilogue (accumulate, split output).  The world-model
-// backward's K = 200 input gradients ran on the f32 tile kernel at ~21 TF/s.
-int op_gemm_nt_split3_ex(int M, int N, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
-                         const void* wr, const float* bias, int act, float* Y, int ldy, int accumulate, float* Y2,
-                         int ldy2, int nsplitY, float* part, size_t part_floats, hipStream_t s, int splits_fixed);
-static bool s3_tall_ok(const GemmArgs& g) {
-  const bool seg = g.ksplitA < g.K;  // second A segment (A2 at k >= ksplitA)
-  return g.wsplit && !g.bf16 && g.M >= 1024 && g.epi == EPI_NONE && !g.out_conv && !g.W2 && !g.addend &&
-         g.alpha == 1.0f && (g.act == 0 || g.act == 1) &&
-         (!seg || (g.A2 && aligned16(g.A2) && g.ksplitA % 4 == 0 && g.lda2 % 4 == 0 &&
-                   (long long)g.M * g.lda2 < (1LL << 31))) &&
-         g.wsplit_np == (g.N + 127) / 128 * 128 &&
-         g.N % 4 == 0 && g.K % 4 == 0 && g.lda % 4 == 0 && g.ldy % 4 == 0 && aligned16(g.A) && aligned16(g.Y) &&
-         (!g.bias || aligned16(g.bias)) && (g.nsplitY >= g.N || (g.Y2 && aligned16(g.Y2) && g.ldy2 % 4 == 0 &&
-                                                                  g.nsplitY % 4 == 0)) &&
-         (long long)g.M * g.lda < (1LL << 31) && g.lda < INT_MAX && g.ldy < INT_MAX && g.ldy2 < INT_MAX;
-}
-
-// bf16 mode's chain products without weight planes on k_gemm_tile_b16 (the
-// f32 wave-K kernel measured 723.3 k against 730.5 k bf16 headline,
-// profiles/r03zf_ab_bf16_chain_route.txt)
-template <int AMODE, bool A_KM, bool B_KN>
-static int launch_pick(const GemmBatch& gb, int count, hipStream_t s) {
-  if (AMODE == AM_PLAIN && !A_KM && !B_KN) {
-    // problems of the batch that qualify run one after another on the split3
-    // tall GEMM, the rest as a (smaller) batch below
-    GemmBatch rest;
-    int nrest = 0;
-    for (int i = 0; i < count; ++i) {
-      const GemmArgs& g = gb.p[i];
-      if (!s3_tall_ok(g)) {
-        rest.p[nrest++] = g;
-        continue;
-      }
-      // (the 200-wide, K <= 1024 problems on the wave-K split3 kernel's 32 x 32
-      // tiles instead -- it fills the chip where 64 x 64 tiles leave ~450 waves
-      // -- measured the same WM step, r06t: not kept)
-      DR_TRY(op_gemm_nt_split3_ex(g.M, g.N, g.K, g.A, (int)g.lda, g.A2, (int)g.lda2, g.ksplitA < g.K ? g.ksplitA : g.K,
-                                  g.wsplit, g.bias, g.act, g.Y, (int)g.ldy, g.accumulate, g.Y2, (int)g.ldy2,
-                                  g.nsplitY < g.N ? g.nsplitY : INT_MAX, g.splitk_ws,
-                                  g.splitk_ws ? (size_t)g.splitk_floats : 0, s, 0));
-    }
-    if (nrest == 0) return DR_OK;
-    if (nrest < count) return launch_pick<AMODE, A_KM, B_KN>(rest, nrest, s);
-  }
-  if (AMODE == AM_PLAIN && tile_offsets_ok(gb, count)) {
-    int maxM = 0, minK = 1 << 30, tiles = 0;
-    bool ws = true;
-    for (int i = 0; i < count; ++i) {
-      maxM = std::max(maxM, gb.p[i].M);
-      minK = std::min(minK, gb.p[i].K);
-      tiles += dr_cdiv(gb.p[i].M, 64) * dr_cdiv(gb.p[i].N, 64);
-      ws = ws && gb.p[i].splitk_ws != nullptr;
-    }
-    // per-step products at 128-512 rows with a deep K (BPTT input gradients,
-    // K = 1800; the heads' first layers, K = 1624) or a wide N (the GRU's
-    // hidden product): 32 x 32 tiles, K chunks of 64, split-K only while the
-    // tile grid is under one workgroup per CU.  Against the 16/64-row skinny
-    // tiles, which re-read the weights per row tile and the activations per
-    // 16 columns: 44 -> 32 us (BPTT, 2 problems), 23 -> 15 us (heads, 3
-    // problems, split-K 4), profiles/r02h_kbench_tile_B256.txt
-    // shallow-K products the caller gave weight planes (the BPTT's actor
-    // input gradient, K = 200, N = 1624): the wave-K split3 kernel
-    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512 && minK < 512 && wks3_ok(gb, count)) {
-      launch_wks3(gb, count, s, b16_ok(gb, count));
-      return DR_OK;
-    }
-    if (!A_KM && !B_KN && maxM >= 128 && maxM <= 512) {
-      int tiles32 = 0;
-      for (int i = 0; i < count; ++i) tiles32 += dr_cdiv(gb.p[i].M, 32) * dr_cdiv(gb.p[i].N, 32);
-      // (f32 under ~112 tiles -- one per-step Linear of 200 outputs, K = 1624 --
-      // the 16-row skinny tiles spread wider: 8.4 against 13.0 us)
-      if ((minK >= 1024 && (tiles32 >= 112 || b16_ok(gb, count))) || (minK >= 512 && tiles32 >= 256)) {
-        GemmBatch gt = gb;
-        if (tiles32 >= 256)
-          for (int i = 0; i < count; ++i) gt.p[i].splitk_ws = nullptr;
-        // f32: the wave-K kernel (32 x 32 tiles, 4 waves, no split-K: heads
-        // 15.8 -> 13.0 us, BPTT 32.2 -> 25.7, GRU hidden product 13.3 -> 12.3,
-        // profiles/r03g_kbench_wk.txt); the LDS tile kernel stays for the
-        // shapes the wave-K kernel does not take
-        if (wks3_ok(gb, count)) launch_wks3(gt, count, s, b16_ok(gb, count));
-        else if (b16_ok(gb, count)) launch_tile_b16<32, 32, 4>(gt, count, s);
-        else if (wk_ok(gb, count)) launch_wk(gt, count, s);
-        else launch_tile2<32, 32, 64, false, false, 4>(gt, count, s);
-        return DR_OK;
-      }
-    }
-    // weight gradients (TN) and tall, deep products go to the tile kernel --
-    // when it can fill the chip: a per-step product at B = 256 (16 tiles of
-    // 64 x 64, no split-K scratch) runs on 52+ skinny 64-row workgroups instead
-    // tall products with a small K (M >= 1024: the world-model heads' and
-    // decoder's layers over B (T - 1) rows, the critic's over B (H + 1)): the
-    // 64-row skinny tiles re-read the weights per row tile and run 16 columns
-    // per workgroup (480 us for the decoder's 3584 x 4096 x 200 product)
-    const bool tall = !A_KM && !B_KN && maxM >= 1024 && tiles >= 256;
-    if (A_KM || (maxM >= 256 && minK >= 512 && (ws || tiles >= 128)) || tall) {
-      GemmBatch gt = gb;
-      // tall NT products with a deep K (the encoder feature projection, the
-      // critic's first layer over B*(H+1) rows): 8 waves as 4 x 2 over 64 x 64
-      // with K chunks of 64 -- 198 -> 171 us (M 8192, K 4096), 51 -> 47 us
-      // (M 4096, K 1624), profiles/r02m_kbench_tall_tiles.txt
-      if (!A_KM && !B_KN && minK >= 1024) {
-        if (b16_ok(gb, count)) launch_tile_b16<64, 64, 8>(gt, count, s);
-        else launch_tile2<64, 64, 64, false, false, 8>(gt, count, s);
-      } else {
-        launch_tile2<64, 64, 32, A_KM, B_KN>(gt, count, s);
-      }
-      return DR_OK;
-    }
-  }
-  if (AMODE == AM_LNBWD) {
-    if (!A_KM && !B_KN && try_skinny<AM_LNBWD, false>(gb, count, s)) return DR_OK;
-    dr_set_error("gemm: LayerNorm-backward prologue needs the staged NT skinny path");
-    return DR_E_INVALID;
-  }
-  if (AMODE == AM_STEBWD) {
-    if (!A_KM && !B_KN && try_skinny<AM_STEBWD, false>(gb, count, s)) return DR_OK;
-    dr_set_error("gemm: softmax-STE-backward prologue needs the staged NT skinny path");
-    return DR_E_INVALID;
-  }
-  if (!A_KM && (AMODE == AM_PLAIN || AMODE == AM_LNSILU)) {
-    if (try_skinny<(AMODE == AM_LNSILU ? AM_LNSILU : AM_PLAIN), B_KN>(gb, count, s)) return DR_OK;
-  }
-  long long work = 0;
-  for (int i = 0; i < count; ++i) work += (long long)gb.p[i].M * gb.p[i].N;
-  // large problems: 64x64 tiles; small (per-step, M = batch rows): 32x32 tiles
-  // so that the launch spreads over more CUs.
-  if (work >= 256LL * 1024) launch_tile<64, 64, AMODE, A_KM, B_KN>(gb, count, s);
-  else launch_tile<32, 32, AMODE, A_KM, B_KN>(gb, count, s);
-  return DR_OK;
-}
-
-// the sampler-head kernel's shape: one LN-SiLU NT problem, C = 32, K <= 256
-static bool ln_sample_ok(const GemmArgs& g) {
-  return g.epi == EPI_SAMPLE && g.C == 32 && g.R * g.C == g.N && g.N % LS_NT == 0 && g.K > 0 && g.K % 4 == 0 &&
-         g.K <= LS_KMAX && g.M > 0 && g.M <= 65536 && g.ln_g && g.ln_b && g.ksplitA >= g.K && !g.addend &&
-         g.alpha == 1.0f && g.act == 0 && !g.accumulate && !g.W2 && aligned16(g.A) && aligned16(g.W) &&
-         aligned16(g.ln_g) && aligned16(g.ln_b) && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
-         (!g.a_out || (aligned16(g.a_out) && g.ld_aout % 4 == 0)) && skinny_offsets_ok(g, false) &&
-         (long long)g.M * g.ldz < (1LL << 31) && aligned16(g.z_out) && g.ldz % 4 == 0 &&
-         (!g.soft_out || (aligned16(g.soft_out) && g.ld_soft % 4 == 0)) && (!g.noise.q || aligned16(g.noise.q));
-}
-
-template <int NK>
-static int launch_ln_sample_nk(const GemmArgs& g, hipStream_t s) {
-  const size_t lds = ln_sample_lds_bytes(g.K);
-  if (lds > 64 * 1024) {
-    static const bool raised = [] {
-      (void)hipFuncSetAttribute((const void*)k_ln_gemm_sample<NK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)ln_sample_lds_bytes(16 * NK));
-      return true;
-    }();
-    (void)raised;
-  }
-  const int tiles = dr_cdiv(g.M, LS_MT) * (g.N / LS_NT);
-  hipLaunchKernelGGL(k_ln_gemm_sample<NK>, dim3(dr_xcd_grid(tiles)), dim3(256), lds, s, g);
-  return dr_check_launch("ln_gemm_sample");
-}
-
-static int launch_ln_sample(const GemmArgs& g, hipStream_t s) {
-  switch ((g.K + 15) >> 4) {  // ln_sample_ok: 0 < K <= LS_KMAX
-#define DR_LS_CASE(n) \
-  case n:             \
-    return launch_ln_sample_nk<n>(g, s);
-    DR_LS_CASE(1) DR_LS_CASE(2) DR_LS_CASE(3) DR_LS_CASE(4) DR_LS_CASE(5) DR_LS_CASE(6) DR_LS_CASE(7)
-    DR_LS_CASE(8) DR_LS_CASE(9) DR_LS_CASE(10) DR_LS_CASE(11) DR_LS_CASE(12) DR_LS_CASE(13) DR_LS_CASE(14)
-    DR_LS_CASE(15) DR_LS_CASE(16)
-#undef DR_LS_CASE
-    default:
-      dr_set_error("ln_gemm_sample: K %d out of range", g.K);
-      return DR_E_INVALID;
-  }
-}
-
 // SiLU(LayerNorm(x)) of whole rows, one wave per row: the staged prologue of
 // k_gemm_skinny (same lane -> k mapping and summation order, so the same
 // values) as its own pass for tall products, whose consumers then run a plain
@@ -2925,6 +2406,356 @@ __global__ __launch_bounds__(256) void k_ln_silu_rows(int M, int K, const float*
   }
 }
 
+// ---- Host side.  gemm_plan decides the route of a batch; gemm_launch validates
+// the arguments, plans, and runs the plan's steps (one switch per family).
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// the problems a route covers, in batch order
+struct PlanProbs {
+  const GemmArgs* p[4];
+  int mask = 0, n = 0;
+  void add(const GemmArgs* g, int i) { p[n++] = g; mask |= 1 << i; }
+  const GemmArgs& operator[](int i) const { return *p[i]; }
+};
+static void plan_fail(GemmPlan& pl, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(pl.err, sizeof(pl.err), fmt, ap);
+  va_end(ap);
+  pl.rc = DR_E_INVALID;
+}
+static GemmStep& plan_step(GemmPlan& pl, int family, int mask, int gx, int gy, int gz, int block) {
+  GemmStep& st = pl.step[pl.nsteps++] = GemmStep{};
+  st.family = family; st.mask = mask; st.gx = gx; st.gy = gy; st.gz = gz; st.block = block;
+  return st;
+}
+// 16-byte rows of k runs of kq floats: A (with its second segment) and / or W
+static bool rows_aligned(const GemmArgs& g, int kq, bool a, bool w) {
+  if (a && (g.K % kq != 0 || g.lda % 4 != 0 || !aligned16(g.A))) return false;
+  if (a && g.ksplitA < g.K && (g.ksplitA % kq != 0 || g.lda2 % 4 != 0 || !aligned16(g.A2))) return false;
+  return !w || (g.ldb % 4 == 0 && aligned16(g.W));
+}
+// tiles of the largest problem (a blockIdx.z slice) and of all (a packed grid); every problem with split-K
+// scratch; the batch's most rows and shallowest K
+struct TileCount { int maxt, tot; bool ws; int maxM, minK; };
+static TileCount tile_count(const PlanProbs& q, int bm, int bn) {
+  TileCount c = {0, 0, true, 0, 1 << 30};
+  for (int i = 0; i < q.n; ++i) {
+    const int t = dr_cdiv(q[i].M, bm) * dr_cdiv(q[i].N, bn);
+    c.maxt = std::max(c.maxt, t);
+    c.tot += t;
+    c.ws = c.ws && q[i].splitk_ws != nullptr;
+    c.maxM = std::max(c.maxM, q[i].M);
+    c.minK = std::min(c.minK, q[i].K);
+  }
+  return c;
+}
+// split-K of the tile kernels, every problem with scratch: about two workgroups
+// per CU over the problems' real tiles (the grid's surplus blocks of the
+// smaller problems exit at once)
+static int splitk_count(const PlanProbs& q, int tot, int kc) {
+  int nch = 1 << 30;
+  for (int i = 0; i < q.n; ++i) nch = std::min(nch, dr_cdiv(q[i].K, kc));
+  int splits = std::max(1, std::min(DR_TILE_SPLITS, dr_cdiv(512, tot)));
+  splits = std::min(splits, std::max(1, nch / 2));  // at least 2 chunks per split
+  for (int i = 0; i < q.n; ++i)
+    while (splits > 1 && (long long)splits * q[i].M * q[i].N > q[i].splitk_floats) --splits;
+  return splits;
+}
+
+// the skinny kernel addresses A, A2, W and a_out with 32-bit element offsets
+static bool skinny_offsets_ok(const GemmArgs& g, bool b_kn) {
+  const long long lim = 1LL << 30;
+  return (long long)g.M * g.lda < lim && (long long)g.M * g.lda2 < lim && (long long)(b_kn ? g.K : g.N) * g.ldb < lim &&
+         !(g.W2 && (long long)(g.K + g.N) * g.ldb2 >= lim) && !(g.a_out && (long long)g.M * g.ld_aout >= lim);
+}
+
+// Rows of a skinny tile: 16 up to 64 rows, else 64 -- and
+// 16-row tiles past 64 rows while the grid stays within ~2.5 dispatch
+// rounds: a B = 256 per-step product (N = 200) then spreads over 208
+// workgroups instead of 52 (K = 1624: 19.3 -> 8.4 us, profiles/r02_kbench_B256.txt)
+// (also the staged LayerNorm- and softmax-STE-backward prologues:
+// at 64-row tiles a B = 256 LN-backward product ran on 52 workgroups, 16.5 us)
+static int skinny_tile_rows(const PlanProbs& q, int amode, int maxM, bool sample) {
+  if (maxM <= 64) return 16;
+  if (amode != AM_PLAIN && amode != AM_LNSILU && amode != AM_LNBWD && amode != AM_STEBWD) return 64;
+  return tile_count(q, 16, sample ? 32 : 16).tot <= 640 ? 16 : 64;
+}
+
+// k_gemm_skinny; false where the batch does not take it
+static bool plan_skinny(GemmPlan& pl, const PlanProbs& q, int amode, bool b_kn) {
+  int maxM = 0, epi = EPI_NONE;
+  bool vec = true;
+  for (int i = 0; i < q.n; ++i) {
+    const GemmArgs& g = q[i];
+    if (g.out_conv) return false;
+    if ((g.epi == EPI_SAMPLE) != (q[0].epi == EPI_SAMPLE)) return false;  // 32-column tiles for all or none
+    if (g.epi != EPI_NONE) epi = g.epi;
+    maxM = g.M > maxM ? g.M : maxM;
+    if (!skinny_offsets_ok(g, b_kn)) return false;
+    vec = vec && rows_aligned(g, 4, true, !b_kn);
+  }
+  // fused row epilogues are validated for M <= 4096 (gemm_plan); plain
+  // epilogues take any M the 32-bit offsets allow (64-row tiles past 64 rows)
+  if (maxM > (epi == EPI_NONE ? (1 << 20) : 4096)) return false;
+  const int mt = skinny_tile_rows(q, amode, maxM, epi == EPI_SAMPLE);
+  // 16-column tiles by default; 32-column tiles when the 16-column grid would
+  // exceed one workgroup per CU (these 512-thread tiles hold 1 per CU by VGPRs,
+  // so a second dispatch round costs more than the wider tile's extra MFMAs)
+  bool wide = mt == 16 && tile_count(q, 16, 16).tot > 256;
+  // The staged LayerNorm-backward tile holds one workgroup per CU, so its grid
+  // is never left between one and two dispatch rounds: where the 32-column
+  // grid has more than 256 and fewer than 512 tiles (a full round plus a tail
+  // that costs a whole second one) and 48 columns bring it to at most 256,
+  // the tile is 16 x 48.  B = 256, N = 600 (the BPTT's hidden-state gradient
+  // with the GRU backward in its epilogue): 304 tiles -> 208.  The tile stages
+  // K <= 256 (sk_stage_vecs); a shape it cannot stage keeps 32 columns.
+  bool wide48 = false;
+  if (amode == AM_LNBWD && epi == EPI_NONE && wide && vec) {
+    const int t32 = tile_count(q, 16, 32).tot;
+    wide48 = t32 > 256 && t32 < 512 && tile_count(q, 16, 48).tot <= 256;
+    for (int i = 0; i < q.n; ++i) wide48 = wide48 && sk_staged(amode, 16, 48, q[i].K, vec, b_kn);
+  }
+  // the backward prologues exist only on the staged path (A and weight rows of
+  // the tile in LDS, sk_staged): a tile whose rows do not fit
+  // would read the raw operand.  At K = 1024 (the STE backward of a 32 x 32
+  // latent) the 32-column tile does not fit (48 x 1032 floats), so a B = 512
+  // grid (416 16-column tiles) stays on 16 columns
+  const bool bwd = amode == AM_LNBWD || amode == AM_STEBWD;
+  if (bwd && wide && !wide48 && epi != EPI_SAMPLE)
+    for (int i = 0; i < q.n; ++i) wide = wide && sk_staged(amode, 16, 32, q[i].K, vec, b_kn);
+  const int nt = epi == EPI_SAMPLE ? 32 : (epi == EPI_ACTOR || mt == 64) ? 16 : wide48 ? 48 : wide ? 32 : 16;
+  int lds = 0;
+  for (int i = 0; i < q.n; ++i) {
+    if (bwd && !sk_staged(amode, mt, nt, q[i].K, vec, b_kn)) return false;
+    lds = std::max(lds, sk_lds_floats(amode, mt, nt, q[i].K, vec, b_kn));
+  }
+  const TileCount tc = tile_count(q, mt, nt);
+  if (tc.maxt == 0) return true;
+  const int npack = q.n > 1 ? q.n : 0;
+  GemmStep& st =
+      plan_step(pl, GF_SKINNY, q.mask, dr_xcd_grid(npack ? tc.tot : tc.maxt), 1, npack ? 1 : q.n, 64 * DR_SKW);
+  st.bm = mt; st.bn = nt; st.amode = amode; st.b_kn = b_kn; st.vec = vec; st.epi = epi; st.npack = npack;
+  st.lds = lds * (int)sizeof(float);
+  return true;
+}
+
+// mid-size GEMMs: LDS double-buffered tile kernel (k_gemm_tile, or bf16 mode's
+// k_gemm_tile_b16: kc = 64, no packed grid, split-K under 256 tiles only),
+// split-K when the tile grid is too small to fill the chip and every problem
+// brought scratch for it (partials + k_splitk_finish)
+static void plan_tile(GemmPlan& pl, const PlanProbs& q, int family, int bm, int bn, int kc, int nw, bool a_km,
+                      bool b_kn, bool no_ws) {
+  const TileCount tc = tile_count(q, bm, bn);
+  if (tc.maxt == 0) return;
+  const bool b16 = family == GF_TILE_B16;
+  long long maxMN = 0;
+  bool vec = true;
+  for (int i = 0; i < q.n; ++i) {
+    maxMN = std::max(maxMN, (long long)q[i].M * q[i].N);
+    vec = vec && rows_aligned(q[i], 4, !a_km, !b_kn);
+  }
+  const int splits = (!no_ws && tc.ws && (!b16 || tc.tot < 256)) ? splitk_count(q, tc.tot, kc) : 1;
+  const int npack = (!b16 && q.n > 1) ? q.n : 0;
+  GemmStep& st = plan_step(pl, family, q.mask, dr_xcd_grid(npack ? tc.tot : tc.maxt), splits, npack ? 1 : q.n, 64 * nw);
+  st.bm = bm; st.bn = bn; st.kc = kc; st.nw = nw; st.a_km = a_km; st.b_kn = b_kn; st.vec = b16 || vec; st.bf16 = b16;
+  st.splits = splits; st.npack = npack; st.no_ws = no_ws;
+  if (splits > 1) plan_step(pl, GF_SPLITK_FINISH, q.mask, (int)((maxMN + 255) / 256), 1, q.n, 256).splits = splits;
+}
+
+// wave-K chain kernel: 8-wide k runs on 16-byte boundaries in every operand
+// (ksplitA on an 8 boundary); b16: k_gemm_tile_b16's test, every problem bf16 as well
+static bool chain_ok(const PlanProbs& q, bool b16) {
+  for (int i = 0; i < q.n; ++i) {
+    const GemmArgs& g = q[i];
+    if (!rows_aligned(g, 8, true, true) || g.W2 || g.epi != EPI_NONE || g.out_conv) return false;
+    if (b16 ? !g.bf16 : (g.K < 8 || g.M < 1 || g.N < 1)) return false;
+  }
+  return true;
+}
+static bool b16_ok(const PlanProbs& q) { return chain_ok(q, true); }
+
+// every problem with pre-split weight planes and the wave-K shape (NT, no second
+// A segment or B segment, K % 8 == 0, 16-byte aligned rows, 32-bit offsets)
+static bool wks3_ok(const PlanProbs& q) {
+  for (int i = 0; i < q.n; ++i) {
+    const GemmArgs& g = q[i];
+    if (!g.wsplit || g.wsplit_np < ((g.N + 31) & ~31) || g.K < 8 || !rows_aligned(g, 8, true, false) ||
+        ((uintptr_t)g.wsplit & 15) || g.ksplitA < g.K || g.W2 || g.epi != EPI_NONE || g.out_conv || g.M < 1 || g.N < 1 ||
+        (long long)g.M * g.lda >= (1LL << 30) || (long long)((g.K + 31) / 32) * 3 * g.wsplit_np * 32 >= (1LL << 30))
+      return false;
+  }
+  return true;
+}
+// 4 waves per 32 x 32 (bf16: 16 x 32) tile, each over its own run of
+// k-chunks through a register ring (r04g: 8 waves, whole-wave prefetch and A
+// planes measured slower, profiles/r04g_ab_wks3.txt, r04t_ab_aplanes.txt)
+// (r06o / r06p: the K loop fully unrolled -- the rolled loop's back edge makes
+// the compiler wait for every outstanding load at each chunk, so the ring never
+// overlaps loads with MFMAs; unrolled, the waits are per slot -- bitwise the
+// same epoch, and no faster: B = 256 fp32 596 -> 596 k, bf16 909 -> 900 k (864 k
+// unrolled for short K too), B = 128 fp32 446 -> 454 k; not kept,
+// profiles/r06p_ab_wks3_unroll.txt.  The per-wave latency chain is not what
+// bounds these launches.)
+// (r05w: 64-row tiles, each weight plane read by half as many row tiles,
+// measured slower -- 548 k vs 566 k fp32, 776 k vs 803 k bf16 at B = 256)
+// register-ring depth (K chunks in flight per wave).  1: the fp32 kernel at 83
+// VGPRs (4 waves per SIMD) instead of 140 (3), bf16 48 instead of 86 (7 / 4):
+// fp32 headline 581 -> 592 k, bf16 818 -> 828 k; depth 3 / 4 slower still
+// than 2 (profiles/r05zf_ab_wks3_depth.txt)
+#define DR_WKS3_D 1
+// 16-row fragments per tile: 2 (32 x 32 tiles) for the fp32 products, 1 for
+// bf16 mode's (16 x 32 tiles: 828 -> 838 k bf16 headline; fp32 595 -> 587 k,
+// kept at 2; 8 or 2 waves per tile: +0.2 % / -6 %, profiles/r05zh_ab_wks3_shape.txt)
+// (64-column tiles, half the A re-reads: fp32 32 x 64 596 -> 567 k, 16 x 64
+// 567 k, bf16 16 x 64 917 -> 899 k; not kept, profiles/r06w_ab_wks3_columns.txt)
+#define DR_WKS3_NW 4  // waves per tile (each a 1/NW share of K)
+#define DR_WKS3_FM 2
+#define DR_WKS3_FM_B16 1
+// (GF_WK: the wave-K chain kernel on 32 x 32 tiles, 4 waves, ring depth 2, no split-K)
+static void plan_wave(GemmPlan& pl, const PlanProbs& q, int family, bool bf16, bool no_ws) {
+  const int fm = family == GF_WK ? 2 : bf16 ? DR_WKS3_FM_B16 : DR_WKS3_FM, nw = family == GF_WK ? 4 : DR_WKS3_NW;
+  const TileCount tc = tile_count(q, 16 * fm, 32);
+  if (tc.maxt == 0) return;
+  const int npack = q.n > 1 ? q.n : 0;
+  // bf16 A copies from the producers where every problem of the batch has one
+  // (bitwise the same epoch; bf16 headline B = 256 891 -> 909 k, profiles/r06n_ab_a16_convT_cls.txt)
+  bool a16 = family == GF_WKS3 && bf16;
+  for (int i = 0; i < q.n && a16; ++i) a16 = q[i].A16 && ((uintptr_t)q[i].A16 & 15) == 0 && q[i].lda % 8 == 0;
+  GemmStep& st = plan_step(pl, family, q.mask, dr_xcd_grid(npack ? tc.tot : tc.maxt), 1, 1, 64 * nw);
+  st.bm = 16 * fm; st.bn = 32; st.nw = nw; st.vec = 1; st.bf16 = family == GF_WKS3 && bf16; st.a16 = a16;
+  st.splits = 1; st.npack = npack; st.no_ws = no_ws;
+}
+
+static bool tile_offsets_ok(const PlanProbs& q) {
+  const long long lim = 1LL << 30;
+  for (int i = 0; i < q.n; ++i) {
+    const GemmArgs& g = q[i];
+    const long long arows = std::max((long long)g.M, (long long)g.K), brows = std::max((long long)g.N, (long long)g.K);
+    if (arows * g.lda >= lim || arows * g.lda2 >= lim || brows * g.ldb >= lim) return false;
+    if (g.epi != EPI_NONE || g.out_conv) return false;
+  }
+  return true;
+}
+
+// tall NT products (>= 1024 rows) whose caller split the weights into planes,
+// f32 mode: the split3 tall GEMM of conv_split.hip (k_gemm_split3) with the
+// data-gradient epilogue (accumulate, split output).  The world-model
+// backward's K = 200 input gradients ran on the f32 tile kernel at ~21 TF/s.
+int op_gemm_nt_split3_ex(int M, int N, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                         const void* wr, const float* bias, int act, float* Y, int ldy, int accumulate, float* Y2,
+                         int ldy2, int nsplitY, float* part, size_t part_floats, hipStream_t s, int splits_fixed);
+static bool s3_tall_ok(const GemmArgs& g) {
+  const bool seg = g.ksplitA < g.K;  // second A segment (A2 at k >= ksplitA)
+  return g.wsplit && !g.bf16 && g.M >= 1024 && g.epi == EPI_NONE && !g.out_conv && !g.W2 && !g.addend &&
+         g.alpha == 1.0f && (g.act == 0 || g.act == 1) &&
+         (!seg || (g.A2 && aligned16(g.A2) && g.ksplitA % 4 == 0 && g.lda2 % 4 == 0 &&
+                   (long long)g.M * g.lda2 < (1LL << 31))) &&
+         g.wsplit_np == (g.N + 127) / 128 * 128 &&
+         g.N % 4 == 0 && g.K % 4 == 0 && g.lda % 4 == 0 && g.ldy % 4 == 0 && aligned16(g.A) && aligned16(g.Y) &&
+         (!g.bias || aligned16(g.bias)) && (g.nsplitY >= g.N || (g.Y2 && aligned16(g.Y2) && g.ldy2 % 4 == 0 &&
+                                                                  g.nsplitY % 4 == 0)) &&
+         (long long)g.M * g.lda < (1LL << 31) && g.lda < INT_MAX && g.ldy < INT_MAX && g.ldy2 < INT_MAX;
+}
+
+// The route of validated problems sharing (amode, layout), in this order.
+// bf16 mode's chain products without weight planes on k_gemm_tile_b16 (the
+// f32 wave-K kernel measured 723.3 k against 730.5 k bf16 headline,
+// profiles/r03zf_ab_bf16_chain_route.txt)
+static void plan_route(GemmPlan& pl, int amode, bool a_km, bool b_kn, PlanProbs q) {
+  const bool nt = !a_km && !b_kn;
+  if (amode == AM_PLAIN && nt) {
+    // problems of the batch that qualify run one after another on the split3
+    // tall GEMM, the rest as a (smaller) batch below
+    // (the 200-wide, K <= 1024 problems on the wave-K split3 kernel's 32 x 32
+    // tiles instead -- it fills the chip where 64 x 64 tiles leave ~450 waves
+    // -- measured the same WM step, r06t: not kept)
+    PlanProbs rest;
+    for (int i = 0; i < q.n; ++i) {  // (q is the whole batch here: bit i = problem i)
+      if (s3_tall_ok(q[i])) plan_step(pl, GF_S3_TALL, 1 << i, 0, 0, 0, 0);
+      else rest.add(q.p[i], i);
+    }
+    if (rest.n == 0) return;
+    q = rest;
+  }
+  if (amode == AM_PLAIN && tile_offsets_ok(q)) {
+    const TileCount t64 = tile_count(q, 64, 64);
+    const int maxM = t64.maxM, minK = t64.minK;
+    // per-step products at 128-512 rows with a deep K (BPTT input gradients,
+    // K = 1800; the heads' first layers, K = 1624) or a wide N (the GRU's
+    // hidden product): 32 x 32 tiles, K chunks of 64, split-K only while the
+    // tile grid is under one workgroup per CU.  Against the 16/64-row skinny
+    // tiles, which re-read the weights per row tile and the activations per
+    // 16 columns: 44 -> 32 us (BPTT, 2 problems), 23 -> 15 us (heads, 3
+    // problems, split-K 4), profiles/r02h_kbench_tile_B256.txt
+    // shallow-K products the caller gave weight planes (the BPTT's actor
+    // input gradient, K = 200, N = 1624): the wave-K split3 kernel
+    const bool step_rows = nt && maxM >= 128 && maxM <= 512;
+    if (step_rows && minK < 512 && wks3_ok(q)) return plan_wave(pl, q, GF_WKS3, b16_ok(q), false);
+    if (step_rows) {
+      const int tiles32 = tile_count(q, 32, 32).tot;
+      // (f32 under ~112 tiles -- one per-step Linear of 200 outputs, K = 1624 --
+      // the 16-row skinny tiles spread wider: 8.4 against 13.0 us)
+      if ((minK >= 1024 && (tiles32 >= 112 || b16_ok(q))) || (minK >= 512 && tiles32 >= 256)) {
+        const bool no_ws = tiles32 >= 256;
+        // f32: the wave-K kernel (32 x 32 tiles, 4 waves, no split-K: heads
+        // 15.8 -> 13.0 us, BPTT 32.2 -> 25.7, GRU hidden product 13.3 -> 12.3,
+        // profiles/r03g_kbench_wk.txt); the LDS tile kernel stays for the
+        // shapes the wave-K kernel does not take
+        if (wks3_ok(q)) plan_wave(pl, q, GF_WKS3, b16_ok(q), no_ws);
+        else if (b16_ok(q)) plan_tile(pl, q, GF_TILE_B16, 32, 32, 64, 4, false, false, no_ws);
+        else if (chain_ok(q, false)) plan_wave(pl, q, GF_WK, false, no_ws);
+        else plan_tile(pl, q, GF_TILE, 32, 32, 64, 4, false, false, no_ws);
+        return;
+      }
+    }
+    // weight gradients (TN) and tall, deep products go to the tile kernel --
+    // when it can fill the chip: a per-step product at B = 256 (16 tiles of
+    // 64 x 64, no split-K scratch) runs on 52+ skinny 64-row workgroups instead
+    // tall products with a small K (M >= 1024: the world-model heads' and
+    // decoder's layers over B (T - 1) rows, the critic's over B (H + 1)): the
+    // 64-row skinny tiles re-read the weights per row tile and run 16 columns
+    // per workgroup (480 us for the decoder's 3584 x 4096 x 200 product)
+    const bool tall = nt && maxM >= 1024 && t64.tot >= 256;
+    if (a_km || (maxM >= 256 && minK >= 512 && (t64.ws || t64.tot >= 128)) || tall) {
+      // tall NT products with a deep K (the encoder feature projection, the
+      // critic's first layer over B*(H+1) rows): 8 waves as 4 x 2 over 64 x 64
+      // with K chunks of 64 -- 198 -> 171 us (M 8192, K 4096), 51 -> 47 us
+      // (M 4096, K 1624), profiles/r02m_kbench_tall_tiles.txt
+      if (nt && minK >= 1024 && b16_ok(q)) plan_tile(pl, q, GF_TILE_B16, 64, 64, 64, 8, false, false, false);
+      else if (nt && minK >= 1024) plan_tile(pl, q, GF_TILE, 64, 64, 64, 8, false, false, false);
+      else plan_tile(pl, q, GF_TILE, 64, 64, 32, 4, a_km, b_kn, false);
+      return;
+    }
+  }
+  if (amode == AM_LNBWD || amode == AM_STEBWD) {
+    if (nt && plan_skinny(pl, q, amode, false)) return;
+    plan_fail(pl, amode == AM_LNBWD ? "gemm: LayerNorm-backward prologue needs the staged NT skinny path"
+                                    : "gemm: softmax-STE-backward prologue needs the staged NT skinny path");
+    return;
+  }
+  if (!a_km && (amode == AM_PLAIN || amode == AM_LNSILU) && plan_skinny(pl, q, amode, b_kn)) return;
+  long long work = 0;
+  for (int i = 0; i < q.n; ++i) work += (long long)q[i].M * q[i].N;
+  // large problems: 64x64 tiles; small (per-step, M = batch rows): 32x32 tiles
+  // so that the launch spreads over more CUs.
+  const int bt = work >= 256LL * 1024 ? 64 : 32;
+  const TileCount tc = tile_count(q, bt, bt);
+  if (tc.maxt == 0) return;
+  GemmStep& st = plan_step(pl, GF_LEGACY, q.mask, tc.maxt, 1, q.n, 256);
+  st.bm = st.bn = bt; st.amode = amode; st.a_km = a_km; st.b_kn = b_kn;
+}
+
+// the sampler-head kernel's shape: one LN-SiLU NT problem, C = 32, K <= 256
+static bool ln_sample_ok(const GemmArgs& g) {
+  return g.epi == EPI_SAMPLE && g.C == 32 && g.R * g.C == g.N && g.N % LS_NT == 0 && g.K > 0 && g.K % 4 == 0 &&
+         g.K <= LS_KMAX && g.M > 0 && g.M <= 65536 && g.ln_g && g.ln_b && g.ksplitA >= g.K && !g.addend &&
+         g.alpha == 1.0f && g.act == 0 && !g.accumulate && !g.W2 && aligned16(g.A) && aligned16(g.W) &&
+         aligned16(g.ln_g) && aligned16(g.ln_b) && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
+         (!g.a_out || (aligned16(g.a_out) && g.ld_aout % 4 == 0)) && skinny_offsets_ok(g, false) &&
+         (long long)g.M * g.ldz < (1LL << 31) && aligned16(g.z_out) && g.ldz % 4 == 0 &&
+         (!g.soft_out || (aligned16(g.soft_out) && g.ld_soft % 4 == 0)) && (!g.noise.q || aligned16(g.noise.q));
+}
+
 // tall LN-SiLU products (M >= 1024 rows: the world-model heads / decoder over
 // B (T - 1) rows, the critic over B (H + 1)) whose transformed rows are saved
 // anyway (a_out): normalise once, then the plain GEMM on the saved rows
@@ -2938,101 +2769,242 @@ static bool tall_ln_ok(const GemmArgs* probs, int count) {
   }
   return true;
 }
+// a problem as the steps after its k_ln_silu_rows pre-pass see it
+static void after_ln_rows(GemmArgs& g) {
+  g.A = g.a_out; g.lda = g.ld_aout;
+  g.ln_g = g.ln_b = nullptr; g.a_out = nullptr;
+}
 
-int gemm_launch(GemmLayout lay, int amode, const GemmArgs* probs, int count, hipStream_t s) {
-  if (count < 1 || count > 4) {
-    dr_set_error("gemm_launch: bad problem count %d", count);
-    return DR_E_INVALID;
-  }
+static void plan_build(GemmPlan& pl, GemmLayout lay, int amode, const GemmArgs* probs, int count) {
+  if (count < 1 || count > 4) return plan_fail(pl, "gemm_launch: bad problem count %d", count);
+  GemmArgs pp[4];
   if (lay == G_NT && amode == AM_LNSILU && tall_ln_ok(probs, count)) {
-    GemmArgs pp[4];
     for (int i = 0; i < count; ++i) {
-      const GemmArgs& g = probs[i];
-      const dim3 grid((unsigned)((g.M + 3) / 4));
-      if (g.K <= 256)
-        hipLaunchKernelGGL(k_ln_silu_rows<1>, grid, dim3(256), 0, s, g.M, g.K, g.A, (int)g.lda, g.ln_g, g.ln_b, g.a_out,
-                           (int)g.ld_aout);
-      else
-        hipLaunchKernelGGL(k_ln_silu_rows<4>, grid, dim3(256), 0, s, g.M, g.K, g.A, (int)g.lda, g.ln_g, g.ln_b, g.a_out,
-                           (int)g.ld_aout);
-      DR_TRY(dr_check_launch("ln_silu_rows"));
-      pp[i] = g;
-      pp[i].A = g.a_out;
-      pp[i].lda = g.ld_aout;
-      pp[i].ln_g = pp[i].ln_b = nullptr;
-      pp[i].a_out = nullptr;
+      plan_step(pl, GF_LN_ROWS, 1 << i, (probs[i].M + 3) / 4, 1, 1, 256).kc = probs[i].K <= 256 ? 1 : 4;
+      after_ln_rows(pp[i] = probs[i]);
     }
-    return gemm_launch(G_NT, AM_PLAIN, pp, count, s);
+    pl.ln_pre = 1; probs = pp; amode = AM_PLAIN;
   }
-  if (lay == G_NT && amode == AM_LNSILU && count == 1 && ln_sample_ok(probs[0]))
-    return launch_ln_sample(probs[0], s);
+  if (lay == G_NT && amode == AM_LNSILU && count == 1 && ln_sample_ok(probs[0])) {
+    const GemmArgs& g = probs[0];
+    GemmStep& st = plan_step(pl, GF_LN_SAMPLE, 1, dr_xcd_grid(dr_cdiv(g.M, LS_MT) * (g.N / LS_NT)), 1, 1, 256);
+    st.bm = LS_MT; st.bn = LS_NT; st.kc = (g.K + 15) >> 4; st.amode = AM_LNSILU; st.vec = 1; st.epi = EPI_SAMPLE;
+    st.lds = (int)ln_sample_lds_bytes(g.K);
+    return;
+  }
+  PlanProbs q;
   for (int i = 0; i < count; ++i) {
     const GemmArgs& g = probs[i];
-    if (g.epi == EPI_SAMPLE && (g.C < 1 || g.C > 32 || 32 % g.C != 0 || g.N != g.R * g.C)) {
-      dr_set_error("gemm_launch: sampler epilogue needs C | 32 and N == R*C (C=%d R=%d N=%d)", g.C, g.R, g.N);
-      return DR_E_INVALID;
-    }
-    if (g.epi == EPI_ACTOR && (g.N != 2 * g.na || g.na > 8)) {
-      dr_set_error("gemm_launch: actor epilogue needs N == 2A <= 16");
-      return DR_E_INVALID;
-    }
+    if (g.epi == EPI_SAMPLE && (g.C < 1 || g.C > 32 || 32 % g.C != 0 || g.N != g.R * g.C))
+      return plan_fail(pl, "gemm_launch: sampler epilogue needs C | 32 and N == R*C (C=%d R=%d N=%d)", g.C, g.R, g.N);
+    if (g.epi == EPI_ACTOR && (g.N != 2 * g.na || g.na > 8))
+      return plan_fail(pl, "gemm_launch: actor epilogue needs N == 2A <= 16");
     if (g.epi != EPI_NONE && (lay != G_NT || (amode != AM_PLAIN && amode != AM_LNSILU) || g.M > 4096 ||
-                              !skinny_offsets_ok(g, false))) {
-      dr_set_error("gemm_launch: fused epilogues need the NT skinny path");
-      return DR_E_INVALID;
-    }
+                              !skinny_offsets_ok(g, false)))
+      return plan_fail(pl, "gemm_launch: fused epilogues need the NT skinny path");
+    q.add(&g, i);
   }
-  GemmBatch gb;
-  for (int i = 0; i < count; ++i) {
-    gb.p[i] = probs[i];
-    if (probs[i].M < 0 || probs[i].N < 0 || probs[i].K < 0) {
-      dr_set_error("gemm_launch: negative dims");
-      return DR_E_INVALID;
-    }
-  }
-  switch (lay) {
-    case G_NT:
-      switch (amode) {
-        case AM_PLAIN: DR_TRY((launch_pick<AM_PLAIN, false, false>(gb, count, s))); break;
-        case AM_LNSILU: DR_TRY((launch_pick<AM_LNSILU, false, false>(gb, count, s))); break;
-        case AM_CONV: DR_TRY((launch_pick<AM_CONV, false, false>(gb, count, s))); break;
-        case AM_CONV_SRC: DR_TRY((launch_pick<AM_CONV_SRC, false, false>(gb, count, s))); break;
-        case AM_LNBWD: {
-          const bool r16 = gemm_bwd_rows16(probs, count);
-          for (int i = 0; i < count; ++i) {
-            const GemmArgs& g = probs[i];
-            const int lim = r16 ? 1024 : 256;  // staged rows per lane: SV = 4 (MT 16) / 1 (MT 64)
-            if (g.K % 4 || g.K > lim || g.lda % 4 || g.ld_pre % 4 || g.ldb % 4 ||
-                ((uintptr_t)g.A | (uintptr_t)g.pre | (uintptr_t)g.W | (uintptr_t)g.ln_g | (uintptr_t)g.ln_b) & 15) {
-              dr_set_error("gemm_launch: AM_LNBWD needs K %% 4 == 0, K <= %d, 16-byte aligned rows (K=%d)", lim, g.K);
-              return DR_E_INVALID;
-            }
-          }
-          DR_TRY((launch_pick<AM_LNBWD, false, false>(gb, count, s)));
-          break;
-        }
-        case AM_STEBWD: {
-          const bool r16 = gemm_bwd_rows16(probs, count);
-          for (int i = 0; i < count; ++i) {
-            const GemmArgs& g = probs[i];
-            const int lim = r16 ? 1024 : 256;
-            const int gl = g.C / 4;
-            if (g.K % 4 || g.K > lim || g.lda % 4 || g.ld_pre % 4 || g.ldb % 4 || g.C < 4 || g.C % 4 ||
-                (gl & (gl - 1)) || gl > 64 || g.K % g.C || !r16 ||
-                ((uintptr_t)g.A | (uintptr_t)g.pre | (uintptr_t)g.W) & 15) {
-              dr_set_error("gemm_launch: AM_STEBWD needs 16-row tiles (gemm_bwd_rows16), K %% C == 0, C/4 a power "
+  for (int i = 0; i < count; ++i)
+    if (probs[i].M < 0 || probs[i].N < 0 || probs[i].K < 0) return plan_fail(pl, "gemm_launch: negative dims");
+  if (lay != G_NT) return plan_route(pl, AM_PLAIN, lay == G_TN, true, q);
+  if (amode < AM_PLAIN || amode > AM_STEBWD) return plan_fail(pl, "gemm_launch: bad amode");
+  // The staged backward prologues (AM_LNBWD, AM_STEBWD) run on 16-row tiles
+  // (K <= 1024) when the problem has at most 64 rows or its 16 x 16 grid stays
+  // within ~2.5 dispatch rounds (skinny_tile_rows), else on 64-row tiles (K <= 256).
+  // (The 16 x 48 LayerNorm-backward tile plan_skinny picks for a grid between one
+  // and two rounds stages K <= 256 as well; wider K keeps 32 columns.)
+  const int maxM = tile_count(q, 16, 16).maxM;
+  const bool r16 = maxM <= 4096 && skinny_tile_rows(q, amode, maxM, false) == 16;
+  const int lim = r16 ? 1024 : 256;  // staged rows per lane: SV = 4 (MT 16) / 1 (MT 64)
+  for (int i = 0; i < count && (amode == AM_LNBWD || amode == AM_STEBWD); ++i) {
+    const GemmArgs& g = probs[i];
+    const bool rows = g.K % 4 == 0 && g.K <= lim && g.lda % 4 == 0 && g.ld_pre % 4 == 0 && g.ldb % 4 == 0 &&
+                      (((uintptr_t)g.A | (uintptr_t)g.pre | (uintptr_t)g.W) & 15) == 0;
+    const int gl = g.C / 4;
+    if (amode == AM_LNBWD && (!rows || (((uintptr_t)g.ln_g | (uintptr_t)g.ln_b) & 15)))
+      return plan_fail(pl, "gemm_launch: AM_LNBWD needs K %% 4 == 0, K <= %d, 16-byte aligned rows (K=%d)", lim, g.K);
+    if (amode == AM_STEBWD && (!rows || g.C < 4 || g.C % 4 || (gl & (gl - 1)) || gl > 64 || g.K % g.C || !r16))
+      return plan_fail(pl, "gemm_launch: AM_STEBWD needs 16-row tiles (gemm_bwd_rows16), K %% C == 0, C/4 a power "
                            "of two, K <= %d, 16-byte aligned rows (K=%d C=%d)", lim, g.K, g.C);
-              return DR_E_INVALID;
-            }
-          }
-          DR_TRY((launch_pick<AM_STEBWD, false, false>(gb, count, s)));
-          break;
-        }
-        default: dr_set_error("gemm_launch: bad amode"); return DR_E_INVALID;
+  }
+  plan_route(pl, amode, false, false, q);
+}
+GemmPlan gemm_plan(GemmLayout lay, int amode, const GemmArgs* probs, int count) {
+  GemmPlan pl;
+  pl.rc = DR_OK; pl.err[0] = 0; pl.ln_pre = 0; pl.nsteps = 0;
+  plan_build(pl, lay, amode, probs, count);
+  return pl;
+}
+
+int gemm_bwd_fusable(const GemmPlan& pl) {
+  if (pl.rc != DR_OK || pl.nsteps > 1) return 0;
+  return pl.nsteps == 0 ? 16 : pl.step[0].family == GF_SKINNY ? pl.step[0].bm : 0;  // (no tile at all: no launch)
+}
+
+// ---- executor: the plan's steps, exactly the kernel instantiations named there
+// opt in to more than the default 64 KB of dynamic LDS (once per kernel instantiation)
+template <auto KERNEL>
+static void lds_opt_in(int bytes) {
+  static const bool raised = [bytes] {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return true;
+  }();
+  (void)raised;
+}
+template <int MT, int NT, int AMODE, bool B_KN, int EPI>
+static void launch_skinny(const GemmStep& st, const GemmBatch& gb, hipStream_t s) {
+  constexpr auto kv = k_gemm_skinny<MT, NT, AMODE, B_KN, true, EPI>;
+  constexpr auto ks = k_gemm_skinny<MT, NT, AMODE, B_KN, false, EPI>;
+  if (st.lds > 64 * 1024) lds_opt_in<kv>(150 * 1024), lds_opt_in<ks>(150 * 1024);
+  hipLaunchKernelGGL((st.vec ? kv : ks), dim3(st.gx, st.gy, st.gz), dim3(st.block), st.lds, s, gb, st.npack);
+}
+template <int AMODE, bool B_KN>
+static void exec_skinny(const GemmStep& st, const GemmBatch& gb, hipStream_t s) {
+#define DR_SK(mt, nt, e) launch_skinny<mt, nt, AMODE, B_KN, e>(st, gb, s)
+  const bool r64 = st.bm == 64;
+  if (st.epi == EPI_SAMPLE) return r64 ? DR_SK(64, 32, EPI_SAMPLE) : DR_SK(16, 32, EPI_SAMPLE);
+  if (st.epi == EPI_ACTOR) return r64 ? DR_SK(64, 16, EPI_ACTOR) : DR_SK(16, 16, EPI_ACTOR);
+  if (r64) return DR_SK(64, 16, EPI_NONE);
+  if constexpr (AMODE == AM_LNBWD)
+    if (st.bn == 48) return DR_SK(16, 48, EPI_NONE);
+  return st.bn == 32 ? DR_SK(16, 32, EPI_NONE) : DR_SK(16, 16, EPI_NONE);
+#undef DR_SK
+}
+
+// k_gemm_skinny (the A-modes and layouts plan_route sends there) or the legacy k_gemm of one (amode, layout)
+template <int AMODE, bool A_KM, bool B_KN>
+static void exec_mode(const GemmStep& st, const GemmBatch& gb, hipStream_t s) {
+  if constexpr (!A_KM && AMODE != AM_CONV && AMODE != AM_CONV_SRC)
+    if (st.family == GF_SKINNY) return exec_skinny<AMODE, B_KN>(st, gb, s);
+  hipLaunchKernelGGL((st.bm == 64 ? k_gemm<64, 64, AMODE, A_KM, B_KN> : k_gemm<32, 32, AMODE, A_KM, B_KN>),
+                     dim3(st.gx, st.gy, st.gz), dim3(st.block), 0, s, gb);
+}
+template <int BM, int BN, int KC, bool A_KM, bool B_KN, int NW = 4>
+static void launch_tile2(const GemmStep& st, const GemmBatch& gb, hipStream_t s) {
+  constexpr auto kv = k_gemm_tile<BM, BN, KC, A_KM, B_KN, true, NW>;
+  constexpr auto ks = k_gemm_tile<BM, BN, KC, A_KM, B_KN, false, NW>;
+  hipLaunchKernelGGL((st.vec ? kv : ks), dim3(st.gx, st.gy, st.gz), dim3(st.block), 0, s, gb, st.splits, st.npack);
+}
+template <int NK>
+static void launch_ln_sample_nk(const GemmStep& st, const GemmArgs& g, hipStream_t s) {
+  if (st.lds > 64 * 1024) lds_opt_in<k_ln_gemm_sample<NK>>((int)ln_sample_lds_bytes(16 * NK));
+  hipLaunchKernelGGL(k_ln_gemm_sample<NK>, dim3(st.gx), dim3(st.block), st.lds, s, g);
+}
+
+static int exec_step(const GemmStep& st, const GemmBatch& gb, hipStream_t s) {
+  const dim3 grid(st.gx, st.gy, st.gz), blk(st.block);
+  const GemmArgs& g = gb.p[0];
+  switch (st.family) {
+    case GF_LN_ROWS:
+      hipLaunchKernelGGL((st.kc == 1 ? k_ln_silu_rows<1> : k_ln_silu_rows<4>), grid, blk, 0, s, g.M, g.K, g.A,
+                         (int)g.lda, g.ln_g, g.ln_b, g.a_out, (int)g.ld_aout);
+      return dr_check_launch("ln_silu_rows");
+    case GF_LN_SAMPLE: {  // ln_sample_ok: 0 < K <= LS_KMAX, so kc = 1 .. 16
+#define DR_LS(n) launch_ln_sample_nk<n>, launch_ln_sample_nk<n + 1>, launch_ln_sample_nk<n + 2>, launch_ln_sample_nk<n + 3>
+      static void (*const nk[16])(const GemmStep&, const GemmArgs&, hipStream_t) = {DR_LS(1), DR_LS(5), DR_LS(9),
+                                                                                    DR_LS(13)};
+#undef DR_LS
+      nk[st.kc - 1](st, g, s);
+      return dr_check_launch("ln_gemm_sample");
+    }
+    case GF_S3_TALL:
+      return op_gemm_nt_split3_ex(g.M, g.N, g.K, g.A, (int)g.lda, g.A2, (int)g.lda2, g.ksplitA < g.K ? g.ksplitA : g.K,
+                                  g.wsplit, g.bias, g.act, g.Y, (int)g.ldy, g.accumulate, g.Y2, (int)g.ldy2,
+                                  g.nsplitY < g.N ? g.nsplitY : INT_MAX, g.splitk_ws,
+                                  g.splitk_ws ? (size_t)g.splitk_floats : 0, s, 0);
+    case GF_TILE:
+      if (st.bm == 32) launch_tile2<32, 32, 64, false, false, 4>(st, gb, s);
+      else if (st.nw == 8) launch_tile2<64, 64, 64, false, false, 8>(st, gb, s);
+      else if (st.a_km) launch_tile2<64, 64, 32, true, true>(st, gb, s);
+      else if (st.b_kn) launch_tile2<64, 64, 32, false, true>(st, gb, s);
+      else launch_tile2<64, 64, 32, false, false>(st, gb, s);
+      break;
+    case GF_TILE_B16:
+      hipLaunchKernelGGL((st.bm == 32 ? k_gemm_tile_b16<32, 32, 4> : k_gemm_tile_b16<64, 64, 8>), grid, blk, 0, s, gb,
+                         st.splits);
+      break;
+    case GF_SPLITK_FINISH: hipLaunchKernelGGL(k_splitk_finish, grid, blk, 0, s, gb, st.splits); break;
+    case GF_WK: hipLaunchKernelGGL((k_gemm_wk<32, 32, 4, 2, 1>), grid, blk, 0, s, gb, 1, st.npack); break;
+    case GF_WKS3:
+      hipLaunchKernelGGL((st.a16    ? k_gemm_wks3<1, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM_B16, true>
+                          : st.bf16 ? k_gemm_wks3<1, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM_B16>
+                                    : k_gemm_wks3<3, DR_WKS3_D, DR_WKS3_NW, DR_WKS3_FM>),
+                         grid, blk, 0, s, gb, st.npack);
+      break;
+    case GF_SKINNY:
+    case GF_LEGACY:
+      switch (st.amode) {
+        case AM_LNSILU: exec_mode<AM_LNSILU, false, false>(st, gb, s); break;
+        case AM_CONV: exec_mode<AM_CONV, false, false>(st, gb, s); break;
+        case AM_CONV_SRC: exec_mode<AM_CONV_SRC, false, false>(st, gb, s); break;
+        case AM_LNBWD: exec_mode<AM_LNBWD, false, false>(st, gb, s); break;
+        case AM_STEBWD: exec_mode<AM_STEBWD, false, false>(st, gb, s); break;
+        default:
+          if (st.a_km) exec_mode<AM_PLAIN, true, true>(st, gb, s);
+          else if (st.b_kn) exec_mode<AM_PLAIN, false, true>(st, gb, s);
+          else exec_mode<AM_PLAIN, false, false>(st, gb, s);
       }
       break;
-    case G_NN: DR_TRY((launch_pick<AM_PLAIN, false, true>(gb, count, s))); break;
-    case G_TN: DR_TRY((launch_pick<AM_PLAIN, true, true>(gb, count, s))); break;
+  }
+  return DR_OK;
+}
+
+int gemm_launch(GemmLayout lay, int amode, const GemmArgs* probs, int count, hipStream_t s) {
+  return gemm_run(gemm_plan(lay, amode, probs, count), probs, count, s);
+}
+int gemm_run(const GemmPlan& pl, const GemmArgs* probs, int count, hipStream_t s) {
+  if (pl.rc != DR_OK) return dr_set_error("%s", pl.err), pl.rc;
+  for (int k = 0; k < pl.nsteps; ++k) {
+    const GemmStep& st = pl.step[k];
+    GemmBatch gb;
+    for (int i = 0, n = 0; i < count; ++i) {
+      if (!(st.mask >> i & 1)) continue;
+      GemmArgs& g = gb.p[n++] = probs[i];  // the one copy of the problem: the kernel's argument
+      if (pl.ln_pre && st.family != GF_LN_ROWS) after_ln_rows(g);
+      if (st.no_ws) g.splitk_ws = nullptr;
+    }
+    DR_TRY(exec_step(st, gb, s));
+    if (st.family == GF_LN_SAMPLE) return DR_OK;
   }
   return dr_check_launch("gemm");
+}
+
+// internal (not in dreamer_hip.h), for the host tests: the plan of a batch given as 17 ints per problem (below; flags
+// and the misalignment nibbles mis0 / mis1 of the dummy pointers as tests/test_gemm_plan_host.py names them; strides
+// the list leaves out follow lda, ldb or ldy).  Writes the steps (GemmStep as ints) to out; returns their count, or
+// -rc and the message in msg.
+extern "C" int dr_internal_gemm_plan(int lay, int amode, int count, const int* in, int* out, int out_steps, char* msg,
+                                     int msg_cap) {
+  GemmArgs pr[4];
+  for (int i = 0; i < count && i < 4; ++i) {
+    const int *v = in + 17 * i, fl = v[11];
+    auto ptr = [&](int slot, int nib, bool on) {  // nib: 0-7 of mis0, 8-11 of mis1, -1 aligned
+      const int mis = nib < 0 ? 0 : (v[14 + nib / 8] >> (4 * (nib % 8))) & 15;
+      return on ? (float*)(((uintptr_t)(16 * i + slot + 1) << 32) + mis) : nullptr;
+    };
+    GemmArgs g = gemm_args();
+    g.M = v[0]; g.N = v[1]; g.K = v[2]; g.C = v[8]; g.R = v[9]; g.na = v[10];
+    g.bf16 = (fl >> 7) & 1; g.epi = (fl >> 8) & 3; g.out_conv = (fl >> 11) & 1; g.accumulate = (fl >> 13) & 1;
+    g.A = ptr(0, 0, true); g.lda = v[3];
+    g.A2 = ptr(1, 1, fl & 1); g.lda2 = v[4]; g.ksplitA = v[5];
+    g.W = ptr(2, 2, true); g.ldb = v[6];
+    g.Y = ptr(3, 3, true); g.ldy = v[7];
+    g.ln_g = ptr(4, 4, fl & 2); g.ln_b = ptr(5, 5, fl & 2);
+    g.a_out = ptr(6, 6, fl & 4); g.ld_aout = v[16];
+    g.pre = ptr(7, 7, fl & 8); g.ld_pre = v[3];
+    g.splitk_ws = ptr(8, -1, fl & 16); g.splitk_floats = v[12];
+    g.wsplit = (const unsigned short*)ptr(9, 8, fl & 32); g.wsplit_np = v[13];
+    g.A16 = (const unsigned short*)ptr(10, 9, fl & 64);
+    g.W2 = ptr(11, -1, fl & 1024); g.ldb2 = v[6];
+    g.addend = ptr(12, -1, fl & 4096); g.ld_add = v[7];
+    g.bias = ptr(13, 10, fl & 16384);
+    g.z_out = ptr(14, 11, g.epi == EPI_SAMPLE); g.ldz = v[7];
+    pr[i] = g;
+  }
+  const GemmPlan pl = gemm_plan((GemmLayout)lay, amode, pr, count);
+  if (pl.rc != DR_OK) snprintf(msg, msg_cap, "%s", pl.err);
+  static_assert(sizeof(GemmStep) == 21 * sizeof(int), "GemmStep is copied out as 21 ints");
+  for (int k = 0; pl.rc == DR_OK && k < pl.nsteps && k < out_steps; ++k)
+    memcpy(out + 21 * k, &pl.step[k], sizeof(GemmStep));
+  return pl.rc != DR_OK ? -pl.rc : pl.nsteps;
 }
