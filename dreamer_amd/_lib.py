@@ -74,6 +74,14 @@ class dr_frames(C.Structure):
                 ("stride_b", C.c_longlong), ("stride_t", C.c_longlong), ("raw255", C.c_int), ("t0", C.c_int)]
 
 
+class dr_dream_outputs(C.Structure):
+    """dr_dream_stats' outputs (include/dreamer_hip.h); a field left None is NULL: not computed."""
+    _fields_ = [(n, fp) for n in (
+        "R_lambda", "R_mc", "adv", "adv_norm", "weight", "logp", "base_entropy", "saturated",
+        "reward_mean", "reward_std", "ret_mean", "ret_std", "logp_mean", "logp_std", "alive", "action_spread",
+        "best", "worst", "n_finite")]
+
+
 _P = C.POINTER
 _sz = C.c_size_t
 _i = C.c_int
@@ -96,6 +104,8 @@ _SIGS = {
     "dr_replay_returns": (_i, [_i, _i, fp, _ll, fp, _ll, _i, fp, _f, _f, fp, fp, fp, fp]),
     "dr_value_stats": (_i, [_i, _i, _i, _i, fp, _ll, fp, fp, fp, fp, fp, fp]),
     "dr_action_logprob": (_i, [_i, _i, _i, fp, fp, fp, _ll, _ll, fp, fp, fp, fp]),
+    "dr_dream_stats": (_i, [_i, _i, _i, _i, fp, fp, fp, fp, fp, fp, fp, _f, _f, fp, _f, _P(dr_dream_outputs), fp]),
+    "dr_actor_draws": (_i, [_i, _i, _i, dr_noise, fp, fp]),
     "dr_plan_sample": (_i, [_i, _i, _i, _i, _i, fp, fp, fp, dr_noise, fp, fp]),
     "dr_plan_update": (_i, [_i, _i, _i, _i, _i, fp, fp, fp, _f, _f, _f, _f, _f, fp, fp, fp, fp, fp, fp, fp, fp]),
     "dr_imagine_tape_bytes":(_sz, [_P(dr_dims), _i, _i]),
@@ -200,6 +210,8 @@ DR_ACT_MAX_ENVS = 16  # include/dreamer_hip.h: rows of one dr_act_batch / dr_act
 DR_ACT_VEC_MAX_OBS = 1023  # include/dreamer_hip.h: widest observation vector dr_act_vec takes
 DR_PLAN_MAX_CANDIDATES = 2048  # include/dreamer_hip.h: candidates per environment of dr_plan_sample / dr_plan_update
 DR_ENSEMBLE_MAX_SAMPLES = 64  # include/dreamer_hip.h: futures per window of dr_ensemble_metrics
+DR_DREAM_STATS_MAX_DREAMS = 64  # include/dreamer_hip.h: dreams per window of dr_dream_stats (= DR_ENSEMBLE_MAX_SAMPLES)
+DR_DREAM_STATS_MAX_LDS_FLOATS = 15360  # include/dreamer_hip.h: (M | 1) * (3 H + 2) of one dr_dream_stats window
 DR_PLAN_MAX_ELEMS = 1024  # include/dreamer_hip.h: H * A of one planned action sequence
 DR_SALIENCY_MAX_CELLS = 1024  # include/dreamer_hip.h: cells of one frame's saliency grid
 DR_SALIENCY_MAX_RADIUS = 15  # include/dreamer_hip.h: widest blur radius of dr_occlude_frames

@@ -307,6 +307,65 @@ class Dreamer(nn.Module):
         from .agent_trace import evaluate_values
         return evaluate_values(self, batches=batches, batch_size=batch_size, length=length, sample=sample)
 
+    def dream_trace(self, starts=None, batch_size=None, context=None, horizon=None, samples=1, deterministic=False,
+                    sample=True, noise=None, decode=True, saturation=0.99, _mark=None):
+        """M = `samples` imagined rollouts under the current actor per replay
+        window (dream_trace.py; the definitions are in include/dreamer_hip.h):
+        what train_Agent learns from (Dreamer.py:143-175, Agent.py:96-135),
+        kept per dream.  open_loop's gather, encoder and context filter once
+        for the B windows, the posteriors replicated M times (rollout row
+        b*M + m), one dr_imagine_fwd of `horizon` steps at B*M rows -- Philox is
+        keyed by row, so the replicas differ --, one dr_critic_fwd each for the
+        online and the target critic over the B*M*(H+1) states, one
+        dr_dream_stats for the lambda-returns, Monte-Carlo returns, advantages
+        (raw and divided by the agent's max(S, 1), which is read and not
+        updated), discount weights, action log-probabilities and saturation
+        counts of every dream and their mean / spread over a window's dreams,
+        and -- decode=True -- one dr_decoder_fwd of all the states.  Returns a
+        DreamResult (entropy(), curves(), pick(), video()).
+
+        starts: window starts (default: buffer.sample_start_indices(batch_size
+        or self.batch_size)); context defaults to S // 2 (the warm start's),
+        1 <= context <= S; horizon defaults to self.horizon, any H >= 1 (a dream
+        needs no ring frames).  samples: an integer in 1 .. 64 with B * samples
+        <= 4096 (ValueError otherwise, raised before np.random is drawn from,
+        like every argument check).  noise: optional explicit draws (q_context
+        (Tc, B*R, C), q_dream (H, B*M*R, C), both Exp(1), and eps (H, B*M, A),
+        N(0,1)), else Philox; sample=False takes the mode of every categorical
+        (q == 1) and leaves the actor's draws to Philox; deterministic=True
+        acts with tanh(mu).  saturation: the |a| from which an action dimension
+        counts as saturated.  Vector models have no u8 frames.  Everything
+        runs on the current stream without a sync.  _mark: stage hook of
+        tools/dream_trace_timing.py."""
+        from .dream_trace import dream_trace
+        return dream_trace(self, starts=starts, batch_size=batch_size, context=context, horizon=horizon,
+                           samples=samples, deterministic=deterministic, sample=sample, noise=noise, decode=decode,
+                           saturation=saturation, _mark=_mark)
+
+    def evaluate_dreams(self, batches=1, batch_size=None, context=None, horizon=None, samples=8, real=False):
+        """Per-step dream curves averaged over `batches` sampled batches of
+        windows and their dreams: a dict of CPU float lists -- reward, cont,
+        ret_lambda, advantage, advantage_norm, neg_logp, sigma, saturated_frac,
+        action_spread, ret_std (length H), alive and value (the online
+        critic's; length H+1).  Leaves np.random's state, the Philox {seed,
+        offset} and stream counter and the agent's S as it found them, like
+        evaluate_values.
+
+        real=True also runs agent_trace on the same starts (both filters at the
+        posterior's mode, sample=False, so both see the same states; needs
+        context <= S - 1) and adds the scalar
+            gap = mean_b (mean_m R_mc[b][m][0] - real R_mc[b][context - 1]),
+        the model's optimism about the current policy.  The two sides are not
+        the same quantity: the dream's is H imagined steps under the current
+        actor bootstrapped by the target critic at state H, the replay's is
+        the S - context recorded steps (the actions of whatever policy filled
+        the ring) bootstrapped by the target critic at the window's last
+        state.  Two estimates over different horizons, both resting on the
+        same target critic; read it as a trend, not as a model error."""
+        from .dream_trace import evaluate_dreams
+        return evaluate_dreams(self, batches=batches, batch_size=batch_size, context=context, horizon=horizon,
+                               samples=samples, real=real)
+
     def saliency_frames(self, frames, hiddens, stride=4, fill="blur", blur_sigma=3.0, mask_sigma=None, sample=False,
                         noise=None, _mark=None):
         """Perturbation saliency of N frames (saliency.py; Greydanus et al. 2018):

@@ -677,6 +677,65 @@ int dr_action_logprob(int B, int T, int A, const float* mu, const float* sigma, 
                       long long act_sb, long long act_st, float* logp, float* logp_dims, float* base_entropy,
                       hipStream_t stream);
 
+/* ---- dream trace: imagined rollouts under the actor from replay windows
+ *      (Dreamer.dream_trace, dreamer_amd/dream_trace.py): what train_Agent learns
+ *      from (Dreamer.py:143-175, Agent.py:96-135), per dream and per window.
+ * N = B*M rows; row n = b*M + m is dream m of window b.  Inputs: rewards,
+ * continues [N][H] as dr_imagine_fwd writes them (natural-space reward,
+ * continue probability); V_target, V_online [N][H+1], dr_critic_fwd's values of
+ * the H+1 states; mus, sigmas, actions [N][H][A]; norm: a device scalar holding
+ * max(S, 1) (Agent.py:78-88), read and never written, NULL = 1.
+ * Per dream (every output may be NULL; at least one output in all is required):
+ *   R_lambda[n][t]  = r_t + gamma c_t ((1 - lam) Vt_{t+1} + lam R_lambda[n][t+1]),
+ *                     R_lambda[n][H-1] = r_{H-1} + gamma c_{H-1} Vt_H (Agent.py:156-172):
+ *                     bit for bit dr_lambda_returns(N, H, ...) -- its expressions
+ *                     in its order, 1 - lam formed in double and rounded once
+ *   R_mc[n][t]      = the same at lam = 1; for finite V bit for bit
+ *                     dr_lambda_returns(..., lam = 1) (dr_replay_returns' convention)
+ *   adv[n][t]       = R_lambda[n][t] - V_online[n][t];  adv_norm = adv / norm
+ *                     (Agent.py:105-121)
+ *   weight[n][t]    [N][H+1]: w_0 = 1, w_{t+1} = w_t * (gamma * c_t) in f32, t
+ *                     ascending; entry H weighs the bootstrap value
+ *   logp[n][t], base_entropy[n][t]: bit for bit dr_action_logprob's on the same
+ *                     mus, sigmas and actions
+ *   saturated[n][t] int32: the number of dimensions i with |a_i| >= sat
+ * Per window over its M dreams, f32, m ascending from 0.0f; a mean is sum / M,
+ * a std sqrt((sum_m (x_m - mean)^2) / M) in a second pass (population):
+ *   reward_mean, reward_std [B][H]   of rewards
+ *   ret_mean, ret_std       [B][H]   of R_lambda
+ *   logp_mean, logp_std     [B][H]   of logp
+ *   alive                   [B][H+1] the mean of weight
+ *   action_spread           [B][H]   sqrt((sum_i var_m(a_i)) / A), i ascending
+ *   best, worst, n_finite   [B] int32: the dream with the largest / smallest
+ *                     R_mc[.][0] among those where it is finite, ties to the lower
+ *                     m; n_finite counts those dreams, 0 of them: best = worst = 0
+ * Non-finite inputs propagate into the per-dream outputs and into the means and
+ * stds of their (b, t); they never make a dream best or worst.
+ * One launch, one 256-thread workgroup per window, no atomics: a window's
+ * outputs are the same bits at every B and position, with any subset of the
+ * outputs asked for, and from run to run.  The window's R_lambda, logp and
+ * weight rows sit in LDS: M <= DR_DREAM_STATS_MAX_DREAMS (dr_ensemble_metrics' 64) and
+ *   (M | 1) * (3 H + 2) <= DR_DREAM_STATS_MAX_LDS_FLOATS   (M = 64: H <= 78)
+ * else DR_E_UNSUPPORTED.  M, H, A >= 1, B >= 0 (B = 0 is a no-op); bad dimensions,
+ * a missing input or no output: DR_E_INVALID before any launch. */
+#define DR_DREAM_STATS_MAX_DREAMS 64
+#define DR_DREAM_STATS_MAX_LDS_FLOATS 15360
+typedef struct {
+  float *R_lambda, *R_mc, *adv, *adv_norm, *weight, *logp, *base_entropy;
+  int* saturated;
+  float *reward_mean, *reward_std, *ret_mean, *ret_std, *logp_mean, *logp_std, *alive, *action_spread;
+  int *best, *worst, *n_finite;
+} dr_dream_outputs;
+int dr_dream_stats(int B, int M, int H, int A, const float* rewards, const float* continues,
+                   const float* V_target, const float* V_online, const float* mus, const float* sigmas,
+                   const float* actions, float gamma, float lam, const float* norm, float sat,
+                   const dr_dream_outputs* out, hipStream_t stream);
+/* eps[s][row][i], s < steps, row < rows, i < A: the N(0,1) Philox variate of
+ * (noise.stream + s, noise.row0 + row, i) -- what dr_imagine_fwd's actor draws at
+ * step s -- written out, so that a call can pair them with explicit categorical
+ * draws (dream_trace's sample=False). */
+int dr_actor_draws(int steps, int rows, int A, dr_noise noise, float* eps, hipStream_t stream);
+
 /* ---- perturbation saliency (Dreamer.saliency, dreamer_amd/saliency.py;
  *      Greydanus et al. 2018, "Visualizing and Understanding Atari Agents"):
  *      blend a blurred copy of the frame into one small region, run the agent
