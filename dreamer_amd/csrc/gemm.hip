@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "gemm.h"
+#include "conv.h"  // dr_internal_gemm_run: weight planes and bf16 rows as the engine's callers make them
 
 #include <algorithm>
 
@@ -2969,42 +2970,117 @@ int gemm_run(const GemmPlan& pl, const GemmArgs* probs, int count, hipStream_t s
   return dr_check_launch("gemm");
 }
 
-// internal (not in dreamer_hip.h), for the host tests: the plan of a batch given as 17 ints per problem (below; flags
-// and the misalignment nibbles mis0 / mis1 of the dummy pointers as tests/test_gemm_plan_host.py names them; strides
-// the list leaves out follow lda, ldb or ldy).  Writes the steps (GemmStep as ints) to out; returns their count, or
-// -rc and the message in msg.
-extern "C" int dr_internal_gemm_plan(int lay, int amode, int count, const int* in, int* out, int out_steps, char* msg,
-                                     int msg_cap) {
-  GemmArgs pr[4];
-  for (int i = 0; i < count && i < 4; ++i) {
-    const int *v = in + 17 * i, fl = v[11];
-    auto ptr = [&](int slot, int nib, bool on) {  // nib: 0-7 of mis0, 8-11 of mis1, -1 aligned
-      const int mis = nib < 0 ? 0 : (v[14 + nib / 8] >> (4 * (nib % 8))) & 15;
-      return on ? (float*)(((uintptr_t)(16 * i + slot + 1) << 32) + mis) : nullptr;
-    };
-    GemmArgs g = gemm_args();
-    g.M = v[0]; g.N = v[1]; g.K = v[2]; g.C = v[8]; g.R = v[9]; g.na = v[10];
-    g.bf16 = (fl >> 7) & 1; g.epi = (fl >> 8) & 3; g.out_conv = (fl >> 11) & 1; g.accumulate = (fl >> 13) & 1;
-    g.A = ptr(0, 0, true); g.lda = v[3];
-    g.A2 = ptr(1, 1, fl & 1); g.lda2 = v[4]; g.ksplitA = v[5];
-    g.W = ptr(2, 2, true); g.ldb = v[6];
-    g.Y = ptr(3, 3, true); g.ldy = v[7];
-    g.ln_g = ptr(4, 4, fl & 2); g.ln_b = ptr(5, 5, fl & 2);
-    g.a_out = ptr(6, 6, fl & 4); g.ld_aout = v[16];
-    g.pre = ptr(7, 7, fl & 8); g.ld_pre = v[3];
-    g.splitk_ws = ptr(8, -1, fl & 16); g.splitk_floats = v[12];
-    g.wsplit = (const unsigned short*)ptr(9, 8, fl & 32); g.wsplit_np = v[13];
-    g.A16 = (const unsigned short*)ptr(10, 9, fl & 64);
-    g.W2 = ptr(11, -1, fl & 1024); g.ldb2 = v[6];
-    g.addend = ptr(12, -1, fl & 4096); g.ld_add = v[7];
-    g.bias = ptr(13, 10, fl & 16384);
-    g.z_out = ptr(14, 11, g.epi == EPI_SAMPLE); g.ldz = v[7];
-    pr[i] = g;
+// internal (not in dreamer_hip.h), for the tests: one problem of a batch from the 17 ints tests/test_gemm_plan_host.py
+// gives per problem (flags and the misalignment nibbles mis0 / mis1 as that file names them; strides the list leaves
+// out follow lda, ldb or ldy).  Both hooks below fill their GemmArgs here, so the batch the planner is asked about on
+// the host is the batch that runs; only the pointer source differs: ptr(slot, nibble, on) for the 15 slots A, A2, W,
+// Y, ln_g, ln_b, a_out, pre, splitk_ws, wsplit, A16, W2, addend, bias, z_out.  num / xp (NULL = neutral): the fields
+// the 17 ints do not carry, in the order of the GX_* / GP_* lists.
+enum { GX_ALPHA, GX_ACT, GX_LDY2, GX_NSPLITY, GX_KSPLITB, GX_NSPLITB, GX_LD_ADD, GX_LD_PRE, GX_LD_SV, GX_LD_SOFT, GX_LD_MU,
+       GX_LD_SIG, GX_LD_ACT, GX_GB_LDH, GX_GB_LDO, GX_GB_HD, GX_OHOW, GX_UNIMIX, GX_DET, GX_STEP, GX_LDB2, GX_COUNT = 24 };
+enum { GP_Y2, GP_SV_GY, GP_SV_XH, GP_SOFT, GP_IDX, GP_ZVAL, GP_Q, GP_EPS, GP_MU, GP_SIG, GP_ACT, GP_GB_H, GP_GB_R, GP_GB_U,
+       GP_GB_N, GP_GB_GHN, GP_GB_GI, GP_GB_GH, GP_GB_HO, GP_COUNT = 24 };
+template <class PtrSource>
+static GemmArgs hook_args(const int* v, PtrSource ptr, const double* num, void* const* xp) {
+  const int fl = v[11];
+  GemmArgs g = gemm_args();
+  g.M = v[0]; g.N = v[1]; g.K = v[2]; g.C = v[8]; g.R = v[9]; g.na = v[10];
+  g.bf16 = (fl >> 7) & 1; g.epi = (fl >> 8) & 3; g.out_conv = (fl >> 11) & 1; g.accumulate = (fl >> 13) & 1;
+  g.A = ptr(0, 0, true); g.lda = v[3];
+  g.A2 = ptr(1, 1, fl & 1); g.lda2 = v[4]; g.ksplitA = v[5];
+  g.W = ptr(2, 2, true); g.ldb = v[6];
+  g.Y = ptr(3, 3, true); g.ldy = v[7];
+  g.ln_g = ptr(4, 4, fl & 2); g.ln_b = ptr(5, 5, fl & 2);
+  g.a_out = ptr(6, 6, fl & 4); g.ld_aout = v[16];
+  g.pre = ptr(7, 7, fl & 8); g.ld_pre = v[3];
+  g.splitk_ws = ptr(8, -1, fl & 16); g.splitk_floats = v[12];
+  g.wsplit = (const unsigned short*)ptr(9, 8, fl & 32); g.wsplit_np = v[13];
+  g.A16 = (const unsigned short*)ptr(10, 9, fl & 64);
+  g.W2 = ptr(11, -1, fl & 1024); g.ldb2 = v[6];
+  g.addend = ptr(12, -1, fl & 4096); g.ld_add = v[7];
+  g.bias = ptr(13, 10, fl & 16384);
+  g.z_out = ptr(14, 11, g.epi == EPI_SAMPLE); g.ldz = v[7];
+  if (num) {
+    g.alpha = (float)num[GX_ALPHA]; g.act = (int)num[GX_ACT];
+    g.ldy2 = (long long)num[GX_LDY2]; g.nsplitY = (int)num[GX_NSPLITY];
+    g.ksplitB = (int)num[GX_KSPLITB]; g.nsplitB = (int)num[GX_NSPLITB]; g.ldb2 = (long long)num[GX_LDB2];
+    g.ld_add = (long long)num[GX_LD_ADD]; g.ld_pre = (long long)num[GX_LD_PRE]; g.ld_sv = (long long)num[GX_LD_SV];
+    g.ld_soft = (long long)num[GX_LD_SOFT]; g.ld_mu = (long long)num[GX_LD_MU]; g.ld_sig = (long long)num[GX_LD_SIG];
+    g.ld_act = (long long)num[GX_LD_ACT];
+    g.gb.ldh = (long long)num[GX_GB_LDH]; g.gb.ldo = (long long)num[GX_GB_LDO]; g.gb.Hd = (int)num[GX_GB_HD];
+    g.oh = (int)num[GX_OHOW]; g.ow = 1;  // the kernels use the product alone
+    g.unimix = (float)num[GX_UNIMIX]; g.det = (int)num[GX_DET]; g.step = (int)num[GX_STEP];
   }
-  const GemmPlan pl = gemm_plan((GemmLayout)lay, amode, pr, count);
+  if (xp) {
+    auto f = [&](int k) { return (float*)xp[k]; };
+    g.Y2 = f(GP_Y2); g.sv_gy = f(GP_SV_GY); g.sv_xh = f(GP_SV_XH);
+    g.soft_out = f(GP_SOFT); g.idx_out = (int*)xp[GP_IDX]; g.zval_out = f(GP_ZVAL);
+    g.noise.q = f(GP_Q); g.noise.eps = f(GP_EPS);
+    g.mu_out = f(GP_MU); g.sig_out = f(GP_SIG); g.act_out = f(GP_ACT);
+    g.gb.h = f(GP_GB_H); g.gb.r = f(GP_GB_R); g.gb.u = f(GP_GB_U); g.gb.n = f(GP_GB_N); g.gb.ghn = f(GP_GB_GHN);
+    g.gb.gi = f(GP_GB_GI); g.gb.gh = f(GP_GB_GH); g.gb.ho = f(GP_GB_HO);
+  }
+  return g;
+}
+// the plan's steps (GemmStep as ints) to out; their count, or -rc and the message in msg
+static int hook_steps(const GemmPlan& pl, int* out, int out_steps, char* msg, int msg_cap) {
   if (pl.rc != DR_OK) snprintf(msg, msg_cap, "%s", pl.err);
   static_assert(sizeof(GemmStep) == 21 * sizeof(int), "GemmStep is copied out as 21 ints");
   for (int k = 0; pl.rc == DR_OK && k < pl.nsteps && k < out_steps; ++k)
     memcpy(out + 21 * k, &pl.step[k], sizeof(GemmStep));
   return pl.rc != DR_OK ? -pl.rc : pl.nsteps;
+}
+
+// The plan of a batch on dummy pointers (problem and slot in the high word, the misalignment nibble in the low bits):
+// pure host code.  Writes the steps to out; returns their count, or -rc and the message in msg.
+extern "C" int dr_internal_gemm_plan(int lay, int amode, int count, const int* in, int* out, int out_steps, char* msg,
+                                     int msg_cap) {
+  GemmArgs pr[4];
+  for (int i = 0; i < count && i < 4; ++i) {
+    const int* v = in + 17 * i;
+    auto ptr = [&](int slot, int nib, bool on) {  // nib: 0-7 of mis0, 8-11 of mis1, -1 aligned
+      const int mis = nib < 0 ? 0 : (v[14 + nib / 8] >> (4 * (nib % 8))) & 15;
+      return on ? (float*)(((uintptr_t)(16 * i + slot + 1) << 32) + mis) : nullptr;
+    };
+    pr[i] = hook_args(v, ptr, nullptr, nullptr);
+  }
+  return hook_steps(gemm_plan((GemmLayout)lay, amode, pr, count), out, out_steps, msg, msg_cap);
+}
+
+// Its twin on real device memory: the same 17 ints per problem, ptrs = 15 device pointers per problem in the slot
+// order above (the caller has applied the misalignment nibbles; a slot whose flag is off is ignored), num / xp =
+// GX_COUNT doubles / GP_COUNT pointers per problem (either may be NULL).  Plans the batch, copies the steps out as
+// the plan hook does and runs that plan on `stream`.  Where the flags ask for weight planes or a bf16 copy of A, they
+// are made first, as the engine's callers make them (op_nt_repack_split3, op_to_bf16_2d), into the wsplit / A16 slot:
+// planes of wsplit_np rows ([K/32][3][wsplit_np][32]; a row count other than the engine's padding goes through
+// op_repack_multi, the same element code), A16 as M rows of lda.  Returns the step count, or -rc and the message;
+// nothing is launched for a batch the planner refuses.
+extern "C" int dr_internal_gemm_run(int lay, int amode, int count, const int* in, void* const* ptrs, const double* num,
+                                    void* const* xp, void* stream, int* out, int out_steps, char* msg, int msg_cap) {
+  hipStream_t s = (hipStream_t)stream;
+  GemmArgs pr[4];
+  for (int i = 0; i < count && i < 4; ++i) {
+    auto ptr = [&](int slot, int, bool on) { return on ? (float*)ptrs[15 * i + slot] : nullptr; };
+    pr[i] = hook_args(in + 17 * i, ptr, num ? num + GX_COUNT * i : nullptr, xp ? xp + GP_COUNT * i : nullptr);
+  }
+  const GemmPlan pl = gemm_plan((GemmLayout)lay, amode, pr, count);
+  const int n = hook_steps(pl, out, out_steps, msg, msg_cap);
+  if (n < 0) return n;
+  int rc = DR_OK;
+  for (int i = 0; i < count && rc == DR_OK; ++i) {
+    const GemmArgs& g = pr[i];
+    if (g.wsplit && g.wsplit_np > 0 && g.N > 0 && g.K > 0) {
+      if (g.wsplit_np == (g.N + 127) / 128 * 128) {
+        rc = op_nt_repack_split3(g.N, g.K, g.W, (int)g.ldb, (void*)g.wsplit, s);
+      } else {
+        RepackJob j = rj_nt(g.N, g.K, g.W, (int)g.ldb, (void*)g.wsplit);
+        j.c = g.wsplit_np; j.total = (long long)((g.K + 31) / 32) * 32 * g.wsplit_np;
+        rc = op_repack_multi(&j, 1, s);
+      }
+    }
+    if (rc == DR_OK && g.A16 && g.M > 0 && g.lda > 0) rc = op_to_bf16_2d(g.M, (int)g.lda, g.A, g.lda, (void*)g.A16, s);
+  }
+  if (rc == DR_OK) rc = gemm_run(pl, pr, count, s);
+  if (rc != DR_OK) return snprintf(msg, msg_cap, "%s", dr_last_error()), -rc;
+  return n;
 }
