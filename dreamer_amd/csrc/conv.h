@@ -4,6 +4,18 @@
 #pragma once
 #include "common.h"
 
+// Which kernel instantiation the conv-family launch helpers of this thread launched last: the kernel's name and
+// template arguments, e.g. k_conv_glds_s3<64,nchw,128,fwd> (read back by the dr_internal_conv_run test hook,
+// conv_hook.hip).  DR_CONV_NOTE formats its string once per call site and instantiation (compile-time arguments
+// only) and then stores one pointer per launch; nothing is launched differently.
+extern thread_local const char* dr_conv_form_last;
+const char* dr_conv_form(const char* fmt, ...);
+#define DR_CONV_NOTE(...)                                  \
+  do {                                                     \
+    static const char* form_ = dr_conv_form(__VA_ARGS__);  \
+    dr_conv_form_last = form_;                             \
+  } while (0)
+
 // k4 s2 p1 conv + bias + SiLU; in NHWC [n][ih][iw][cin], wr [cout][16][cin]
 // (op_conv_repack_pad layout); out NHWC [n][ih/2][iw/2][cout] or, with
 // out_nchw, [n][cout][ih/2][iw/2] (the encoder's flatten order).
@@ -149,7 +161,7 @@ struct ConvTArgs {
   float* out;           // NHWC [n][2h][2w][ldc]
   float* out2;          // CT_EPI_BIAS: optional SiLU(acc + bias) (same layout), for the consumers
   int silu_out;         // CT_EPI_BIAS: out receives SiLU(acc + bias) instead of acc + bias
-  int ldc;              // channel stride of out (>= cout; extra channels written as 0)
+  int ldc;              // channel stride of out and out2 (>= cout; extra channels inside the last column tile are written as 0)
   const float* pre;     // CT_EPI_DSILU: out = acc * SiLU'(pre) (pre NHWC, stride cout)
   // CT_EPI_TANH_MSE: mu = tanh(acc + bias); err = mu - target; out = coef[f] * err * (1 - mu^2)
   // (the gradient wrt the pre-tanh value); part[f * nparts + j] = sum err^2 over tile j of frame f

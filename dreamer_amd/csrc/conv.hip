@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_conv_nhwc(int n_frames, int ih, int iw,
   // NHWC output: weights are the MFMA A operand (DR_CONV_MFMA), so lane (r, q)
   // holds channels 4q..4q+3 of pixel r and stores float4s along c.  NCHW
   // output: pixels are the A operand, so the lane holds 4 consecutive pixels
-  // of channel r, one float4 along the plane (hw % 4 == 0, checked on the host).
+  // of channel r, one float4 along the plane where hw % 4 == 0, element stores otherwise.
   float cs[FN][4];  // CONV_EPI_DSILU with csum: this lane's channel sums
 #pragma unroll
   for (int j = 0; j < FN; ++j)
@@ -189,6 +189,17 @@ __global__ __launch_bounds__(256) void k_conv_nhwc(int n_frames, int ih, int iw,
         if (m >= M || co >= cout) continue;
         const float bv = bias[co];
         f32x4 v = acc[i][j] + bv;
+        if (hw & 3) {  // a plane no float4 tiles (a 1 x 1 or 1 x 3 feature grid): element stores, rows past M masked
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const long long me = m + e;
+            if (me >= M) break;
+            if (pre) pre[me * cout + co] = v[e];
+            const long long fe = me / hw;
+            out[(fe * cout + co) * hw + (me - fe * hw)] = v[e] / (1.0f + expf(-v[e]));
+          }
+          continue;
+        }
         if (pre) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) pre[(m + e) * cout + co] = v[e];
@@ -657,8 +668,8 @@ int op_conv1_frames(int n, int nb, int ih, int iw, int cout, const dr_frames* sr
 template <int BM, int BN, int CIN, bool OUT_NCHW, int EPI>
 static int launch_conv(int n, int ih, int iw, int cout, const float* in, const float* wr, const float* bias,
                        float* out, float* pre, hipStream_t s, float* csum = nullptr) {
-  if (cout % 4 != 0 || (OUT_NCHW && ((ih / 2) * (iw / 2)) % 4 != 0)) {
-    dr_set_error("conv: float4 epilogue needs cout %% 4 == 0 (and oh*ow %% 4 == 0 for NCHW output)");
+  if (cout % 4 != 0) {
+    dr_set_error("conv: float4 epilogue needs cout %% 4 == 0");
     return DR_E_INVALID;
   }
   const long long M = (long long)n * (ih / 2) * (iw / 2);
@@ -676,6 +687,8 @@ static int launch_conv(int n, int ih, int iw, int cout, const float* in, const f
   (void)raised;
   hipLaunchKernelGGL((k_conv_nhwc<BM, BN, CIN, OUT_NCHW, EPI>), grid, dim3(256), 0, s, n, ih, iw, cout,
                      in, wr, bias, out, pre, csum);
+  DR_CONV_NOTE("k_conv_nhwc<%d,%d,%d,%s,%s>", BM, BN, CIN, OUT_NCHW ? "nchw" : "nhwc",
+               EPI == CONV_EPI_DSILU ? "dsilu" : "fwd");
   return dr_check_launch("conv");
 }
 
@@ -693,6 +706,7 @@ int op_conv_nhwc_ex(int n, int cin, int ih, int iw, int cout, const float* in, c
     }
     hipLaunchKernelGGL(k_conv1_direct, dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(256), 0, s, n, ih, iw, cout, in, wr,
                        bias, out, pre);
+    DR_CONV_NOTE("k_conv1_direct");
     return dr_check_launch("conv1_direct");
   }
   if (epi == CONV_EPI_DSILU && (out_nchw || !pre)) {
@@ -708,6 +722,7 @@ int op_conv_nhwc_ex(int n, int cin, int ih, int iw, int cout, const float* in, c
     }
     hipLaunchKernelGGL(k_conv4_direct_dsilu, dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(256), 0, s, n, ih, iw, cout,
                        in, wr, pre, out, csum);
+    DR_CONV_NOTE("k_conv4_direct_dsilu");
     return dr_check_launch("conv4_direct_dsilu");
   }
 #define DR_CONV_L(BM, BN, C, NCHW)                                                                \

@@ -562,6 +562,7 @@ static int launch_glds_s3(int n, int ih, int iw, int cout, const float* in, cons
   }
   GS3Args g = {n, ih, iw, cout, 0, in, (const u16*)wr, bias, out, nullptr, pre};
   hipLaunchKernelGGL((k_conv_glds_s3<C, NCHW, BN, EPI, RW>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0, s, g);
+  DR_CONV_NOTE("k_conv_glds_s3<%d,%s,%d,%s>", C, NCHW ? "nchw" : "nhwc", BN, EPI == CONV_EPI_DSILU ? "dsilu" : "fwd");
   return dr_check_launch("conv_glds_s3");
 }
 
@@ -614,6 +615,7 @@ static int launch_glds_t3(const ConvTArgs& a, const void* wr, hipStream_t s) {
   GS3Args g = {a.n, a.h, a.w, a.cout, a.silu_out, a.in, (const u16*)wr, a.bias, a.out, a.out2, const_cast<float*>(a.pre)};
   hipLaunchKernelGGL((k_conv_glds_s3<C, false, BN, EPI, RW, true>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512),
                      0, s, g);
+  DR_CONV_NOTE("k_conv_glds_s3<%d,nhwc,%d,%s,up>", C, BN, EPI == CT_EPI_DSILU ? "dsilu" : "bias");
   return dr_check_launch("convT_glds_s3");
 }
 

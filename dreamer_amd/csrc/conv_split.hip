@@ -1069,6 +1069,7 @@ static int launch_s1_f32(int n, int ih, int iw, int cout, const float* in, const
   }
   hipLaunchKernelGGL((k_conv_s1<256, BN, CIN, NCHW, EPI, false>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0,
                      s, n, ih, iw, cout, in, (const u16*)wr, bias, out, pre);
+  DR_CONV_NOTE("k_conv_s1<256,%d,%d,%s,%s>", BN, CIN, NCHW ? "nchw" : "nhwc", EPI == CONV_EPI_DSILU ? "dsilu" : "fwd");
   return dr_check_launch("conv_split3 (one term)");
 }
 
@@ -1517,7 +1518,11 @@ bool op_convT_cls_supported(int n, int cin, int h, int w, int cout) {
 static int launch_convT_cls(int epi, const ConvTArgs& a, const void* wr, hipStream_t s, int terms) {
   const long long tiles = (long long)a.n * (a.h / CC_TY) * (a.w / CC_TX);
   const dim3 grid((unsigned)dr_xcd_grid((int)tiles));
-#define DR_CCL(E, T) hipLaunchKernelGGL((k_convT_cls<E, T>), grid, dim3(256), 0, s, a, (const u16*)wr)
+#define DR_CCL(E, T)                                                                         \
+  do {                                                                                       \
+    hipLaunchKernelGGL((k_convT_cls<E, T>), grid, dim3(256), 0, s, a, (const u16*)wr);        \
+    DR_CONV_NOTE("k_convT_cls<%s,%d>", E == CT_EPI_DSILU ? "dsilu" : "bias", T);             \
+  } while (0)
   if (epi == CT_EPI_DSILU) {
     if (terms == 1) DR_CCL(CT_EPI_DSILU, 1);
     else DR_CCL(CT_EPI_DSILU, 3);
@@ -1546,6 +1551,7 @@ static int launch_t1(const ConvTArgs& a, const void* wr, hipStream_t s) {
   const long long tiles = 4 * (((long long)a.n * a.h * a.w + 255) / 256) * (a.cout / BN);
   hipLaunchKernelGGL((k_convT_s1<256, BN, C, EPI>), dim3((unsigned)dr_xcd_grid((int)tiles)), dim3(512), 0, s, a,
                      (const u16*)wr);
+  DR_CONV_NOTE("k_convT_s1<256,%d,%d,%s>", BN, C, EPI == CT_EPI_DSILU ? "dsilu" : "bias");
   return dr_check_launch("convT_split3 (one term)");
 }
 
@@ -1948,9 +1954,12 @@ int op_wgrad_split3(int n, int h, int w, int ca, int cb, const float* lo, int ld
   }
   const int tiles = (ca / bm) * (16 * cb / bn);
   const int lh = ilog2_exact(h), lw = ilog2_exact(w);
-#define DR_W3L(BM, BN)                                                                                            \
-  hipLaunchKernelGGL((k_wgrad_s1<BM, BN>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, lh, lw, ca, \
-                     cb, lo, lda, hi, ldb, ch, ws)
+#define DR_W3L(BM, BN)                                                                                              \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((k_wgrad_s1<BM, BN>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, lh, lw, ca, \
+                       cb, lo, lda, hi, ldb, ch, ws);                                                               \
+    DR_CONV_NOTE("k_wgrad_s1<%d,%d>", BM, BN);                                                                      \
+  } while (0)
   if (terms == 1) {
     if (bn == 512) {
       DR_W3L(64, 512);
@@ -1964,9 +1973,12 @@ int op_wgrad_split3(int n, int h, int w, int ca, int cb, const float* lo, int ld
       else DR_W3L(32, 128);
     }
   } else {  // six products: the double-buffered kernel (WM step fp32 13.87 -> 13.82 ms, r06l)
-#define DR_W3D(BM, BN)                                                                                            \
-  hipLaunchKernelGGL((k_wgrad_split3_db<BM, BN, 32>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, \
-                     lh, lw, ca, cb, lo, lda, hi, ldb, ch, ws)
+#define DR_W3D(BM, BN)                                                                                              \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((k_wgrad_split3_db<BM, BN, 32>), dim3((unsigned)dr_xcd_grid(tiles * ns)), dim3(512), 0, s, n, \
+                       lh, lw, ca, cb, lo, lda, hi, ldb, ch, ws);                                                   \
+    DR_CONV_NOTE("k_wgrad_split3_db<%d,%d,32>", BM, BN);                                                            \
+  } while (0)
     if (bm == 128) DR_W3D(128, 128);
     else if (bn == 256) DR_W3D(64, 256);
     else DR_W3D(64, 128);

@@ -163,6 +163,7 @@ extern "C" int dr_encoder_features(const dr_dims* d, const dr_world_model* wm, c
              "image size must be a multiple of 2^depth (16, or 32 for the 5-layer encoder)");
   DR_REQUIRE(d->enc_f1 % 4 == 0 && d->enc_f2 % 4 == 0, "encoder filter counts must be multiples of 4");
   DR_REQUIRE(d->precision == DR_PREC_FP32 || d->precision == DR_PREC_BF16, "precision must be DR_PREC_FP32/BF16");
+  if (d->precision == DR_PREC_FP32) DR_TRY(dims_envelope(__func__, d, ENV_ENCODER_FWD));
   const int n = B * T;
   Carve c(ws);
   EncWs w;

@@ -53,7 +53,21 @@ static inline int conv_bias_aligned(const char* fn, const char* layer, int k, co
 // obs_dim % 4, image size a multiple of 2^depth) -- stated once and checked
 // before an entry point's first launch.  parts: what the entry point runs.
 // The deep checks stay where they are.
-enum { ENV_GRU = 1, ENV_SAMPLER = 2, ENV_ACTOR = 4, ENV_ENCODER = 8 };
+//
+// Filter counts are channel counts of the conv kernels, which are instantiated
+// per input-channel count: op_conv_nhwc_ex takes cin in {4, 8, ..., 256},
+// op_convT_nhwc cin in {8, ..., 256}, op_convT_out3 cin in {8, 16, 32, 64} (the
+// six-product / one-term kernels take subsets, and the engine falls back to
+// these).  The stacks are 3 -> f1 -> f2 -> 2 f2 -> 4 f2 (-> 4 f2) and its mirror:
+//   ENV_ENCODER_FWD (dr_encoder_features, fp32): f1, f2, 2 f2 (depth 5: 4 f2) are
+//     conv input channels: f1 in {4, ..., 256}, f2 in {4, ..., 128} ({4, ..., 64});
+//   ENV_ENCODER (the training step): 4 f2 is also the input-channel count of the
+//     last conv's data gradient (an upsampling conv), and counts are multiples of 8:
+//     f1 in {8, ..., 256}, f2 in {8, 16, 32, 64};
+//   ENV_DECODER (dr_decoder_fwd, the training step): 4 f2, 2 f2, f2 feed
+//     op_convT_nhwc and f1 feeds op_convT_out3: f1, f2 in {8, 16, 32, 64}.
+enum { ENV_GRU = 1, ENV_SAMPLER = 2, ENV_ACTOR = 4, ENV_ENCODER = 8, ENV_DECODER = 16, ENV_ENCODER_FWD = 32 };
+static inline bool filter_pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
 static inline int dims_envelope(const char* fn, const dr_dims* d, int parts) {
 #define DR_ENVELOPE(ok, field, value, limit)                                                                  \
   do {                                                                                                        \
@@ -75,10 +89,22 @@ static inline int dims_envelope(const char* fn, const dr_dims* d, int parts) {
                 "must divide 32 (1, 2, 4, 8, 16 or 32)");
   if ((parts & ENV_ENCODER) && d->obs_dim > 0)
     DR_ENVELOPE(d->obs_dim % 4 == 0, "obs_dim", d->obs_dim, "must be a multiple of 4");
+  if ((parts & ENV_ENCODER_FWD) && d->obs_dim <= 0) {
+    DR_ENVELOPE(filter_pow2_in(d->enc_f1, 4, 256), "enc_f1", d->enc_f1, "must be one of 4, 8, 16, 32, 64, 128, 256");
+    if (d->enc_depth == 5)
+      DR_ENVELOPE(filter_pow2_in(d->enc_f2, 4, 64), "enc_f2", d->enc_f2,
+                  "must be one of 4, 8, 16, 32, 64 (5-layer encoder)");
+    else
+      DR_ENVELOPE(filter_pow2_in(d->enc_f2, 4, 128), "enc_f2", d->enc_f2, "must be one of 4, 8, 16, 32, 64, 128");
+  }
+  if ((parts & ENV_DECODER) && d->obs_dim <= 0) {
+    DR_ENVELOPE(filter_pow2_in(d->dec_f1, 8, 64), "dec_f1", d->dec_f1, "must be one of 8, 16, 32, 64");
+    DR_ENVELOPE(filter_pow2_in(d->dec_f2, 8, 64), "dec_f2", d->dec_f2, "must be one of 8, 16, 32, 64");
+  }
   if ((parts & ENV_ENCODER) && d->obs_dim <= 0) {
     const int depth = d->enc_depth == 5 ? 5 : 4;
-    DR_ENVELOPE(d->enc_f1 > 0 && d->enc_f1 % 4 == 0, "enc_f1", d->enc_f1, "must be a positive multiple of 4");
-    DR_ENVELOPE(d->enc_f2 > 0 && d->enc_f2 % 4 == 0, "enc_f2", d->enc_f2, "must be a positive multiple of 4");
+    DR_ENVELOPE(filter_pow2_in(d->enc_f1, 8, 256), "enc_f1", d->enc_f1, "must be one of 8, 16, 32, 64, 128, 256");
+    DR_ENVELOPE(filter_pow2_in(d->enc_f2, 8, 64), "enc_f2", d->enc_f2, "must be one of 8, 16, 32, 64");
     DR_ENVELOPE(d->img_h > 0 && d->img_h % (1 << depth) == 0, "img_h", d->img_h,
                 "must be a multiple of 2^depth (16, or 32 for the 5-layer encoder)");
     DR_ENVELOPE(d->img_w > 0 && d->img_w % (1 << depth) == 0, "img_w", d->img_w,

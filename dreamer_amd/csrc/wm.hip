@@ -639,7 +639,7 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
                   hipStream_t s) {
   DR_REQUIRE(d && wm && dec && src && bt && losses && gw && gd && stats && B > 0 && T >= 2, "null argument or T < 2");
   DR_REQUIRE(bt->actions && bt->rewards && bt->continues, "window actions / rewards / continues required");
-  DR_TRY(dims_envelope("dr_wm_train", d, ENV_GRU | ENV_SAMPLER | ENV_ENCODER));
+  DR_TRY(dims_envelope("dr_wm_train", d, ENV_GRU | ENV_SAMPLER | ENV_ENCODER | ENV_DECODER));
   DR_REQUIRE(vae_depth_ok(d), "enc_depth must be 0, 4 or 5");
   DR_REQUIRE(d->obs_dim > 0 || (d->img_h % (1 << vae_depth(d)) == 0 && d->img_w % (1 << vae_depth(d)) == 0),
              "image size must be a multiple of 2^depth (16, or 32 for the 5-layer VAE)");
@@ -1236,6 +1236,7 @@ extern "C" int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, co
   DR_REQUIRE(vae_depth_ok(d), "enc_depth must be 0, 4 or 5");
   DR_REQUIRE(d->obs_dim > 0 || (d->img_h % (1 << vae_depth(d)) == 0 && d->img_w % (1 << vae_depth(d)) == 0),
              "image size must be a multiple of 2^depth (16, or 32 for the 5-layer VAE)");
+  DR_TRY(dims_envelope(__func__, d, ENV_DECODER));
   DR_REQUIRE(d->dec_f1 % 8 == 0 && d->dec_f2 % 8 == 0, "decoder filter counts must be multiples of 8");
   Carve c(ws);
   DecWs w;

@@ -216,6 +216,7 @@ __global__ __launch_bounds__(256) void k_convT_nhwc(ConvTArgs a) {
           if (co >= ldc) break;
           if (co >= cout) {
             a.out[opix * ldc + co] = 0.0f;
+            if (EPI == CT_EPI_BIAS && a.out2) a.out2[opix * ldc + co] = 0.0f;
             continue;
           }
           const float v = acc[i][j][e];
@@ -247,6 +248,7 @@ __global__ __launch_bounds__(256) void k_convT_nhwc(ConvTArgs a) {
         if (co >= ldc) continue;
         if (co >= cout) {  // padding channels of a wider output row
           a.out[opix * ldc + co] = 0.0f;
+          if (EPI == CT_EPI_BIAS && a.out2) a.out2[opix * ldc + co] = 0.0f;
           continue;
         }
         const float v = acc[i][j][e];
@@ -291,10 +293,13 @@ static int launch_convT(const ConvTArgs& a, hipStream_t s) {
     return DR_E_INVALID;
   }
   dim3 grid((unsigned)dr_xcd_grid((int)tiles));
-  if (a.silu_in)
+  if (a.silu_in) {
     hipLaunchKernelGGL((k_convT_nhwc<BM, BN, CIN, EPI, true>), grid, dim3(256), 0, s, a);
-  else
+    DR_CONV_NOTE("k_convT_nhwc<%d,%d,%d,%s,silu_in>", BM, BN, CIN, EPI == CT_EPI_DSILU ? "dsilu" : "bias");
+  } else {
     hipLaunchKernelGGL((k_convT_nhwc<BM, BN, CIN, EPI, false>), grid, dim3(256), 0, s, a);
+    DR_CONV_NOTE("k_convT_nhwc<%d,%d,%d,%s,plain>", BM, BN, CIN, EPI == CT_EPI_DSILU ? "dsilu" : "bias");
+  }
   return dr_check_launch("convT");
 }
 
@@ -466,10 +471,13 @@ int op_convT_out3(const ConvTArgs& a, hipStream_t s) {
   }
 #define DR_O3(C)                                                                       \
   do {                                                                                 \
-    if (loss)                                                                          \
+    if (loss) {                                                                        \
       hipLaunchKernelGGL((k_convT_out3<C, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);  \
-    else                                                                               \
+      DR_CONV_NOTE("k_convT_out3<%d,loss>", C);                                        \
+    } else {                                                                           \
       hipLaunchKernelGGL((k_convT_out3<C, false>), dim3((unsigned)blocks), dim3(256), 0, s, a); \
+      DR_CONV_NOTE("k_convT_out3<%d,mu>", C);                                          \
+    }                                                                                  \
   } while (0)
   switch (a.cin) {
     case 8: DR_O3(8); break;
@@ -759,12 +767,16 @@ int op_conv_wgrad(int n, int h, int w, int ca, int cb, const float* lo, int lda,
   }
   const int tiles = ((ca + bm - 1) / bm) * (16 * cb / 64);
   dim3 grid((unsigned)(tiles * ns));
-  if (bm == 32)
+  if (bm == 32) {
     hipLaunchKernelGGL(k_conv_wgrad<32>, grid, dim3(256), 0, s, n, h, w, ca, cb, lo, lda, lo_silu, hi, ldb, ns, ch, ws);
-  else if (bm == 128)
+    DR_CONV_NOTE("k_conv_wgrad<32>");
+  } else if (bm == 128) {
     hipLaunchKernelGGL(k_conv_wgrad<128>, grid, dim3(256), 0, s, n, h, w, ca, cb, lo, lda, lo_silu, hi, ldb, ns, ch, ws);
-  else
+    DR_CONV_NOTE("k_conv_wgrad<128>");
+  } else {
     hipLaunchKernelGGL(k_conv_wgrad<64>, grid, dim3(256), 0, s, n, h, w, ca, cb, lo, lda, lo_silu, hi, ldb, ns, ch, ws);
+    DR_CONV_NOTE("k_conv_wgrad<64>");
+  }
   DR_TRY(dr_check_launch("conv_wgrad"));
   const int total = ca * 16 * cb;
   hipLaunchKernelGGL(k_wgrad_reduce, dim3((total + 63) / 64), dim3(1024), 0, s, ca, cb, cbo, ns, ws, dw, scale,
@@ -880,6 +892,7 @@ int op_chan_sum_final(int nb, int C, const float* part, float* out, int accumula
     return DR_E_INVALID;
   }
   hipLaunchKernelGGL(k_chan_sum_final, dim3(C), dim3(256), 0, s, nb, C, part, out, accumulate);
+  DR_CONV_NOTE("k_chan_sum_final");
   return dr_check_launch("chan_sum_final");
 }
 
@@ -896,10 +909,13 @@ int op_chan_sum(long long rows, int C, const float* X, int ldx, float* out, int 
   }
   const long long chunk = (rows + nb - 1) / nb;
   const int cp4 = chan_pow2(C < 4 ? 4 : C);
-  if (ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && ldx >= ((C + 3) & ~3))
+  if (ldx % 4 == 0 && ((uintptr_t)X & 15) == 0 && ldx >= ((C + 3) & ~3)) {
     hipLaunchKernelGGL(k_chan_sum_part4, dim3(nb), dim3(256), 0, s, rows, C, cp4, X, ldx, chunk, ws);
-  else
+    DR_CONV_NOTE("k_chan_sum_part4");
+  } else {
     hipLaunchKernelGGL(k_chan_sum_part, dim3(nb), dim3(256), 0, s, rows, C, chan_pow2(C), X, ldx, chunk, ws);
+    DR_CONV_NOTE("k_chan_sum_part");
+  }
   DR_TRY(dr_check_launch("chan_sum_part"));
   hipLaunchKernelGGL(k_chan_sum_final, dim3(C), dim3(256), 0, s, nb, C, ws, out, accumulate);
   return dr_check_launch("chan_sum_final");

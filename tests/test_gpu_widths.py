@@ -16,6 +16,9 @@ fused heads tail, the tile routes) always lands on the same side.  Here:
   at most 1e-3 of a case's draws (tests/test_widths_host.py: 0 or 1 here).
 * dr_mlp3_fwd over an M x K x N table against O.mlp3 in float64, one row per
   GEMM route (MLP3_SHAPES), at test_blocks_teacher_forced's bound.
+* the conv stack off SMALL's and FULL's (widths_cases.CONV_WIDTHS: strip, rect, mixed -- non-square frames, a
+  1 x 3 feature grid, filter sets that send neighbouring layers to different kernel families): the world-model
+  step at (B, T) = (4, 4) and (24, 3) under the same checks, dr_encoder_features and dr_decoder_fwd on their own.
 * the supported widths: a config outside them is refused by
   the first call, before any launch, with a message naming the limit."""
 import pytest
@@ -26,10 +29,11 @@ from gpu_helpers import close, cpu, flip_report
 from mlp3_shapes import MLP3_SHAPES
 from oracle import dreamer_oracle as O
 from test_gpu_wm import check_grads_and_params
-from widths_cases import WIDTHS, bptt_case, critic_case, guard_cap, widths_config, wm_case
+from widths_cases import CONV_WIDTHS, WIDTHS, bptt_case, critic_case, guard_cap, widths_config, wm_case
 
 pytestmark = pytest.mark.gpu
 NAMES = sorted(WIDTHS)
+CONV_NAMES = sorted(CONV_WIDTHS)
 
 
 def _err(a, b):
@@ -82,12 +86,11 @@ def test_critic_vs_float64(name, B, H, gpu):
         close(g_gpu, g_ref.float(), 1e-4, 1e-5 * scale, f"{tag} grad {k}")
 
 
-@pytest.mark.parametrize("B,T", [(4, 4), (128, 3)])
-@pytest.mark.parametrize("name", NAMES)
-def test_wm_step_vs_oracle(name, B, T, gpu):
+def _check_wm_step(name, B, T, gpu):
+    """One library step against the oracle's at widths_config(name): the checks of test_wm_step_vs_oracle."""
     cfg = widths_config(name)
-    d, wm, out, ref, q, names, P0, tg = wm_case(cfg, B, T, gpu, replay_data(512, (32, 32), cfg["action_dims"]),
-                                                cpu_init=True)
+    d, wm, out, ref, q, names, P0, tg = wm_case(cfg, B, T, gpu, replay_data(512, tuple(cfg["observation_dims"]),
+                                                                            cfg["action_dims"]), cpu_init=True)
     tag = f"{name} WM B{B} T{T}"
     guard_cap(tg)
     C = wm.latent_num_columns
@@ -121,6 +124,55 @@ def test_wm_step_vs_oracle(name, B, T, gpu):
     n_amb = check_grads_and_params(named, keys, P0, lambda k: gref[k], lambda k: post[k],
                                    lambda t: t.reshape(-1), tag)
     print(f"{tag}: {n_amb} sign-ambiguous parameters")
+
+
+@pytest.mark.parametrize("B,T", [(4, 4), (128, 3)])
+@pytest.mark.parametrize("name", NAMES)
+def test_wm_step_vs_oracle(name, B, T, gpu):
+    _check_wm_step(name, B, T, gpu)
+
+
+# ---------------------------------------------------------------------------
+# the conv stack off SMALL and FULL (widths_cases.CONV_WIDTHS: strip, rect, mixed)
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("B,T", [(4, 4), (24, 3)])
+@pytest.mark.parametrize("name", CONV_NAMES)
+def test_conv_stack_wm_step_vs_oracle(name, B, T, gpu):
+    _check_wm_step(name, B, T, gpu)
+
+
+@pytest.mark.parametrize("name", CONV_NAMES)
+def test_conv_stack_encoder_and_decoder_vs_oracle(name, gpu):
+    """dr_encoder_features and dr_decoder_fwd on their own at the conv-stack configs against the oracle's encoder
+    conv stack + feature projection and its decoder_forward, rtol 1e-4 / atol 1e-5 (test_decoder_forward's)."""
+    import torch.nn.functional as F
+    from test_gpu_bf16 import _features
+    from widths_cases import build_dreamer
+    cfg = widths_config(name, batch_size=4, horizon=3)
+    d, P = build_dreamer(cfg, gpu, cpu_init=True)
+    wm = d.world_model
+    H, W = cfg["observation_dims"]
+    R, C = cfg["latent_state_dims"]
+    g = torch.Generator().manual_seed(11)
+    for n in (1, 13):  # one frame; several frames in one pixel tile with a ragged tail
+        frames = torch.randint(0, 256, (n, 3, H, W), generator=g, dtype=torch.uint8)
+        got = _features(wm.packed(), wm.dims(d.agent), frames, gpu)
+        x = O.normalise_obs(frames.float())
+        for i in range(4):
+            x = F.silu(F.conv2d(x, P[f"world_model.encoder.feature_extractor.{2 * i}.weight"],
+                                P[f"world_model.encoder.feature_extractor.{2 * i}.bias"], stride=2, padding=1))
+        flat = x.flatten(1)
+        ref = (flat @ P["world_model.encoder.latent_mapper.0.weight"][:, :flat.shape[1]].t()
+               + P["world_model.encoder.latent_mapper.0.bias"])
+        print(f"{name} encoder features n{n}: {_err(got, ref)}")
+        close(got, ref, 1e-4, 1e-5, f"{name} encoder features n{n}")
+    h = torch.randn(3, 2, cfg["hidden_state_dims"], generator=g)
+    z = torch.nn.functional.one_hot(torch.randn(3, 2, R, C, generator=g).argmax(-1), C).float()
+    with torch.no_grad():
+        mu = wm.decoder(h.to(gpu), z.to(gpu))
+    ref = O.decoder_forward(h, z, P, (wm.observation_dim_x, wm.observation_dim_y))
+    print(f"{name} decoder mu: {_err(mu, ref)}")
+    close(mu, ref, 1e-4, 1e-5, f"{name} decoder mu")
 
 
 # ---------------------------------------------------------------------------
@@ -188,11 +240,16 @@ OUTSIDE = [
     (dict(latent_state_dims=[40, 8]), "rows", 40, "at most 32"),
     (dict(latent_state_dims=[12, 12]), "cols", 12, "divide 32"),
     (dict(action_dims=9), "action", 9, "at most 8"),
+    # filter counts no conv kernel is instantiated for: the imagination runs no conv, the training step refuses
+    (dict(encoder_filter_num_1=24), "enc_f1", 24, "one of 8, 16, 32, 64, 128, 256"),
+    (dict(decoder_filter_num_1=128), "dec_f1", 128, "one of 8, 16, 32, 64"),
 ]
+CONV_FIELDS = ("enc_f1", "enc_f2", "dec_f1", "dec_f2")
 
 
 def test_outside_supported_widths_is_refused_up_front(gpu):
-    """hidden 90, rows 10, rows 40, cols 12, actions 9: the model builds; the
+    """hidden 90, rows 10, rows 40, cols 12, actions 9, and the filter counts
+    enc_f1 = 24 and dec_f1 = 128 (training step only): the model builds; the
     first _imagine_raw and the first train_step_hip raise DR_E_INVALID with
     the limit and the value before any launch (dims_envelope is the entry
     points' first statement after their null checks; what precedes the call
@@ -210,11 +267,14 @@ def test_outside_supported_widths_is_refused_up_front(gpu):
         g = torch.Generator().manual_seed(1)
         z0 = torch.nn.functional.one_hot(torch.randint(0, C, (B, 1, R), generator=g), C).float().to(gpu)
         h0 = torch.randn(B, 1, Hd, generator=g).to(gpu)
-        with pytest.raises(L.HipError) as ei:
-            d._imagine_raw(z0, h0)
-        msg = str(ei.value)
-        assert ei.value.code == L.DR_E_INVALID and "dr_imagine_fwd" in msg, msg
-        assert f"{field} = {value}" in msg and words in msg and "supported widths" in msg, msg
+        if field in CONV_FIELDS:
+            d._imagine_raw(z0, h0)  # no conv stack behind the imagination: these widths do not concern it
+        else:
+            with pytest.raises(L.HipError) as ei:
+                d._imagine_raw(z0, h0)
+            msg = str(ei.value)
+            assert ei.value.code == L.DR_E_INVALID and "dr_imagine_fwd" in msg, msg
+            assert f"{field} = {value}" in msg and words in msg and "supported widths" in msg, msg
         fr, ac, rw, ct = replay_data(16, (32, 32), A)
         obs = torch.tensor(fr[:B * T].reshape(B, T, 3, 32, 32), dtype=torch.float32).to(gpu)
         act = torch.tensor(ac[:B * T].reshape(B, T, A)).to(gpu)

@@ -8,17 +8,19 @@ import pytest
 import torch
 
 from formula import replay_data
-from widths_cases import WIDTHS, bptt_oracle, critic_oracle, guard_cap, widths_config, wm_oracle
+from widths_cases import CONV_WIDTHS, WIDTHS, bptt_oracle, critic_oracle, guard_cap, widths_config, wm_oracle
 
 DREAM_BATCHES = (4, 20, 128)
 DREAM_H = 3
 CRITIC_SHAPES = ((20, 2), (128, 2))       # B (H + 1) = 60 and 384 rows
 WM_SHAPES = ((4, 4), (128, 3))
 NAMES = sorted(WIDTHS)
+CONV_WM_SHAPES = ((4, 4), (24, 3))        # the conv-stack configs (widths_cases.CONV_WIDTHS): 128 and 576 draws
+CONV_NAMES = sorted(CONV_WIDTHS)
 
 
 def wm_replay(cfg):
-    return replay_data(512, (32, 32), cfg["action_dims"])
+    return replay_data(512, tuple(cfg["observation_dims"]), cfg["action_dims"])
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -68,4 +70,35 @@ def test_oracle_wm_step(name, B, T):
     print(f"{name} B{B} T{T}: WM step guarded {tg.guarded}/{tg.draws} draws, norm before clipping "
           f"{float(ref['norm']):.1f}")
     assert float(ref["norm"]) > 100.0  # the clip path is live
+    assert bool(torch.isfinite(ref["total"])) and all(bool(torch.isfinite(g).all()) for g in ref["grads_clipped"])
+
+
+@pytest.mark.parametrize("name", CONV_NAMES)
+def test_conv_config_constructs_on_cpu(name):
+    from dreamer_amd import Dreamer
+    cfg = widths_config(name)
+    sd = Dreamer(cfg, "cpu").state_dict()
+    H, W = cfg["observation_dims"]
+    e1, e2 = cfg["encoder_filter_num_1"], cfg["encoder_filter_num_2"]
+    d1, d2 = cfg["decoder_filter_num_1"], cfg["decoder_filter_num_2"]
+    assert tuple(sd["world_model.encoder.feature_extractor.0.weight"].shape) == (e1, 3, 4, 4)
+    assert tuple(sd["world_model.encoder.feature_extractor.6.weight"].shape) == (4 * e2, 2 * e2, 4, 4)
+    assert sd["world_model.encoder.latent_mapper.0.weight"].shape[1] == 4 * e2 * (H // 16) * (W // 16) + cfg[
+        "hidden_state_dims"]
+    assert tuple(sd["world_model.decoder.image_builder.0.weight"].shape) == (4 * d2, 2 * d2, 4, 4)
+    assert tuple(sd["world_model.decoder.image_builder.6.weight"].shape) == (d1, 3, 4, 4)
+
+
+@pytest.mark.parametrize("B,T", CONV_WM_SHAPES)
+@pytest.mark.parametrize("name", CONV_NAMES)
+def test_oracle_wm_step_conv_stacks(name, B, T):
+    """The conv-stack configs' oracle stage: no guarded draw of the 128 / 576, gradient norms of 198 to 828."""
+    cfg = widths_config(name)
+    d, wm, _, ref, q, names, P0, tg = wm_oracle(cfg, B, T, "cpu", wm_replay(cfg))
+    guard_cap(tg)
+    assert tg.draws == T * B * cfg["latent_state_dims"][0] == {4: 128, 24: 576}[B]
+    print(f"{name} B{B} T{T}: WM step guarded {tg.guarded}/{tg.draws} draws, norm before clipping "
+          f"{float(ref['norm']):.1f}")
+    assert tg.guarded == 0
+    assert 190.0 < float(ref["norm"]) < 840.0  # above 100: the clip path is live
     assert bool(torch.isfinite(ref["total"])) and all(bool(torch.isfinite(g).all()) for g in ref["grads_clipped"])

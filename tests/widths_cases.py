@@ -55,8 +55,34 @@ WIDTHS = {
 }
 
 
+def _stack(frame, enc, dec):
+    """SMALL's MLP widths with another conv stack: frame (H, W), encoder and decoder filters (f1, f2)."""
+    cfg = dict(SMALL)
+    cfg.update(observation_dims=list(frame), encoder_filter_num_1=enc[0], encoder_filter_num_2=enc[1],
+               decoder_filter_num_1=dec[0], decoder_filter_num_2=dec[1])
+    return cfg
+
+
+# which conv-family routes each stack forces that SMALL (32 x 32, 8 / 16: every layer on the f32-MFMA kernels) and
+# FULL (64 x 64, 32 / 64: conv2.. and the decoder on the six-product / LDS-DMA kernels) never take
+CONV_WIDTHS = {
+    # feature grid 1 x 3: every f32 kernel (k_conv_nhwc, k_convT_nhwc, k_conv_wgrad, both channel sums) at h = 1,
+    # non-square and with w not a power of two; the last conv writes 3 pixels per frame (no NCHW float4 epilogue
+    # would fit: oh ow % 4 != 0 is refused, so this pins that the encoder's last layer at 1 x 3 has a route)
+    "strip": _stack((16, 48), (8, 16), (8, 16)),
+    # encoder 3 -> 16 -> 32 -> 64 -> 128: conv1 / conv2 stay on k_conv_nhwc (cin 4, 16), conv3 (32 -> 64) and conv4
+    # (64 -> 128) take the six-product kernels; decoder 128 -> 64 -> 32 -> 16 -> 3: 128 -> 64 on the LDS-DMA kernel,
+    # 64 -> 32 at 4 x 8 misses the all-class kernel (h % 8) and falls to k_convT_nhwc, k_convT_out3<16>
+    "rect": _stack((32, 64), (16, 32), (16, 32)),
+    # encoder 3 -> 32 -> 16 -> 32 -> 64: conv2 (32 -> 16) and conv3 (cin 16) have no six-product form between conv1
+    # and conv4 (32 -> 64) that do; decoder 256 -> 128 -> 64 -> 8 -> 3: 256 and 128 input channels at 4 x 2 and
+    # 8 x 4, 64 -> 8 on k_convT_nhwc's 16-column tile, k_convT_out3<8>
+    "mixed": _stack((64, 32), (32, 16), (8, 64)),
+}
+
+
 def widths_config(name, **over):
-    cfg = dict(WIDTHS[name])
+    cfg = dict(WIDTHS[name] if name in WIDTHS else CONV_WIDTHS[name])
     cfg.update(over)
     return cfg
 
