@@ -282,6 +282,16 @@ static int pow2_ge(int c) {
 struct MlpBwd {  // backward scratch of one 3-layer head (and its LayerNorm saves)
   float *gx2, *gp2, *gy2, *xh2, *gx1, *gp1, *gy1, *xh1;
 };
+// one head MLP of the world model over the M1 rows t >= 1 (WmWs::head: prior, reward, continue)
+struct HeadWs {
+  float *p1, *x1, *p2, *x2, *lg;  // .0 / .3 pre-activations, their LN-SiLU outputs, the logits
+  float* g;                       // dL/d logits
+  float *t6, *t3, *t0;            // transposed weights
+  // split3 planes (below) of the forward Linears and of the input-gradient
+  // Linears; pl_f6 / pl_h6: the prior only (NULL for the reward and continue heads)
+  void *pl_f0, *pl_f3, *pl_f6, *pl_h6, *pl_h3, *pl_h0;
+  MlpBwd b;
+};
 struct WmWs {
   void* tn;         // split3 TN scratch (tn_launch)
   size_t tn_bytes;
@@ -292,8 +302,7 @@ struct WmWs {
   float *act_tm, *rew_tm, *cont_tm, *zeros, *h_all, *z_all, *soft, *plog, *pre_m, *x_m, *sr, *su, *sn, *sghn, *gi, *gh,
       *wt;
   int* idx;
-  // heads (M1 rows)
-  float *pp1, *px1, *pp2, *px2, *prior_lg, *rp1, *rx1, *rp2, *rx2, *rew_lg, *cp1, *cx1, *cp2, *cx2, *cont_lg;
+  HeadWs head[3];  // heads (M1 rows): prior, reward, continue
   // decoder: upscaler pre-activations (du1, du2 = .3 output NHWC), convT k's output pre-activation dq[k] (k < N-1;
   // vector mode: dq[0] = image_builder.0 pre, dq[1] = mu) and its SiLU dqp[k]; dgout = dL/d(pre-tanh output)
   float *du1, *dx1, *du2, *du2p, *dq[DR_MAX_DEPTH], *dqp[DR_MAX_DEPTH], *dgout, *w3p, *b3p;
@@ -311,26 +320,25 @@ struct WmWs {
   // rows, W_hh^T; K = 3 Hd)
   void *s3wtb, *s3twhh;
   // split3 planes of the tall (B (T-1) / B T rows) NT products' weights: the
-  // heads' input-gradient Linears (.3 / .0 of each, the prior's .6), the
-  // decoder upscaler's .3 / .0, the encoder projection (forward, and its
-  // transposed input gradient) -- k_gemm_split3 instead of the f32 tile kernel
-  void *pl_h3[3], *pl_h0[3], *pl_h6, *pl_up3, *pl_up0, *pl_w0tp, *pl_map0f;
+  // heads' input-gradient Linears (.3 / .0 of each, the prior's .6: HeadWs
+  // pl_h3 / pl_h0 / pl_h6), the decoder upscaler's .3 / .0, the encoder
+  // projection (forward, and its transposed input gradient) -- k_gemm_split3
+  // instead of the f32 tile kernel
+  void *pl_up3, *pl_up0, *pl_w0tp, *pl_map0f;
   // ... and of the forward heads / upscaler over B (T - 1) rows: the first
-  // Linears (prior, reward, continue, upscaler.0), the .3 layers, the prior's
-  // .6, upscaler.3 (permuted rows)
-  void *pl_f0[4], *pl_f3[3], *pl_f6, *pl_fup3;
+  // Linears (HeadWs pl_f0; upscaler.0: pl_fup0), the .3 layers (pl_f3), the
+  // prior's .6 (pl_f6), upscaler.3 (permuted rows)
+  void *pl_fup0, *pl_fup3;
   // loss
   float *coef_row, *coef_obs, *obs_part, *obs_bpart, *kl_grp, *rew_row, *cont_row, *scal, *stats;
   float* csp;  // per-tile channel sums of the last decoder layer's input gradient (k_conv_nhwc csum)
   // backward
-  float *gH, *gZ, *glog, *gpost, *g_prior, *g_rew, *g_cont;
-  MlpBwd bp, br, bc;
+  float *gH, *gZ, *glog, *gpost;
   float *gxu, *gpu, *gyu, *xhu, *dgq[DR_MAX_DEPTH], *dgu2, *dw3p, *db3p;  // dgq[k]: dL/d dq[k]
   float *ggi, *ggh, *gpre_m, *gy_m, *xh_m, *gx_s, *gh_dummy;
   float* gp[DR_MAX_DEPTH];  // dL/d pre[k]
-  // transposed / permuted weights
-  float *t_pl6, *t_pl3, *t_pl0, *t_rl6, *t_rl3, *t_rl0, *t_cl6, *t_cl3, *t_cl0, *t_up3, *t_up0, *t_map3, *t_map0, *t_whh,
-      *w0tp;
+  // transposed / permuted weights (the heads': HeadWs t6 / t3 / t0)
+  float *t_up3, *t_up0, *t_map3, *t_map0, *t_whh, *w0tp;
   float *cws;  // conv weight-gradient / channel-sum scratch
   long long cws_n;
   float* sk;  // split-K partial planes of the tile GEMMs (reused launch to launch)
@@ -371,6 +379,19 @@ static WmDims wm_dims(const dr_dims* d, int B, int T) {
   }
   return w;
 }
+// one row of the head table: the head's weights and their gradients, its
+// widths (Linear [h | z] -> w1 -> w2 -> nout) and in_z (0: its input is h only)
+struct WmHead {
+  const dr_mlp3 *m, *g;
+  int w1, w2, nout, in_z;
+};
+// prior, reward, continue (wm / gw NULL: the widths alone, for the carve)
+static void wm_heads(const WmDims& D, const dr_world_model* wm, const dr_world_model* gw, WmHead* h) {
+  h[0] = {wm ? &wm->prior : nullptr, gw ? &gw->prior : nullptr, D.ph1, D.ph2, D.L, 0};
+  h[1] = {wm ? &wm->reward : nullptr, gw ? &gw->reward : nullptr, D.rh1, D.rh2, D.nb, 1};
+  h[2] = {wm ? &wm->cont : nullptr, gw ? &gw->cont : nullptr, D.ch1, D.ch2, 1, 1};
+}
+static inline int head_in(const WmDims& D, const WmHead& h) { return h.in_z ? D.Hd + D.L : D.Hd; }
 // channel stride of conv k's input (the frames are padded to 4 channels) and of convT k's output (3 -> 4)
 static inline int enc_cin_st(const WmDims& D, int k) { return k == 0 ? 4 : D.e[k]; }
 static inline int dec_cout_st(const WmDims& D, int k) { return k == D.N - 1 ? 4 : D.cd[k + 1]; }
@@ -440,16 +461,18 @@ static void wm_carve(Carve& c, const dr_dims* d, const WmDims& D, WmWs& w) {
   const long long M = D.M, M1 = D.M1, B = D.B;
   const int L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, N = D.N;
   const long long Dv = D.Dv;
+  WmHead hs[3];
+  wm_heads(D, nullptr, nullptr, hs);
   w.x0 = c.f(Dv ? M * Dv : M * D.pix[0] * 4);
   w.s3m0 = c.raw(op_nt_split3_ws_bytes(eh, Hd));
   w.s3whh = c.raw(op_nt_split3_ws_bytes(3 * Hd, Hd));
   w.s3wtb = c.raw(op_nt_split3_ws_bytes(L, 3 * Hd));
-  for (int i = 0; i < 3; ++i) {
-    w.pl_h3[i] = c.raw(op_nt_split3_ws_bytes(std::max(D.ph1, std::max(D.rh1, D.ch1)),
-                                             std::max(D.ph2, std::max(D.rh2, D.ch2))));
-    w.pl_h0[i] = c.raw(op_nt_split3_ws_bytes(Hd + L, std::max(D.ph1, std::max(D.rh1, D.ch1))));
+  for (HeadWs& h : w.head) {
+    h.pl_h3 = c.raw(op_nt_split3_ws_bytes(std::max(D.ph1, std::max(D.rh1, D.ch1)),
+                                          std::max(D.ph2, std::max(D.rh2, D.ch2))));
+    h.pl_h0 = c.raw(op_nt_split3_ws_bytes(Hd + L, std::max(D.ph1, std::max(D.rh1, D.ch1))));
   }
-  w.pl_h6 = c.raw(op_nt_split3_ws_bytes(D.ph2, L));
+  w.head[0].pl_h6 = c.raw(op_nt_split3_ws_bytes(D.ph2, L));
   if (!Dv) {
     w.pl_up3 = c.raw(op_nt_split3_ws_bytes(D.dh, D.Fd));
     w.pl_up0 = c.raw(op_nt_split3_ws_bytes(Hd + L, D.dh));
@@ -458,9 +481,10 @@ static void wm_carve(Carve& c, const dr_dims* d, const WmDims& D, WmWs& w) {
   {
     const int h1 = std::max(D.ph1, std::max(D.rh1, std::max(D.ch1, D.dh)));
     const int h2 = std::max(D.ph2, std::max(D.rh2, D.ch2));
-    for (int i = 0; i < 4; ++i) w.pl_f0[i] = c.raw(op_nt_split3_ws_bytes(h1, Hd + L));
-    for (int i = 0; i < 3; ++i) w.pl_f3[i] = c.raw(op_nt_split3_ws_bytes(h2, h1));
-    w.pl_f6 = c.raw(op_nt_split3_ws_bytes(L, D.ph2));
+    for (HeadWs& h : w.head) h.pl_f0 = c.raw(op_nt_split3_ws_bytes(h1, Hd + L));
+    w.pl_fup0 = c.raw(op_nt_split3_ws_bytes(h1, Hd + L));
+    for (HeadWs& h : w.head) h.pl_f3 = c.raw(op_nt_split3_ws_bytes(h2, h1));
+    w.head[0].pl_f6 = c.raw(op_nt_split3_ws_bytes(L, D.ph2));
     if (!Dv) w.pl_fup3 = c.raw(op_nt_split3_ws_bytes(D.Fd, D.dh));
   }
   w.pl_map0f = c.raw(op_nt_split3_ws_bytes(eh, D.F));
@@ -487,12 +511,11 @@ static void wm_carve(Carve& c, const dr_dims* d, const WmDims& D, WmWs& w) {
   w.gi = c.f(B * 3 * Hd); w.gh = c.f(B * 3 * Hd);
   w.wt = c.f((long long)(L + A) * 3 * Hd);
   w.idx = c.i((long long)D.T * 2 * B * d->rows);
-  w.pp1 = c.f(M1 * D.ph1); w.px1 = c.f(M1 * D.ph1); w.pp2 = c.f(M1 * D.ph2); w.px2 = c.f(M1 * D.ph2);
-  w.prior_lg = c.f(M1 * L);
-  w.rp1 = c.f(M1 * D.rh1); w.rx1 = c.f(M1 * D.rh1); w.rp2 = c.f(M1 * D.rh2); w.rx2 = c.f(M1 * D.rh2);
-  w.rew_lg = c.f(M1 * D.nb);
-  w.cp1 = c.f(M1 * D.ch1); w.cx1 = c.f(M1 * D.ch1); w.cp2 = c.f(M1 * D.ch2); w.cx2 = c.f(M1 * D.ch2);
-  w.cont_lg = c.f(M1);
+  for (int i = 0; i < 3; ++i) {
+    HeadWs& h = w.head[i];
+    h.p1 = c.f(M1 * hs[i].w1); h.x1 = c.f(M1 * hs[i].w1); h.p2 = c.f(M1 * hs[i].w2); h.x2 = c.f(M1 * hs[i].w2);
+    h.lg = c.f(M1 * hs[i].nout);
+  }
   w.du1 = c.f(M1 * D.dh); w.dx1 = c.f(M1 * D.dh); w.du2 = c.f(M1 * D.Fd); w.du2p = c.f(M1 * D.Fd);
   if (Dv) {  // dq[0] / dqp[0] = image_builder.0 pre / post SiLU [M1][Fd], dq[1] = the output mu [M1][Dv]
     w.dq[0] = c.f(M1 * D.Fd); w.dqp[0] = c.f(M1 * D.Fd); w.dq[1] = c.f(M1 * Dv);
@@ -525,10 +548,8 @@ static void wm_carve(Carve& c, const dr_dims* d, const WmDims& D, WmWs& w) {
   w.csp = Dv ? nullptr : c.f(((long long)M1 * (D.IH / 2) * (D.IW / 2) + 127) / 128 * D.cd[N - 1]);
   w.kl_grp = c.f(M1 * d->rows); w.rew_row = c.f(M1); w.cont_row = c.f(M1); w.scal = c.f(8); w.stats = c.f(8);
   w.gH = c.f(M * Hd); w.gZ = c.f(M * L); w.glog = c.f(M * L); w.gpost = c.f(M1 * L);
-  w.g_prior = c.f(M1 * L); w.g_rew = c.f(M1 * D.nb); w.g_cont = c.f(M1);
-  mlp_bwd_carve(c, M1, D.ph1, D.ph2, w.bp);
-  mlp_bwd_carve(c, M1, D.rh1, D.rh2, w.br);
-  mlp_bwd_carve(c, M1, D.ch1, D.ch2, w.bc);
+  for (int i = 0; i < 3; ++i) w.head[i].g = c.f(M1 * hs[i].nout);
+  for (int i = 0; i < 3; ++i) mlp_bwd_carve(c, M1, hs[i].w1, hs[i].w2, w.head[i].b);
   w.gxu = c.f(M1 * D.dh); w.gpu = c.f(M1 * D.dh); w.gyu = c.f(M1 * D.dh); w.xhu = c.f(M1 * D.dh);
   w.dgu2 = c.f(M1 * D.Fd);
   w.dw3p = c.f((long long)D.Fd * D.dh); w.db3p = c.f(D.Fd);
@@ -540,10 +561,11 @@ static void wm_carve(Carve& c, const dr_dims* d, const WmDims& D, WmWs& w) {
   } else {
     for (int k = 0; k < N; ++k) w.gp[k] = c.f(M * D.pix[k + 1] * D.e[k + 1]);
   }
-  w.t_pl6 = c.f((long long)L * D.ph2); w.t_pl3 = c.f((long long)D.ph2 * D.ph1); w.t_pl0 = c.f((long long)D.ph1 * Hd);
-  w.t_rl6 = c.f((long long)D.nb * D.rh2); w.t_rl3 = c.f((long long)D.rh2 * D.rh1);
-  w.t_rl0 = c.f((long long)D.rh1 * (Hd + L));
-  w.t_cl6 = c.f(D.ch2); w.t_cl3 = c.f((long long)D.ch2 * D.ch1); w.t_cl0 = c.f((long long)D.ch1 * (Hd + L));
+  for (int i = 0; i < 3; ++i) {
+    HeadWs& h = w.head[i];
+    h.t6 = c.f((long long)hs[i].nout * hs[i].w2); h.t3 = c.f((long long)hs[i].w2 * hs[i].w1);
+    h.t0 = c.f((long long)hs[i].w1 * head_in(D, hs[i]));
+  }
   w.t_up3 = c.f((long long)D.Fd * D.dh); w.t_up0 = c.f((long long)D.dh * (Hd + L));
   w.t_map3 = c.f((long long)L * eh); w.t_map0 = c.f((long long)eh * (D.F + Hd));
   w.t_whh = c.f((long long)3 * Hd * Hd); w.w0tp = c.f((long long)D.F * eh);
@@ -586,131 +608,91 @@ extern "C" size_t dr_wm_train_workspace_bytes(const dr_dims* d, int B, int T) {
   return c.off;
 }
 
-// input-gradient + weight-gradient pass of one head MLP (Linear-LN-SiLU x2 +
-// Linear) over M1 rows whose input is [h | z] (in_z = 0: h only).  Adds the
-// input gradient into gH/gZ rows t >= 1.
-static int head_bwd(const WmDims& D, const dr_mlp3& m, const dr_mlp3& g, int w1, int w2, int nout, const float* glog,
-                    const float* t6, const float* t3, const float* t0, const float* x1, const float* x2,
-                    const float* pre1, const float* pre2, int in_z, const float* hB, const float* zB, float* gHB,
-                    float* gZB, MlpBwd& b, float* sk, long long sk_n, void* tn, size_t tn_bytes, hipStream_t s,
-                    void* pl6 = nullptr, void* pl3 = nullptr, void* pl0 = nullptr) {
-  const int terms = D.terms;
-  const int M1 = D.M1, Hd = D.Hd, L = D.L;
-  const int n0 = in_z ? Hd + L : Hd;
-  // tall (>= 1024 rows): the input-gradient products on split3 planes of the
-  // transposed weights, split here (the weights change every step)
-  const bool tall = M1 >= 1024;
-  if (!tall) pl6 = pl3 = pl0 = nullptr;
-  if (nout % 4) pl6 = nullptr;
-  if (pl6) DR_TRY(op_nt_repack_split3(w2, nout, t6, nout, pl6, s));
-  if (pl3) DR_TRY(op_nt_repack_split3(w1, w2, t3, w2, pl3, s));
-  if (pl0) DR_TRY(op_nt_repack_split3(n0, w1, t0, w1, pl0, s));
-  {
-    GemmArgs g6 = bwd_nt(M1, w2, nout, glog, nout, t6, b.gx2, w2, 0);
-    wplanes(g6, pl6);
-    DR_TRY(run(G_NT, AM_PLAIN, g6, s));
-  }
-  DR_TRY(lnbwd_nt(M1, w1, w2, b.gx2, w2, pre2, w2, m.n4, t3, b.gx1, w1, 0, b.gp2, w2, b.gy2, b.xh2, nullptr, 0,
-                  INT_MAX, s, nullptr, pl3, sk, sk_n));
-  DR_TRY(lnbwd_nt(M1, n0, w1, b.gx1, w1, pre1, w1, m.n1, t0, gHB, Hd, 1, b.gp1, w1, b.gy1, b.xh1,
-                  in_z ? gZB : nullptr, L, in_z ? Hd : INT_MAX, s, nullptr, pl0, sk, sk_n));
-  GemmArgs p[3];
-  p[0] = bwd_w(nout, w2, M1, glog, nout, x2, w2, g.l6.w);
-  p[1] = bwd_w(w2, w1, M1, b.gp2, w2, x1, w1, g.l3.w);
-  p[2] = bwd_w(w1, in_z ? Hd + L : Hd, M1, b.gp1, w1, hB, Hd, g.l0.w);
-  if (in_z) {
-    p[2].W2 = zB; p[2].ldb2 = L; p[2].nsplitB = Hd;
-  }
-  splitk_all(p, 3, sk, sk_n);
-  DR_TRY(tn_launch(p, 3, tn, tn_bytes, s, terms));
-  ColsumJob cj[7] = {
-      {nout, glog, nout, nullptr, 0, g.l6.b}, {w2, b.gp2, w2, nullptr, 0, g.l3.b},
-      {w2, b.gy2, w2, b.xh2, w2, g.n4.w},     {w2, b.gy2, w2, nullptr, 0, g.n4.b},
-      {w1, b.gp1, w1, nullptr, 0, g.l0.b},    {w1, b.gy1, w1, b.xh1, w1, g.n1.w},
-      {w1, b.gy1, w1, nullptr, 0, g.n1.b},
-  };
-  return op_colsum_multi(M1, cj, 7, s);
+// ---------------------------------------------------------------------------
+// the training step, phase by phase: what the phases of one call share, built
+// once by wm_run after the checks and the carve (cin_t / cout_t point into D:
+// never copied)
+// ---------------------------------------------------------------------------
+struct WmCtx {
+  const dr_dims* d;
+  const dr_world_model *wm, *gw;  // weights / their gradients
+  const dr_decoder *dec, *gd;
+  WmDims D;
+  WmWs w;
+  WmHead head[3];  // prior, reward, continue (w.head[i] is head[i]'s workspace)
+  const dr_frames* src;
+  const dr_wm_batch* bt;
+  dr_noise noise;
+  dr_wm_loss_cfg cfg;
+  float *stats, *losses;
+  int rows_global, *skip;
+  float *hiddens_out, *latents_out, *post_logits_out;  // optional
+  hipStream_t s;
+  const float *hB, *zB, *post1;  // rows t >= 1 of h_all / z_all / plog
+  float *gHB, *gZB;              // ... of gH / gZ
+  const int *cin_t, *cout_t;     // convT k: cd[k] -> cd[k + 1] channels
+  int Wc;                        // latent classes rounded up to a power of two (the KL / sampler kernels' group width)
+  WmCtx() = default;
+  WmCtx(const WmCtx&) = delete;
+};
+
+static int silu(long long n, const float* x, float* y, hipStream_t s) {
+  hipLaunchKernelGGL(k_silu, dim3(blocks(n, 256)), dim3(256), 0, s, n, x, y);
+  return dr_check_launch("silu");
+}
+static int mul_dsilu(long long n, float* g, const float* pre, hipStream_t s) {
+  hipLaunchKernelGGL(k_mul_dsilu, dim3(blocks(n, 256)), dim3(256), 0, s, n, g, pre);
+  return dr_check_launch("mul_dsilu");
+}
+// Y[M][N] = A[M][K] W[K][N]: an input gradient against the weight as stored (the vector stand-ins' backward)
+static int nn_product(int M, int N, int K, const float* A, const float* Wkn, float* Y, hipStream_t s) {
+  GemmArgs g = gemm_args();
+  g.M = M; g.N = N; g.K = K; g.A = A; g.lda = K; g.W = Wkn; g.ldb = N; g.Y = Y; g.ldy = N;
+  return gemm_launch(G_NN, AM_PLAIN, &g, 1, s);
 }
 
-static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const dr_decoder* dec, int B, int T,
-                  const dr_frames* src, const dr_wm_batch* bt, dr_noise noise, dr_wm_loss_cfg cfg, float* stats,
-                  int rows_global, float* losses, int* skip, const dr_world_model* gw, const dr_decoder* gd,
-                  float* hiddens_out, float* latents_out, float* post_logits_out, void* ws, size_t ws_bytes,
-                  hipStream_t s) {
-  DR_REQUIRE(d && wm && dec && src && bt && losses && gw && gd && stats && B > 0 && T >= 2, "null argument or T < 2");
-  DR_REQUIRE(bt->actions && bt->rewards && bt->continues, "window actions / rewards / continues required");
-  DR_TRY(dims_envelope("dr_wm_train", d, ENV_GRU | ENV_SAMPLER | ENV_ENCODER | ENV_DECODER));
-  DR_REQUIRE(vae_depth_ok(d), "enc_depth must be 0, 4 or 5");
-  DR_REQUIRE(d->obs_dim > 0 || (d->img_h % (1 << vae_depth(d)) == 0 && d->img_w % (1 << vae_depth(d)) == 0),
-             "image size must be a multiple of 2^depth (16, or 32 for the 5-layer VAE)");
-  DR_REQUIRE(d->enc_f1 % 8 == 0 && d->enc_f2 % 8 == 0 && d->dec_f1 % 8 == 0 && d->dec_f2 % 8 == 0,
-             "encoder / decoder filter counts must be multiples of 8");
-  DR_REQUIRE(d->cols <= 64, "latent classes must be <= 64");
-  DR_REQUIRE(d->obs_dim == 0 || d->obs_dim % 4 == 0, "vector observations: obs_dim % 4 == 0 required");
-  const WmDims D = wm_dims(d, B, T);
-  // the NT products that take the tile route stay f32 in both modes (on the
-  // bf16 tile GEMM in bf16 mode they saved 0.1 ms but raised the posterior
-  // flips 1.7e-4 -> 1.7e-3, r04p)
-  GemmBf16Scope bf16_scope(false);
-  const bool vec = D.Dv > 0;
-  const int Dv = D.Dv;
-  Carve c(ws);
-  WmWs w;
-  wm_carve(c, d, D, w);
-  WS_CHECK(c, ws_bytes);
-  const int M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, nb = D.nb, F = D.F, R = d->rows;
-  const int IH = D.IH, IW = D.IW, N = D.N;
-  if (D.terms == 3) {  // the biases of the layers routed to the six-product kernels (forward and backward)
-    for (int k = 0; k < N; ++k) {
-      if (w.s3e[k]) DR_TRY(conv_bias_aligned(__func__, "conv", k, wm->conv[k].b));
-      if (w.t3d[k]) DR_TRY(conv_bias_aligned(__func__, "convt", k, dec->convt[k].b));
-    }
-  }
-  const float* hB = w.h_all + (long long)B * Hd;
-  const float* zB = w.z_all + (long long)B * L;
-  float* gHB = w.gH + (long long)B * Hd;
-  float* gZB = w.gZ + (long long)B * L;
-
-  const int* cin_t = D.cd;       // convT k: cd[k] -> cd[k + 1] channels
-  const int* cout_t = D.cd + 1;
-  if (rows_global <= 0) rows_global = M1;
-  if (phases & DR_WM_PREP) {
+static int wm_prep(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_world_model* wm = x.wm; const dr_decoder* dec = x.dec;
+  const int *cin_t = x.cin_t, *cout_t = x.cout_t;
+  const int B = D.B, M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, F = D.F, N = D.N;
   // ---- weights: repacks, transposes, permutations (fixed for the call) ----
-  if (!vec) {
-  // (the f32 layouts only for the layers without split planes: each repack is
-  // a ~5 us launch, 13 of them per step unused, r04zd)
-  for (int k = 0; k < N; ++k) {
-    if (!w.s3e[k]) DR_TRY(op_conv_repack_pad(D.e[k + 1], D.e[k], enc_cin_st(D, k), wm->conv[k].w, w.wr[k], s));
-    // Conv2d data gradient = upsampling conv with the weight read as [cin=co][cout=ci]
-    if (k > 0 && !w.t3e[k]) DR_TRY(op_convT_repack(D.e[k + 1], D.e[k], wm->conv[k].w, w.wqe[k], s));
-  }
-  for (int k = 0; k < N; ++k) {
-    if (k < N - 1) {
-      if (!w.t3d[k]) DR_TRY(op_convT_repack(cin_t[k], cout_t[k], dec->convt[k].w, w.wqd[k], s));
-    } else {
-      DR_TRY(op_convT_out3_repack(cin_t[k], dec->convt[k].w, w.wqd[k], s));
+  if (!D.Dv) {
+    // (the f32 layouts only for the layers without split planes: each repack is
+    // a ~5 us launch, 13 of them per step unused, r04zd)
+    for (int k = 0; k < N; ++k) {
+      if (!w.s3e[k]) DR_TRY(op_conv_repack_pad(D.e[k + 1], D.e[k], enc_cin_st(D, k), wm->conv[k].w, w.wr[k], s));
+      // Conv2d data gradient = upsampling conv with the weight read as [cin=co][cout=ci]
+      if (k > 0 && !w.t3e[k]) DR_TRY(op_convT_repack(D.e[k + 1], D.e[k], wm->conv[k].w, w.wqe[k], s));
     }
-    // ConvTranspose2d data gradient = strided Conv2d with the weight read as [out=ci][in=co]
-    if (!w.s3d[k]) DR_TRY(op_conv_repack_pad(cin_t[k], cout_t[k], dec_cout_st(D, k), dec->convt[k].w, w.wrd[k], s));
+    for (int k = 0; k < N; ++k) {
+      if (k < N - 1) {
+        if (!w.t3d[k]) DR_TRY(op_convT_repack(cin_t[k], cout_t[k], dec->convt[k].w, w.wqd[k], s));
+      } else {
+        DR_TRY(op_convT_out3_repack(cin_t[k], dec->convt[k].w, w.wqd[k], s));
+      }
+      // ConvTranspose2d data gradient = strided Conv2d with the weight read as [out=ci][in=co]
+      if (!w.s3d[k]) DR_TRY(op_conv_repack_pad(cin_t[k], cout_t[k], dec_cout_st(D, k), dec->convt[k].w, w.wrd[k], s));
+    }
+    for (int k = 0; k < N; ++k) {
+      if (w.s3e[k]) DR_TRY(op_conv_repack_split3(D.e[k + 1], D.e[k], wm->conv[k].w, w.s3e[k], s));
+      if (w.s3d[k]) DR_TRY(op_conv_repack_split3(cin_t[k], cout_t[k], dec->convt[k].w, w.s3d[k], s));
+      if (w.t3d[k]) DR_TRY(op_convT_repack_split3(cin_t[k], cout_t[k], dec->convt[k].w, w.t3d[k], s));
+      if (w.t3e[k]) DR_TRY(op_convT_repack_split3(D.e[k + 1], D.e[k], wm->conv[k].w, w.t3e[k], s));
+    }
   }
-  for (int k = 0; k < N; ++k) {
-    if (w.s3e[k]) DR_TRY(op_conv_repack_split3(D.e[k + 1], D.e[k], wm->conv[k].w, w.s3e[k], s));
-    if (w.s3d[k]) DR_TRY(op_conv_repack_split3(cin_t[k], cout_t[k], dec->convt[k].w, w.s3d[k], s));
-    if (w.t3d[k]) DR_TRY(op_convT_repack_split3(cin_t[k], cout_t[k], dec->convt[k].w, w.t3d[k], s));
-    if (w.t3e[k]) DR_TRY(op_convT_repack_split3(D.e[k + 1], D.e[k], wm->conv[k].w, w.t3e[k], s));
-  }
-  }  // !vec
   // decoder.upscaler.3 rows to NHWC order (vector mode: Pf = 1, the identity), so its output is the first convT's NHWC input
   DR_TRY(perm_rows(D.C0, D.Pf, D.dh, dec->up3.w, w.w3p, 1, s));
   DR_TRY(perm_rows(D.C0, D.Pf, 1, dec->up3.b, w.b3p, 1, s));
   {
-    TransposeJob tj[10] = {
-        {L, D.ph2, L, wm->prior.l6.w, w.t_pl6},          {D.ph2, D.ph1, D.ph2, wm->prior.l3.w, w.t_pl3},
-        {D.ph1, Hd, D.ph1, wm->prior.l0.w, w.t_pl0},     {nb, D.rh2, nb, wm->reward.l6.w, w.t_rl6},
-        {D.rh2, D.rh1, D.rh2, wm->reward.l3.w, w.t_rl3}, {D.rh1, Hd + L, D.rh1, wm->reward.l0.w, w.t_rl0},
-        {1, D.ch2, 1, wm->cont.l6.w, w.t_cl6},           {D.ch2, D.ch1, D.ch2, wm->cont.l3.w, w.t_cl3},
-        {D.ch1, Hd + L, D.ch1, wm->cont.l0.w, w.t_cl0},  {3 * Hd, L + A, 3 * Hd, wm->w_ih, w.wt},
-    };
+    TransposeJob tj[10];  // the heads' .6 / .3 / .0 in table order, then W_ih
+    for (int i = 0; i < 3; ++i) {
+      const WmHead& h = x.head[i]; const HeadWs& hw = w.head[i];
+      tj[3 * i] = {h.nout, h.w2, h.nout, h.m->l6.w, hw.t6};
+      tj[3 * i + 1] = {h.w2, h.w1, h.w2, h.m->l3.w, hw.t3};
+      tj[3 * i + 2] = {h.w1, head_in(D, h), h.w1, h.m->l0.w, hw.t0};
+    }
+    tj[9] = {3 * Hd, L + A, 3 * Hd, wm->w_ih, w.wt};
     DR_TRY(op_transpose_multi(tj, 10, s));
     TransposeJob tj2[5] = {
         {D.Fd, D.dh, D.Fd, w.w3p, w.t_up3},          {D.dh, Hd + L, D.dh, dec->up0.w, w.t_up0},
@@ -723,65 +705,77 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
   DR_TRY(perm_rows(D.e[N], D.Pf, eh, w.t_map0, w.w0tp, 1, s));
 
   // ---- window data ----
-  hipLaunchKernelGGL(k_wm_gather, dim3(blocks(M, 256)), dim3(256), 0, s, B, T, A, *bt, w.act_tm, w.rew_tm, w.cont_tm);
+  hipLaunchKernelGGL(k_wm_gather, dim3(blocks(M, 256)), dim3(256), 0, s, B, D.T, A, *x.bt, w.act_tm, w.rew_tm, w.cont_tm);
   DR_TRY(dr_check_launch("wm_gather"));
   DR_TRY(zero(w.zeros, (long long)B * (L + A + Hd), s));
-  hipLaunchKernelGGL(k_wm_masksum, dim3(1), dim3(256), 0, s, M1, w.cont_tm, stats);
-  DR_TRY(dr_check_launch("wm_masksum"));
-  }  // DR_WM_PREP
+  hipLaunchKernelGGL(k_wm_masksum, dim3(1), dim3(256), 0, s, M1, w.cont_tm, x.stats);
+  return dr_check_launch("wm_masksum");
+}
 
-  if (phases & DR_WM_FWD) {
-  hipLaunchKernelGGL(k_wm_coef, dim3(1), dim3(256), 0, s, M1, w.cont_tm, cfg.beta_pred, stats, w.scal, w.coef_row,
+// vector observations, encoder stand-in: pre[0] = X W1^T + b1, a[0] = SiLU, pre[N-1] = a[0] W2^T + b2, a[N-1] = SiLU
+static int wm_vec_encoder_fwd(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_world_model* wm = x.wm;
+  const int M = D.M, F = D.F, Dv = D.Dv, N = D.N;
+  DR_TRY(op_vec_gather(M, D.B, Dv, x.src, w.x0, s));
+  DR_TRY(run(G_NT, AM_PLAIN, lin(M, F, Dv, w.x0, Dv, wm->conv[0].w, Dv, wm->conv[0].b, w.pre[0], F), s));
+  DR_TRY(silu((long long)M * F, w.pre[0], w.a[0], s));
+  DR_TRY(run(G_NT, AM_PLAIN, lin(M, F, F, w.a[0], F, wm->conv[1].w, F, wm->conv[1].b, w.pre[N - 1], F), s));
+  return silu((long long)M * F, w.pre[N - 1], w.a[N - 1], s);
+}
+
+// ---- encoder over all M frames (VAE.py:57-75), activations kept ----
+static int wm_fwd_encoder(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_world_model* wm = x.wm;
+  const int B = D.B, M = D.M, Hd = D.Hd, eh = D.eh, F = D.F, IH = D.IH, IW = D.IW, N = D.N;
+  // the forward's first launch: the rows' prediction-loss factors, from the (all-reduced) mask sum of wm_prep
+  hipLaunchKernelGGL(k_wm_coef, dim3(1), dim3(256), 0, s, D.M1, w.cont_tm, x.cfg.beta_pred, x.stats, w.scal, w.coef_row,
                      w.coef_obs);
   DR_TRY(dr_check_launch("wm_coef"));
-
-  // ---- encoder over all M frames (VAE.py:57-75), activations kept ----
   float* aL = w.a[N - 1];  // the flattened features (NCHW; vector mode: the MLP's last activation)
-  if (vec) {  // MLP stand-in: pre[0] = X W1^T + b1, a[0] = SiLU, pre[N-1] = a[0] W2^T + b2, a[N-1] = SiLU
-    DR_TRY(op_vec_gather(M, B, Dv, src, w.x0, s));
-    DR_TRY(run(G_NT, AM_PLAIN, lin(M, F, Dv, w.x0, Dv, wm->conv[0].w, Dv, wm->conv[0].b, w.pre[0], F), s));
-    hipLaunchKernelGGL(k_silu, dim3(blocks((long long)M * F, 256)), dim3(256), 0, s, (long long)M * F, w.pre[0], w.a[0]);
-    DR_TRY(dr_check_launch("silu"));
-    DR_TRY(run(G_NT, AM_PLAIN, lin(M, F, F, w.a[0], F, wm->conv[1].w, F, wm->conv[1].b, w.pre[N - 1], F), s));
-    hipLaunchKernelGGL(k_silu, dim3(blocks((long long)M * F, 256)), dim3(256), 0, s, (long long)M * F, w.pre[N - 1], aL);
-    DR_TRY(dr_check_launch("silu"));
+  if (D.Dv) {
+    DR_TRY(wm_vec_encoder_fwd(x));
   } else {
-  // (conv1's weight gradient reads it; pad channel = 1: its bias gradient comes
-  // out of the same product, enc_bias_fused below)
-  DR_TRY(op_frames_nhwc4(M, B, IH, IW, src, w.x0, s, 1.0f));
-  // conv1 + conv2 in one kernel from the u8 ring (k_enc12_split3_x8; bf16 mode: k_enc12_s1) with the
-  // backward's saves; other shapes / sources take the per-layer kernels
-  int k0 = 0;
-  if (N >= 2 && w.e12w1 && w.s3e[1]) {
-    // DR_E_INVALID: shape / source not covered (per-layer kernels below); any
-    // other failure (a launch or occupancy query) is returned
-    const int rc12 = op_enc12_split3_ex(M, B, IH, IW, D.e[1], D.e[2], src, wm->conv[0].w, wm->conv[0].b,
-                                        wm->conv[1].w, wm->conv[1].b, w.e12w1, w.s3e[1], w.a[1], w.pre[0], w.a[0],
-                                        w.pre[1], s, D.terms);
-    if (rc12 == DR_OK) k0 = 2;
-    else if (rc12 != DR_E_INVALID) return rc12;
-  }
-  for (int k = k0; k < N; ++k) {
-    if (w.s3e[k])
-      DR_TRY(op_conv_split3_ex(M, D.e[k], IH >> k, IW >> k, D.e[k + 1], w.a[k - 1], w.s3e[k], wm->conv[k].b, w.a[k],
-                               k == N - 1 ? 1 : 0, w.pre[k], CONV_EPI_FWD, s, D.terms));
-    else
-      DR_TRY(op_conv_nhwc_ex(M, enc_cin_st(D, k), IH >> k, IW >> k, D.e[k + 1], k ? w.a[k - 1] : w.x0, w.wr[k],
-                             wm->conv[k].b, w.a[k], k == N - 1 ? 1 : 0, w.pre[k], CONV_EPI_FWD, s));
-  }
-  }
-  {
-    GemmArgs g = lin(M, eh, F, aL, F, wm->map0.w, F + Hd, wm->map0.b, w.feat, eh);
-    splitk_all(&g, 1, w.sk, w.sk_n);
-    if (M >= 1024) {  // the feature projection on split3 planes (as the epoch's warm-start encoder)
-      DR_TRY(op_nt_repack_split3(eh, F, wm->map0.w, F + Hd, w.pl_map0f, s));
-      wplanes(g, w.pl_map0f);
+    // (conv1's weight gradient reads it; pad channel = 1: its bias gradient comes
+    // out of the same product, enc_bias_fused below)
+    DR_TRY(op_frames_nhwc4(M, B, IH, IW, x.src, w.x0, s, 1.0f));
+    // conv1 + conv2 in one kernel from the u8 ring (k_enc12_split3_x8; bf16 mode: k_enc12_s1) with the
+    // backward's saves; other shapes / sources take the per-layer kernels
+    int k0 = 0;
+    if (N >= 2 && w.e12w1 && w.s3e[1]) {
+      // DR_E_INVALID: shape / source not covered (per-layer kernels below); any
+      // other failure (a launch or occupancy query) is returned
+      const int rc12 = op_enc12_split3_ex(M, B, IH, IW, D.e[1], D.e[2], x.src, wm->conv[0].w, wm->conv[0].b,
+                                          wm->conv[1].w, wm->conv[1].b, w.e12w1, w.s3e[1], w.a[1], w.pre[0], w.a[0],
+                                          w.pre[1], s, D.terms);
+      if (rc12 == DR_OK) k0 = 2;
+      else if (rc12 != DR_E_INVALID) return rc12;
     }
-    DR_TRY(run(G_NT, AM_PLAIN, g, s));
+    for (int k = k0; k < N; ++k) {
+      if (w.s3e[k])
+        DR_TRY(op_conv_split3_ex(M, D.e[k], IH >> k, IW >> k, D.e[k + 1], w.a[k - 1], w.s3e[k], wm->conv[k].b, w.a[k],
+                                 k == N - 1 ? 1 : 0, w.pre[k], CONV_EPI_FWD, s, D.terms));
+      else
+        DR_TRY(op_conv_nhwc_ex(M, enc_cin_st(D, k), IH >> k, IW >> k, D.e[k + 1], k ? w.a[k - 1] : w.x0, w.wr[k],
+                               wm->conv[k].b, w.a[k], k == N - 1 ? 1 : 0, w.pre[k], CONV_EPI_FWD, s));
+    }
   }
+  GemmArgs g = lin(M, eh, F, aL, F, wm->map0.w, F + Hd, wm->map0.b, w.feat, eh);
+  splitk_all(&g, 1, w.sk, w.sk_n);
+  if (M >= 1024) {  // the feature projection on split3 planes (as the epoch's warm-start encoder)
+    DR_TRY(op_nt_repack_split3(eh, F, wm->map0.w, F + Hd, w.pl_map0f, s));
+    wplanes(g, w.pl_map0f);
+  }
+  return run(G_NT, AM_PLAIN, g, s);
+}
 
-  // ---- posterior scan (unroll_model, WorldModel.py:97-107) ----
-  const long long idx_stride = 2LL * B * R;
+// ---- posterior scan (unroll_model, WorldModel.py:97-107) ----
+static int wm_fwd_scan(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_dims* d = x.d; const dr_world_model* wm = x.wm;
+  const int B = D.B, T = D.T, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, F = D.F;
+  const long long idx_stride = 2LL * B * d->rows;
   // B >= 128 (split GRU): the next step's hidden product h W_hh^T + b_hh rides
   // in the same grouped launch as latent_mapper.0 (both read only h_t)
   bool gh_pre = false;
@@ -822,246 +816,303 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
     GemmArgs gp = lin_ln(B, L, eh, w.pre_m + rb * eh, eh, wm->map1, wm->map3.w, wm->map3.b, w.plog + rb * L, L);
     gp.a_out = w.x_m + rb * eh;
     gp.ld_aout = eh;
-    with_sampler(gp, d, noise, t, z_t, L, w.idx + t * idx_stride, w.soft + rb * L, L);
+    with_sampler(gp, d, x.noise, t, z_t, L, w.idx + t * idx_stride, w.soft + rb * L, L);
     DR_TRY(run(G_NT, AM_LNSILU, gp, s));
   }
+  return DR_OK;
+}
 
-  // ---- heads on rows t >= 1 (WorldModel.py:116-119) ----
-  {
-    GemmArgs p[4];
-    p[0] = lin(M1, D.ph1, Hd, hB, Hd, wm->prior.l0.w, Hd, wm->prior.l0.b, w.pp1, D.ph1);
-    p[1] = lin2(M1, D.rh1, hB, Hd, Hd, zB, L, L, wm->reward.l0.w, wm->reward.l0.b, w.rp1, D.rh1);
-    p[2] = lin2(M1, D.ch1, hB, Hd, Hd, zB, L, L, wm->cont.l0.w, wm->cont.l0.b, w.cp1, D.ch1);
-    p[3] = lin2(M1, D.dh, hB, Hd, Hd, zB, L, L, dec->up0.w, dec->up0.b, w.du1, D.dh);
-    if (M1 >= 1024) {  // tall: on split3 planes of the weights (gemm.hip s3_tall_ok), split per step
-      DR_TRY(op_nt_repack_split3(D.ph1, Hd, wm->prior.l0.w, Hd, w.pl_f0[0], s));
-      DR_TRY(op_nt_repack_split3(D.rh1, Hd + L, wm->reward.l0.w, Hd + L, w.pl_f0[1], s));
-      DR_TRY(op_nt_repack_split3(D.ch1, Hd + L, wm->cont.l0.w, Hd + L, w.pl_f0[2], s));
-      DR_TRY(op_nt_repack_split3(D.dh, Hd + L, dec->up0.w, Hd + L, w.pl_f0[3], s));
-      for (int i = 0; i < 4; ++i) wplanes(p[i], w.pl_f0[i]);
-      splitk_all(p, 4, w.sk, w.sk_n);
-    }
-    DR_TRY(gemm_launch(G_NT, AM_PLAIN, p, 4, s));
-  }
-  {
-    GemmArgs p[3];
-    p[0] = lin_ln(M1, D.ph2, D.ph1, w.pp1, D.ph1, wm->prior.n1, wm->prior.l3.w, wm->prior.l3.b, w.pp2, D.ph2);
-    p[0].a_out = w.px1; p[0].ld_aout = D.ph1;
-    p[1] = lin_ln(M1, D.rh2, D.rh1, w.rp1, D.rh1, wm->reward.n1, wm->reward.l3.w, wm->reward.l3.b, w.rp2, D.rh2);
-    p[1].a_out = w.rx1; p[1].ld_aout = D.rh1;
-    p[2] = lin_ln(M1, D.ch2, D.ch1, w.cp1, D.ch1, wm->cont.n1, wm->cont.l3.w, wm->cont.l3.b, w.cp2, D.ch2);
-    p[2].a_out = w.cx1; p[2].ld_aout = D.ch1;
-    if (M1 >= 1024) {
-      DR_TRY(op_nt_repack_split3(D.ph2, D.ph1, wm->prior.l3.w, D.ph1, w.pl_f3[0], s));
-      DR_TRY(op_nt_repack_split3(D.rh2, D.rh1, wm->reward.l3.w, D.rh1, w.pl_f3[1], s));
-      DR_TRY(op_nt_repack_split3(D.ch2, D.ch1, wm->cont.l3.w, D.ch1, w.pl_f3[2], s));
-      for (int i = 0; i < 3; ++i) wplanes(p[i], w.pl_f3[i]);
-    }
-    DR_TRY(gemm_launch(G_NT, AM_LNSILU, p, 3, s));
-  }
-  {
-    GemmArgs p[3];
-    p[0] = lin_ln(M1, L, D.ph2, w.pp2, D.ph2, wm->prior.n4, wm->prior.l6.w, wm->prior.l6.b, w.prior_lg, L);
-    p[0].a_out = w.px2; p[0].ld_aout = D.ph2;
-    p[1] = lin_ln(M1, nb, D.rh2, w.rp2, D.rh2, wm->reward.n4, wm->reward.l6.w, wm->reward.l6.b, w.rew_lg, nb);
-    p[1].a_out = w.rx2; p[1].ld_aout = D.rh2;
-    p[2] = lin_ln(M1, 1, D.ch2, w.cp2, D.ch2, wm->cont.n4, wm->cont.l6.w, wm->cont.l6.b, w.cont_lg, 1);
-    p[2].a_out = w.cx2; p[2].ld_aout = D.ch2;
-    if (M1 >= 1024) {  // (the prior's 1024 outputs; the reward's 255 / continue's 1 stay on the tile kernel)
-      DR_TRY(op_nt_repack_split3(L, D.ph2, wm->prior.l6.w, D.ph2, w.pl_f6, s));
-      wplanes(p[0], w.pl_f6);
-    }
-    DR_TRY(gemm_launch(G_NT, AM_LNSILU, p, 3, s));
-  }
-  // decoder (VAE.py:139-161): upscaler.3 pre-activation in NHWC, SiLU applied by the consumers
-  {
-    GemmArgs g = lin_ln(M1, D.Fd, D.dh, w.du1, D.dh, dec->up1, w.w3p, w.b3p, w.du2, D.Fd);
-    g.a_out = w.dx1; g.ld_aout = D.dh;
-    if (M1 >= 1024 && !vec) {
-      DR_TRY(op_nt_repack_split3(D.Fd, D.dh, w.w3p, D.dh, w.pl_fup3, s));
-      wplanes(g, w.pl_fup3);
-    }
-    DR_TRY(run(G_NT, AM_LNSILU, g, s));
-  }
-  if (vec) {
-    // image_builder stand-in: q = SiLU(du2) Wd1^T + bd1, mu = SiLU(q) Wd2^T + bd2; squared error vs rows t >= 1
-    const long long MF = (long long)M1 * D.Fd;
-    hipLaunchKernelGGL(k_silu, dim3(blocks(MF, 256)), dim3(256), 0, s, MF, w.du2, w.du2p);
-    DR_TRY(dr_check_launch("silu"));
-    DR_TRY(run(G_NT, AM_PLAIN, lin(M1, D.Fd, D.Fd, w.du2p, D.Fd, dec->convt[0].w, D.Fd, dec->convt[0].b, w.dq[0], D.Fd), s));
-    hipLaunchKernelGGL(k_silu, dim3(blocks(MF, 256)), dim3(256), 0, s, MF, w.dq[0], w.dqp[0]);
-    DR_TRY(dr_check_launch("silu"));
-    DR_TRY(run(G_NT, AM_PLAIN, lin(M1, Dv, D.Fd, w.dqp[0], D.Fd, dec->convt[1].w, D.Fd, dec->convt[1].b, w.dq[1], Dv), s));
-    hipLaunchKernelGGL(k_vec_mse, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, Dv, w.dq[1], w.x0 + (long long)B * Dv,
-                       w.coef_obs, w.dgout, w.obs_part);
-    DR_TRY(dr_check_launch("vec_mse"));
-  } else {
-    hipLaunchKernelGGL(k_silu, dim3(blocks((long long)M1 * D.Fd, 256)), dim3(256), 0, s, (long long)M1 * D.Fd,
-                       w.du2, w.du2p);
-    DR_TRY(dr_check_launch("silu"));
-    for (int k = 0; k < N; ++k) {
-      ConvTArgs a = {};
-      a.n = M1; a.cin = cin_t[k]; a.h = IH >> (N - k); a.w = IW >> (N - k); a.cout = cout_t[k];
-      a.in = k ? w.dqp[k - 1] : w.du2p; a.silu_in = 0; a.wq = w.wqd[k]; a.bias = dec->convt[k].b;
-      if (k == N - 1 && k > 0) {  // SiLU of the pre-activations on load (dqp[N - 2] is not stored)
-        a.in = w.dq[k - 1];
-        a.silu_in = 1;
-      }
-      if (k < N - 1) {
-        a.out = w.dq[k]; a.out2 = w.dqp[k]; a.ldc = cout_t[k];
-        if (w.t3d[k]) DR_TRY(op_convT_split3(CT_EPI_BIAS, a, w.t3d[k], s, D.terms));
-        else DR_TRY(op_convT_nhwc(CT_EPI_BIAS, a, s));
-      } else {
-        // Tanh + squared error against frames t >= 1 (WorldModel.py:129); writes dL/d(pre-tanh)
-        a.out = w.dgout; a.ldc = 4;
-        a.target = w.x0 + (long long)B * D.pix[0] * 4; a.tstride = 4;
-        a.coef = w.coef_obs; a.part = w.obs_part; a.bpart = w.obs_bpart;
-        DR_TRY(op_convT_nhwc(CT_EPI_TANH_MSE, a, s));
-      }
+// ---- heads on rows t >= 1 (WorldModel.py:116-119) ----
+// three grouped launches, one per layer, the heads in table order; the first
+// carries decoder.upscaler.0 as its fourth problem
+static int wm_fwd_heads(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder* dec = x.dec;
+  const int M1 = D.M1, L = D.L, Hd = D.Hd;
+  const bool tall = M1 >= 1024;  // on split3 planes of the weights (gemm.hip s3_tall_ok), split per step
+  GemmArgs p[4];
+  for (int i = 0; i < 3; ++i) {
+    const WmHead& h = x.head[i]; const HeadWs& hw = w.head[i];
+    p[i] = h.in_z ? lin2(M1, h.w1, x.hB, Hd, Hd, x.zB, L, L, h.m->l0.w, h.m->l0.b, hw.p1, h.w1)
+                  : lin(M1, h.w1, Hd, x.hB, Hd, h.m->l0.w, Hd, h.m->l0.b, hw.p1, h.w1);
+    if (tall) {
+      DR_TRY(op_nt_repack_split3(h.w1, head_in(D, h), h.m->l0.w, head_in(D, h), hw.pl_f0, s));
+      wplanes(p[i], hw.pl_f0);
     }
   }
+  p[3] = lin2(M1, D.dh, x.hB, Hd, Hd, x.zB, L, L, dec->up0.w, dec->up0.b, w.du1, D.dh);
+  if (tall) {
+    DR_TRY(op_nt_repack_split3(D.dh, Hd + L, dec->up0.w, Hd + L, w.pl_fup0, s));
+    wplanes(p[3], w.pl_fup0);
+    splitk_all(p, 4, w.sk, w.sk_n);
+  }
+  DR_TRY(gemm_launch(G_NT, AM_PLAIN, p, 4, s));
+  for (int i = 0; i < 3; ++i) {
+    const WmHead& h = x.head[i]; const HeadWs& hw = w.head[i];
+    p[i] = lin_ln(M1, h.w2, h.w1, hw.p1, h.w1, h.m->n1, h.m->l3.w, h.m->l3.b, hw.p2, h.w2);
+    p[i].a_out = hw.x1; p[i].ld_aout = h.w1;
+    if (tall) {
+      DR_TRY(op_nt_repack_split3(h.w2, h.w1, h.m->l3.w, h.w1, hw.pl_f3, s));
+      wplanes(p[i], hw.pl_f3);
+    }
+  }
+  DR_TRY(gemm_launch(G_NT, AM_LNSILU, p, 3, s));
+  for (int i = 0; i < 3; ++i) {
+    const WmHead& h = x.head[i]; const HeadWs& hw = w.head[i];
+    p[i] = lin_ln(M1, h.nout, h.w2, hw.p2, h.w2, h.m->n4, h.m->l6.w, h.m->l6.b, hw.lg, h.nout);
+    p[i].a_out = hw.x2; p[i].ld_aout = h.w2;
+    // (the prior's 1024 outputs; the reward's 255 / continue's 1 stay on the tile kernel: no pl_f6)
+    if (tall && hw.pl_f6) {
+      DR_TRY(op_nt_repack_split3(h.nout, h.w2, h.m->l6.w, h.w2, hw.pl_f6, s));
+      wplanes(p[i], hw.pl_f6);
+    }
+  }
+  return gemm_launch(G_NT, AM_LNSILU, p, 3, s);
+}
 
-  // ---- losses ----
-  {
-    const int W = pow2_ge(d->cols);
-    const long long th = (long long)M1 * R * W;
-    const float* post1 = w.plog + (long long)B * L;
-    hipLaunchKernelGGL(k_wm_kl<0>, dim3(blocks(th, 256)), dim3(256), 0, s, M1, R, d->cols, W, w.prior_lg, post1,
-                       w.cont_tm, w.scal, w.kl_grp, nullptr, nullptr);
-    DR_TRY(dr_check_launch("wm_kl"));
-    hipLaunchKernelGGL(k_wm_heads, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, nb, w.rew_lg, w.cont_lg, w.rew_tm,
-                       w.cont_tm, wm->buckets_rew, w.coef_row, w.rew_row, w.cont_row, w.g_rew, w.g_cont);
-    DR_TRY(dr_check_launch("wm_heads"));
-    hipLaunchKernelGGL(k_wm_stats, dim3(1), dim3(256), 0, s, M1, R, vec ? 1 : op_convT_mse_parts(IH / 2, IW / 2), w.obs_part,
-                       w.rew_row, w.cont_row, w.kl_grp, w.cont_tm, stats);
-    DR_TRY(dr_check_launch("wm_stats"));
-  }
-  if (hiddens_out) DR_TRY(copy2d(hiddens_out, Hd, w.h_all, Hd, Hd, M, s));
-  if (latents_out) DR_TRY(copy2d(latents_out, L, w.z_all, L, L, M, s));
-  if (post_logits_out) DR_TRY(copy2d(post_logits_out, L, w.plog, L, L, M, s));
-  }  // DR_WM_FWD
+// vector observations, image_builder stand-in: q = SiLU(du2) Wd1^T + bd1, mu = SiLU(q) Wd2^T + bd2; squared error
+// vs rows t >= 1
+static int wm_vec_decoder_fwd(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder* dec = x.dec;
+  const int M1 = D.M1, Dv = D.Dv;
+  const long long MF = (long long)M1 * D.Fd;
+  DR_TRY(silu(MF, w.du2, w.du2p, s));
+  DR_TRY(run(G_NT, AM_PLAIN, lin(M1, D.Fd, D.Fd, w.du2p, D.Fd, dec->convt[0].w, D.Fd, dec->convt[0].b, w.dq[0], D.Fd), s));
+  DR_TRY(silu(MF, w.dq[0], w.dqp[0], s));
+  DR_TRY(run(G_NT, AM_PLAIN, lin(M1, Dv, D.Fd, w.dqp[0], D.Fd, dec->convt[1].w, D.Fd, dec->convt[1].b, w.dq[1], Dv), s));
+  hipLaunchKernelGGL(k_vec_mse, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, Dv, w.dq[1], w.x0 + (long long)D.B * Dv,
+                     w.coef_obs, w.dgout, w.obs_part);
+  return dr_check_launch("vec_mse");
+}
 
-  const bool bwd_heads = (phases & (DR_WM_BWD | DR_WM_BWD_HEADS)) != 0;
-  const bool bwd_scan = (phases & (DR_WM_BWD | DR_WM_BWD_SCAN)) != 0;
-  const bool bwd_enc = (phases & (DR_WM_BWD | DR_WM_BWD_ENC)) != 0;
-  if (!(bwd_heads || bwd_scan || bwd_enc)) return DR_OK;
-  if (bwd_heads) {
-  {
-    const int W = pow2_ge(d->cols);
-    const long long th = (long long)M1 * R * W;
-    const float* post1 = w.plog + (long long)B * L;
-    hipLaunchKernelGGL(k_wm_final, dim3(1), dim3(64), 0, s, stats, rows_global, cfg, w.scal, losses, skip);
-    DR_TRY(dr_check_launch("wm_final"));
-    hipLaunchKernelGGL(k_wm_kl<1>, dim3(blocks(th, 256)), dim3(256), 0, s, M1, R, d->cols, W, w.prior_lg, post1,
-                       w.cont_tm, w.scal, nullptr, w.g_prior, w.gpost);
-    DR_TRY(dr_check_launch("wm_kl_bwd"));
-  }
+// convT k of the decoder over n frames: geometry, weights and bias (the caller sets the input and the outputs)
+static ConvTArgs dec_convt_args(const WmDims& D, int n, int k, const float* wq, const float* bias) {
+  ConvTArgs a = {};
+  a.n = n; a.cin = D.cd[k]; a.h = D.IH >> (D.N - k); a.w = D.IW >> (D.N - k); a.cout = D.cd[k + 1];
+  a.wq = wq; a.bias = bias;
+  return a;
+}
 
-  // ---- backward: heads (rows t >= 1) into dL/dh, dL/dz ----
-  DR_TRY(zero(w.gH, (long long)M * Hd, s));
-  DR_TRY(zero(w.gZ, (long long)M * L, s));
-  DR_TRY(head_bwd(D, wm->prior, gw->prior, D.ph1, D.ph2, L, w.g_prior, w.t_pl6, w.t_pl3, w.t_pl0, w.px1, w.px2, w.pp1,
-                  w.pp2, 0, hB, zB, gHB, gZB, w.bp, w.sk, w.sk_n, w.tn, w.tn_bytes, s, w.pl_h6, w.pl_h3[0],
-                  w.pl_h0[0]));
-  DR_TRY(head_bwd(D, wm->reward, gw->reward, D.rh1, D.rh2, nb, w.g_rew, w.t_rl6, w.t_rl3, w.t_rl0, w.rx1, w.rx2, w.rp1,
-                  w.rp2, 1, hB, zB, gHB, gZB, w.br, w.sk, w.sk_n, w.tn, w.tn_bytes, s, nullptr, w.pl_h3[1],
-                  w.pl_h0[1]));
-  DR_TRY(head_bwd(D, wm->cont, gw->cont, D.ch1, D.ch2, 1, w.g_cont, w.t_cl6, w.t_cl3, w.t_cl0, w.cx1, w.cx2, w.cp1,
-                  w.cp2, 1, hB, zB, gHB, gZB, w.bc, w.sk, w.sk_n, w.tn, w.tn_bytes, s, nullptr, w.pl_h3[2],
-                  w.pl_h0[2]));
-  // decoder: image_builder.6 .. .0 (data grads as strided convs, weight grads, bias sums)
-  if (vec) {
-    // image_builder stand-in backward: dgout = dL/dmu -> Wd2 / bd2 grads, dL/dq = (dgout Wd2) SiLU'(q)
-    // -> Wd1 / bd1 grads, dL/d du2 = (dL/dq Wd1) SiLU'(du2)  (NN products with the weights as stored)
-    const long long MF = (long long)M1 * D.Fd;
-    auto nn = [&](int N, int K, const float* A, const float* Wkn, float* Y) {
-      GemmArgs g = gemm_args();
-      g.M = M1; g.N = N; g.K = K; g.A = A; g.lda = K; g.W = Wkn; g.ldb = N; g.Y = Y; g.ldy = N;
-      return gemm_launch(G_NN, AM_PLAIN, &g, 1, s);
-    };
-    DR_TRY(nn(D.Fd, Dv, w.dgout, dec->convt[1].w, w.dgq[0]));
-    hipLaunchKernelGGL(k_mul_dsilu, dim3(blocks(MF, 256)), dim3(256), 0, s, MF, w.dgq[0], w.dq[0]);
-    DR_TRY(dr_check_launch("mul_dsilu"));
-    DR_TRY(nn(D.Fd, D.Fd, w.dgq[0], dec->convt[0].w, w.dgu2));
-    hipLaunchKernelGGL(k_mul_dsilu, dim3(blocks(MF, 256)), dim3(256), 0, s, MF, w.dgu2, w.du2);
-    DR_TRY(dr_check_launch("mul_dsilu"));
-    GemmArgs p[2];
-    p[0] = bwd_w(Dv, D.Fd, M1, w.dgout, Dv, w.dqp[0], D.Fd, gd->convt[1].w);
-    p[1] = bwd_w(D.Fd, D.Fd, M1, w.dgq[0], D.Fd, w.du2p, D.Fd, gd->convt[0].w);
-    splitk_all(p, 2, w.sk, w.sk_n);
-    DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
-    ColsumJob cj[2] = {{Dv, w.dgout, Dv, nullptr, 0, gd->convt[1].b}, {D.Fd, w.dgq[0], D.Fd, nullptr, 0, gd->convt[0].b}};
-    DR_TRY(op_colsum_multi(M1, cj, 2, s));
-  } else {
-    bool csum_next = false;  // gout of this layer was summed per tile by the layer above's input-gradient conv
-    for (int k = N - 1; k >= 0; --k) {
-      const int ih = IH >> (N - 1 - k), iw = IW >> (N - 1 - k);  // output (high-res) size of convT k
-      const int co = cout_t[k], co_st = dec_cout_st(D, k);
-      float* gin = k ? w.dgq[k - 1] : w.dgu2;              // dL/d(pre-activation) of convT k's input
-      const float* pre = k ? w.dq[k - 1] : w.du2;
-      // input of convT k after SiLU; the last layer's is recomputed from dq (not stored)
-      const bool post_silu = k == N - 1 && k > 0;
-      const float* post = post_silu ? w.dq[k - 1] : k ? w.dqp[k - 1] : w.du2p;
-      const float* gout = k < N - 1 ? w.dgq[k] : w.dgout;  // dL/d(convT k's output pre-activation)
-      // the f32 4-channel input-gradient conv of the last layer also sums its
-      // output per tile: the bias gradient of convT k - 1 without re-reading
-      // that 0.5 GB gradient (csum_next below)
-      const bool csum_here = !w.s3d[k] && k == N - 1 && k > 0;
-      if (w.s3d[k])
-        DR_TRY(op_conv_split3_ex(M1, co_st, ih, iw, cin_t[k], gout, w.s3d[k], nullptr, gin, 0, const_cast<float*>(pre),
-                                 CONV_EPI_DSILU, s, D.terms));
-      else
-        DR_TRY(op_conv_nhwc_ex(M1, co_st, ih, iw, cin_t[k], gout, w.wrd[k], nullptr, gin, 0, const_cast<float*>(pre),
-                               CONV_EPI_DSILU, s, csum_here ? w.csp : nullptr));
-      DR_TRY(wgrad(M1, ih / 2, iw / 2, cin_t[k], co_st, post, cin_t[k], gout, co_st, gd->convt[k].w, co, w.cws, w.cws_n,
-                   s, D.terms, post_silu ? 1 : 0));
-      // (the per-tile partials -- 1.5e4 / 2.9e4 rows -- go through the same
-      // two-pass channel sum: one workgroup per channel over them took 40-70 us)
-      if (k == N - 1 && co == 3)  // the tanh-MSE layer summed its gradient per tile (k_convT_out3)
-        DR_TRY(op_chan_sum((long long)M1 * op_convT_mse_parts(ih / 2, iw / 2), 3, w.obs_bpart, 3, gd->convt[k].b, 0,
-                           w.cws, w.cws_n, s));
-      else if (csum_next)
-        DR_TRY(op_chan_sum(((long long)M1 * ih * iw + 127) / 128, co, w.csp, co, gd->convt[k].b, 0, w.cws, w.cws_n, s));
-      else
-        DR_TRY(op_chan_sum((long long)M1 * ih * iw, co, gout, co_st, gd->convt[k].b, 0, w.cws, w.cws_n, s));
-      csum_next = csum_here;
+// decoder (VAE.py:139-161): upscaler.3 pre-activation in NHWC, SiLU applied by the consumers
+static int wm_fwd_decoder(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder* dec = x.dec;
+  const int M1 = D.M1, N = D.N;
+  GemmArgs g = lin_ln(M1, D.Fd, D.dh, w.du1, D.dh, dec->up1, w.w3p, w.b3p, w.du2, D.Fd);
+  g.a_out = w.dx1; g.ld_aout = D.dh;
+  if (M1 >= 1024 && !D.Dv) {
+    DR_TRY(op_nt_repack_split3(D.Fd, D.dh, w.w3p, D.dh, w.pl_fup3, s));
+    wplanes(g, w.pl_fup3);
+  }
+  DR_TRY(run(G_NT, AM_LNSILU, g, s));
+  if (D.Dv) return wm_vec_decoder_fwd(x);
+  DR_TRY(silu((long long)M1 * D.Fd, w.du2, w.du2p, s));
+  for (int k = 0; k < N; ++k) {
+    ConvTArgs a = dec_convt_args(D, M1, k, w.wqd[k], dec->convt[k].b);
+    a.in = k ? w.dqp[k - 1] : w.du2p;
+    if (k == N - 1 && k > 0) {  // SiLU of the pre-activations on load (dqp[N - 2] is not stored)
+      a.in = w.dq[k - 1];
+      a.silu_in = 1;
+    }
+    if (k < N - 1) {
+      a.out = w.dq[k]; a.out2 = w.dqp[k]; a.ldc = x.cout_t[k];
+      if (w.t3d[k]) DR_TRY(op_convT_split3(CT_EPI_BIAS, a, w.t3d[k], s, D.terms));
+      else DR_TRY(op_convT_nhwc(CT_EPI_BIAS, a, s));
+    } else {
+      // Tanh + squared error against frames t >= 1 (WorldModel.py:129); writes dL/d(pre-tanh)
+      a.out = w.dgout; a.ldc = 4;
+      a.target = w.x0 + (long long)D.B * D.pix[0] * 4; a.tstride = 4;
+      a.coef = w.coef_obs; a.part = w.obs_part; a.bpart = w.obs_bpart;
+      DR_TRY(op_convT_nhwc(CT_EPI_TANH_MSE, a, s));
     }
   }
-  // decoder.upscaler: .3 (permuted rows) then LN-SiLU(.1) and .0 into dL/d[h | z]
-  {
-    GemmArgs g = bwd_nt(M1, D.dh, D.Fd, w.dgu2, D.Fd, w.t_up3, w.gxu, D.dh, 0);
-    splitk_all(&g, 1, w.sk, w.sk_n);
-    if (M1 >= 1024) {
-      DR_TRY(op_nt_repack_split3(D.dh, D.Fd, w.t_up3, D.Fd, w.pl_up3, s));
-      DR_TRY(op_nt_repack_split3(Hd + L, D.dh, w.t_up0, D.dh, w.pl_up0, s));
-      wplanes(g, w.pl_up3);
-    }
-    DR_TRY(run(G_NT, AM_PLAIN, g, s));
-  }
-  DR_TRY(lnbwd_nt(M1, Hd + L, D.dh, w.gxu, D.dh, w.du1, D.dh, dec->up1, w.t_up0, gHB, Hd, 1, w.gpu, D.dh, w.gyu, w.xhu,
-                  gZB, L, Hd, s, nullptr, M1 >= 1024 ? w.pl_up0 : nullptr, w.sk, w.sk_n));
-  {
-    GemmArgs p[2];
-    p[0] = bwd_w(D.Fd, D.dh, M1, w.dgu2, D.Fd, w.dx1, D.dh, w.dw3p);
-    p[1] = bwd_w(D.dh, Hd + L, M1, w.gpu, D.dh, hB, Hd, gd->up0.w);
-    p[1].W2 = zB; p[1].ldb2 = L; p[1].nsplitB = Hd;
-    splitk_all(p, 2, w.sk, w.sk_n);
-    DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
-    ColsumJob cj[4] = {
-        {D.Fd, w.dgu2, D.Fd, nullptr, 0, w.db3p},
-        {D.dh, w.gpu, D.dh, nullptr, 0, gd->up0.b},
-        {D.dh, w.gyu, D.dh, w.xhu, D.dh, gd->up1.w},
-        {D.dh, w.gyu, D.dh, nullptr, 0, gd->up1.b},
-    };
-    DR_TRY(op_colsum_multi(M1, cj, 4, s));
-    DR_TRY(perm_rows(D.C0, D.Pf, D.dh, w.dw3p, gd->up3.w, 0, s));
-    DR_TRY(perm_rows(D.C0, D.Pf, 1, w.db3p, gd->up3.b, 0, s));
-  }
-  }  // bwd_heads
+  return DR_OK;
+}
 
-  if (bwd_scan) {
-  // ---- backward through the posterior scan, t = T-1 .. 0 ----
-  const int Wc = pow2_ge(d->cols);
+// ---- losses ----
+static int wm_fwd_losses(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_dims* d = x.d;
+  const int M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, R = d->rows;
+  hipLaunchKernelGGL(k_wm_kl<0>, dim3(blocks((long long)M1 * R * x.Wc, 256)), dim3(256), 0, s, M1, R, d->cols, x.Wc,
+                     w.head[0].lg, x.post1, w.cont_tm, w.scal, w.kl_grp, nullptr, nullptr);
+  DR_TRY(dr_check_launch("wm_kl"));
+  hipLaunchKernelGGL(k_wm_heads, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, D.nb, w.head[1].lg, w.head[2].lg, w.rew_tm,
+                     w.cont_tm, x.wm->buckets_rew, w.coef_row, w.rew_row, w.cont_row, w.head[1].g, w.head[2].g);
+  DR_TRY(dr_check_launch("wm_heads"));
+  hipLaunchKernelGGL(k_wm_stats, dim3(1), dim3(256), 0, s, M1, R, D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2),
+                     w.obs_part, w.rew_row, w.cont_row, w.kl_grp, w.cont_tm, x.stats);
+  DR_TRY(dr_check_launch("wm_stats"));
+  if (x.hiddens_out) DR_TRY(copy2d(x.hiddens_out, Hd, w.h_all, Hd, Hd, M, s));
+  if (x.latents_out) DR_TRY(copy2d(x.latents_out, L, w.z_all, L, L, M, s));
+  if (x.post_logits_out) DR_TRY(copy2d(x.post_logits_out, L, w.plog, L, L, M, s));
+  return DR_OK;
+}
+
+// input-gradient + weight-gradient pass of one head MLP (Linear-LN-SiLU x2 +
+// Linear) over M1 rows whose input is [h | z] (in_z = 0: h only).  Adds the
+// input gradient into gH/gZ rows t >= 1.
+static int head_bwd(const WmCtx& x, int i) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const WmHead& h = x.head[i]; const HeadWs& hw = w.head[i]; const MlpBwd& b = hw.b;
+  const dr_mlp3 &m = *h.m, &g = *h.g;
+  const int w1 = h.w1, w2 = h.w2, nout = h.nout, in_z = h.in_z, n0 = head_in(D, h);
+  const int M1 = D.M1, Hd = D.Hd, L = D.L;
+  // tall (>= 1024 rows): the input-gradient products on split3 planes of the
+  // transposed weights, split here (the weights change every step)
+  const bool tall = M1 >= 1024;
+  void* pl6 = tall && nout % 4 == 0 ? hw.pl_h6 : nullptr;
+  void* pl3 = tall ? hw.pl_h3 : nullptr;
+  void* pl0 = tall ? hw.pl_h0 : nullptr;
+  if (pl6) DR_TRY(op_nt_repack_split3(w2, nout, hw.t6, nout, pl6, s));
+  if (pl3) DR_TRY(op_nt_repack_split3(w1, w2, hw.t3, w2, pl3, s));
+  if (pl0) DR_TRY(op_nt_repack_split3(n0, w1, hw.t0, w1, pl0, s));
+  {
+    GemmArgs g6 = bwd_nt(M1, w2, nout, hw.g, nout, hw.t6, b.gx2, w2, 0);
+    wplanes(g6, pl6);
+    DR_TRY(run(G_NT, AM_PLAIN, g6, s));
+  }
+  DR_TRY(lnbwd_nt(M1, w1, w2, b.gx2, w2, hw.p2, w2, m.n4, hw.t3, b.gx1, w1, 0, b.gp2, w2, b.gy2, b.xh2, nullptr, 0,
+                  INT_MAX, s, nullptr, pl3, w.sk, w.sk_n));
+  DR_TRY(lnbwd_nt(M1, n0, w1, b.gx1, w1, hw.p1, w1, m.n1, hw.t0, x.gHB, Hd, 1, b.gp1, w1, b.gy1, b.xh1,
+                  in_z ? x.gZB : nullptr, L, in_z ? Hd : INT_MAX, s, nullptr, pl0, w.sk, w.sk_n));
+  GemmArgs p[3];
+  p[0] = bwd_w(nout, w2, M1, hw.g, nout, hw.x2, w2, g.l6.w);
+  p[1] = bwd_w(w2, w1, M1, b.gp2, w2, hw.x1, w1, g.l3.w);
+  p[2] = bwd_w(w1, n0, M1, b.gp1, w1, x.hB, Hd, g.l0.w);
+  if (in_z) {
+    p[2].W2 = x.zB; p[2].ldb2 = L; p[2].nsplitB = Hd;
+  }
+  splitk_all(p, 3, w.sk, w.sk_n);
+  DR_TRY(tn_launch(p, 3, w.tn, w.tn_bytes, s, D.terms));
+  ColsumJob cj[7] = {
+      {nout, hw.g, nout, nullptr, 0, g.l6.b}, {w2, b.gp2, w2, nullptr, 0, g.l3.b},
+      {w2, b.gy2, w2, b.xh2, w2, g.n4.w},     {w2, b.gy2, w2, nullptr, 0, g.n4.b},
+      {w1, b.gp1, w1, nullptr, 0, g.l0.b},    {w1, b.gy1, w1, b.xh1, w1, g.n1.w},
+      {w1, b.gy1, w1, nullptr, 0, g.n1.b},
+  };
+  return op_colsum_multi(M1, cj, 7, s);
+}
+
+// vector observations, image_builder stand-in backward: dgout = dL/dmu -> Wd2 / bd2 grads, dL/dq = (dgout Wd2) SiLU'(q)
+// -> Wd1 / bd1 grads, dL/d du2 = (dL/dq Wd1) SiLU'(du2)  (NN products with the weights as stored)
+static int wm_vec_decoder_bwd(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder *dec = x.dec, *gd = x.gd;
+  const int M1 = D.M1, Dv = D.Dv;
+  const long long MF = (long long)M1 * D.Fd;
+  DR_TRY(nn_product(M1, D.Fd, Dv, w.dgout, dec->convt[1].w, w.dgq[0], s));
+  DR_TRY(mul_dsilu(MF, w.dgq[0], w.dq[0], s));
+  DR_TRY(nn_product(M1, D.Fd, D.Fd, w.dgq[0], dec->convt[0].w, w.dgu2, s));
+  DR_TRY(mul_dsilu(MF, w.dgu2, w.du2, s));
+  GemmArgs p[2];
+  p[0] = bwd_w(Dv, D.Fd, M1, w.dgout, Dv, w.dqp[0], D.Fd, gd->convt[1].w);
+  p[1] = bwd_w(D.Fd, D.Fd, M1, w.dgq[0], D.Fd, w.du2p, D.Fd, gd->convt[0].w);
+  splitk_all(p, 2, w.sk, w.sk_n);
+  DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
+  ColsumJob cj[2] = {{Dv, w.dgout, Dv, nullptr, 0, gd->convt[1].b}, {D.Fd, w.dgq[0], D.Fd, nullptr, 0, gd->convt[0].b}};
+  return op_colsum_multi(M1, cj, 2, s);
+}
+
+// decoder: image_builder.6 .. .0 (data grads as strided convs, weight grads, bias sums)
+static int wm_bwd_decoder(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder* gd = x.gd;
+  const int *cin_t = x.cin_t, *cout_t = x.cout_t;
+  const int M1 = D.M1, IH = D.IH, IW = D.IW, N = D.N;
+  if (D.Dv) return wm_vec_decoder_bwd(x);
+  bool csum_next = false;  // gout of this layer was summed per tile by the layer above's input-gradient conv
+  for (int k = N - 1; k >= 0; --k) {
+    const int ih = IH >> (N - 1 - k), iw = IW >> (N - 1 - k);  // output (high-res) size of convT k
+    const int co = cout_t[k], co_st = dec_cout_st(D, k);
+    float* gin = k ? w.dgq[k - 1] : w.dgu2;              // dL/d(pre-activation) of convT k's input
+    const float* pre = k ? w.dq[k - 1] : w.du2;
+    // input of convT k after SiLU; the last layer's is recomputed from dq (not stored)
+    const bool post_silu = k == N - 1 && k > 0;
+    const float* post = post_silu ? w.dq[k - 1] : k ? w.dqp[k - 1] : w.du2p;
+    const float* gout = k < N - 1 ? w.dgq[k] : w.dgout;  // dL/d(convT k's output pre-activation)
+    // the f32 4-channel input-gradient conv of the last layer also sums its
+    // output per tile: the bias gradient of convT k - 1 without re-reading
+    // that 0.5 GB gradient (csum_next below)
+    const bool csum_here = !w.s3d[k] && k == N - 1 && k > 0;
+    if (w.s3d[k])
+      DR_TRY(op_conv_split3_ex(M1, co_st, ih, iw, cin_t[k], gout, w.s3d[k], nullptr, gin, 0, const_cast<float*>(pre),
+                               CONV_EPI_DSILU, s, D.terms));
+    else
+      DR_TRY(op_conv_nhwc_ex(M1, co_st, ih, iw, cin_t[k], gout, w.wrd[k], nullptr, gin, 0, const_cast<float*>(pre),
+                             CONV_EPI_DSILU, s, csum_here ? w.csp : nullptr));
+    DR_TRY(wgrad(M1, ih / 2, iw / 2, cin_t[k], co_st, post, cin_t[k], gout, co_st, gd->convt[k].w, co, w.cws, w.cws_n,
+                 s, D.terms, post_silu ? 1 : 0));
+    // (the per-tile partials -- 1.5e4 / 2.9e4 rows -- go through the same
+    // two-pass channel sum: one workgroup per channel over them took 40-70 us)
+    if (k == N - 1 && co == 3)  // the tanh-MSE layer summed its gradient per tile (k_convT_out3)
+      DR_TRY(op_chan_sum((long long)M1 * op_convT_mse_parts(ih / 2, iw / 2), 3, w.obs_bpart, 3, gd->convt[k].b, 0,
+                         w.cws, w.cws_n, s));
+    else if (csum_next)
+      DR_TRY(op_chan_sum(((long long)M1 * ih * iw + 127) / 128, co, w.csp, co, gd->convt[k].b, 0, w.cws, w.cws_n, s));
+    else
+      DR_TRY(op_chan_sum((long long)M1 * ih * iw, co, gout, co_st, gd->convt[k].b, 0, w.cws, w.cws_n, s));
+    csum_next = csum_here;
+  }
+  return DR_OK;
+}
+
+// decoder.upscaler: .3 (permuted rows) then LN-SiLU(.1) and .0 into dL/d[h | z]
+static int wm_bwd_upscaler(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_decoder* gd = x.gd;
+  const int M1 = D.M1, L = D.L, Hd = D.Hd;
+  GemmArgs g = bwd_nt(M1, D.dh, D.Fd, w.dgu2, D.Fd, w.t_up3, w.gxu, D.dh, 0);
+  splitk_all(&g, 1, w.sk, w.sk_n);
+  if (M1 >= 1024) {
+    DR_TRY(op_nt_repack_split3(D.dh, D.Fd, w.t_up3, D.Fd, w.pl_up3, s));
+    DR_TRY(op_nt_repack_split3(Hd + L, D.dh, w.t_up0, D.dh, w.pl_up0, s));
+    wplanes(g, w.pl_up3);
+  }
+  DR_TRY(run(G_NT, AM_PLAIN, g, s));
+  DR_TRY(lnbwd_nt(M1, Hd + L, D.dh, w.gxu, D.dh, w.du1, D.dh, x.dec->up1, w.t_up0, x.gHB, Hd, 1, w.gpu, D.dh, w.gyu,
+                  w.xhu, x.gZB, L, Hd, s, nullptr, M1 >= 1024 ? w.pl_up0 : nullptr, w.sk, w.sk_n));
+  GemmArgs p[2];
+  p[0] = bwd_w(D.Fd, D.dh, M1, w.dgu2, D.Fd, w.dx1, D.dh, w.dw3p);
+  p[1] = bwd_w(D.dh, Hd + L, M1, w.gpu, D.dh, x.hB, Hd, gd->up0.w);
+  p[1].W2 = x.zB; p[1].ldb2 = L; p[1].nsplitB = Hd;
+  splitk_all(p, 2, w.sk, w.sk_n);
+  DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
+  ColsumJob cj[4] = {
+      {D.Fd, w.dgu2, D.Fd, nullptr, 0, w.db3p},
+      {D.dh, w.gpu, D.dh, nullptr, 0, gd->up0.b},
+      {D.dh, w.gyu, D.dh, w.xhu, D.dh, gd->up1.w},
+      {D.dh, w.gyu, D.dh, nullptr, 0, gd->up1.b},
+  };
+  DR_TRY(op_colsum_multi(M1, cj, 4, s));
+  DR_TRY(perm_rows(D.C0, D.Pf, D.dh, w.dw3p, gd->up3.w, 0, s));
+  return perm_rows(D.C0, D.Pf, 1, w.db3p, gd->up3.b, 0, s);
+}
+
+// ---- backward: losses, then the heads, decoder and upscaler (rows t >= 1) into dL/dh, dL/dz ----
+static int wm_bwd_heads(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_dims* d = x.d;
+  const int M1 = D.M1, R = d->rows;
+  hipLaunchKernelGGL(k_wm_final, dim3(1), dim3(64), 0, s, x.stats, x.rows_global, x.cfg, w.scal, x.losses, x.skip);
+  DR_TRY(dr_check_launch("wm_final"));
+  hipLaunchKernelGGL(k_wm_kl<1>, dim3(blocks((long long)M1 * R * x.Wc, 256)), dim3(256), 0, s, M1, R, d->cols, x.Wc,
+                     w.head[0].lg, x.post1, w.cont_tm, w.scal, nullptr, w.head[0].g, w.gpost);
+  DR_TRY(dr_check_launch("wm_kl_bwd"));
+  DR_TRY(zero(w.gH, (long long)D.M * D.Hd, s));
+  DR_TRY(zero(w.gZ, (long long)D.M * D.L, s));
+  for (int i = 0; i < 3; ++i) DR_TRY(head_bwd(x, i));
+  DR_TRY(wm_bwd_decoder(x));
+  return wm_bwd_upscaler(x);
+}
+
+// ---- backward through the posterior scan, t = T-1 .. 0 ----
+static int wm_bwd_scan(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_dims* d = x.d; const dr_world_model *wm = x.wm, *gw = x.gw;
+  const int B = D.B, T = D.T, M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, F = D.F, N = D.N;
+  const int R = d->rows, Wc = x.Wc;
   // B >= 128: the per-step input-gradient products (K = 3 Hd) on the split3
   // wave-K kernel from weight planes split once per step (the f32 wave-K
   // kernel took 30.7 us per grouped launch at B = 256)
@@ -1099,80 +1150,139 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
     }
   }
   // scan weight gradients over all rows
-  {
-    GemmArgs p[4];
-    p[0] = bwd_w(L, eh, M, w.glog, L, w.x_m, eh, gw->map3.w);
-    p[1] = bwd_w(eh, F + Hd, M, w.gpre_m, eh, w.a[N - 1], F, gw->map0.w);
-    p[1].W2 = w.h_all; p[1].ldb2 = Hd; p[1].nsplitB = F;
-    p[2] = bwd_w(3 * Hd, L + A, M1, w.ggi + (long long)B * 3 * Hd, 3 * Hd, w.z_all, L, gw->w_ih);
-    p[2].W2 = w.act_tm; p[2].ldb2 = A; p[2].nsplitB = L;
-    p[3] = bwd_w(3 * Hd, Hd, M1, w.ggh + (long long)B * 3 * Hd, 3 * Hd, w.h_all, Hd, gw->w_hh);
-    splitk_all(p, 4, w.sk, w.sk_n);
-    DR_TRY(tn_launch(p, 4, w.tn, w.tn_bytes, s, D.terms));
-    ColsumJob cj[6] = {
-        {L, w.glog, L, nullptr, 0, gw->map3.b},       {eh, w.gpre_m, eh, nullptr, 0, gw->map0.b},
-        {eh, w.gy_m, eh, w.xh_m, eh, gw->map1.w},     {eh, w.gy_m, eh, nullptr, 0, gw->map1.b},
-        {3 * Hd, w.ggi, 3 * Hd, nullptr, 0, gw->b_ih}, {3 * Hd, w.ggh, 3 * Hd, nullptr, 0, gw->b_hh},
-    };
-    DR_TRY(op_colsum_multi(M, cj, 6, s));
-  }
-  }  // bwd_scan
+  GemmArgs p[4];
+  p[0] = bwd_w(L, eh, M, w.glog, L, w.x_m, eh, gw->map3.w);
+  p[1] = bwd_w(eh, F + Hd, M, w.gpre_m, eh, w.a[N - 1], F, gw->map0.w);
+  p[1].W2 = w.h_all; p[1].ldb2 = Hd; p[1].nsplitB = F;
+  p[2] = bwd_w(3 * Hd, L + A, M1, w.ggi + (long long)B * 3 * Hd, 3 * Hd, w.z_all, L, gw->w_ih);
+  p[2].W2 = w.act_tm; p[2].ldb2 = A; p[2].nsplitB = L;
+  p[3] = bwd_w(3 * Hd, Hd, M1, w.ggh + (long long)B * 3 * Hd, 3 * Hd, w.h_all, Hd, gw->w_hh);
+  splitk_all(p, 4, w.sk, w.sk_n);
+  DR_TRY(tn_launch(p, 4, w.tn, w.tn_bytes, s, D.terms));
+  ColsumJob cj[6] = {
+      {L, w.glog, L, nullptr, 0, gw->map3.b},       {eh, w.gpre_m, eh, nullptr, 0, gw->map0.b},
+      {eh, w.gy_m, eh, w.xh_m, eh, gw->map1.w},     {eh, w.gy_m, eh, nullptr, 0, gw->map1.b},
+      {3 * Hd, w.ggi, 3 * Hd, nullptr, 0, gw->b_ih}, {3 * Hd, w.ggh, 3 * Hd, nullptr, 0, gw->b_hh},
+  };
+  return op_colsum_multi(M, cj, 6, s);
+}
 
-  if (bwd_enc) {
-  // ---- backward through the encoder convolutions (all M frames) ----
+// vector observations, encoder stand-in backward: W2 / b2 grads from gL = dL/d pre[N-1], dL/d pre[0] = (gL W2)
+// SiLU'(pre[0]), W1 / b1 grads
+static int wm_vec_encoder_bwd(const WmCtx& x, const float* gL) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_world_model* gw = x.gw;
+  const int M = D.M, F = D.F, Dv = D.Dv;
+  DR_TRY(nn_product(M, F, F, gL, x.wm->conv[1].w, w.gp[0], s));
+  DR_TRY(mul_dsilu((long long)M * F, w.gp[0], w.pre[0], s));
+  GemmArgs p[2];
+  p[0] = bwd_w(F, F, M, gL, F, w.a[0], F, gw->conv[1].w);
+  p[1] = bwd_w(F, Dv, M, w.gp[0], F, w.x0, Dv, gw->conv[0].w);
+  splitk_all(p, 2, w.sk, w.sk_n);
+  DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
+  ColsumJob cj[2] = {{F, gL, F, nullptr, 0, gw->conv[1].b}, {F, w.gp[0], F, nullptr, 0, gw->conv[0].b}};
+  return op_colsum_multi(M, cj, 2, s);
+}
+
+// ---- backward through the encoder convolutions (all M frames) ----
+static int wm_bwd_encoder(const WmCtx& x) {
+  const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
+  const dr_world_model* gw = x.gw;
+  const int M = D.M, eh = D.eh, F = D.F, IH = D.IH, IW = D.IW, N = D.N;
   float* gL = w.gp[N - 1];  // dL/d pre[N-1], NHWC (w0tp's rows are permuted to NHWC)
-  {
-    GemmArgs g = bwd_nt(M, F, eh, w.gpre_m, eh, w.w0tp, gL, F, 0);
-    if (M >= 1024) {
-      DR_TRY(op_nt_repack_split3(F, eh, w.w0tp, eh, w.pl_w0tp, s));
-      wplanes(g, w.pl_w0tp);
-    }
-    DR_TRY(run(G_NT, AM_PLAIN, g, s));
+  GemmArgs g = bwd_nt(M, F, eh, w.gpre_m, eh, w.w0tp, gL, F, 0);
+  if (M >= 1024) {
+    DR_TRY(op_nt_repack_split3(F, eh, w.w0tp, eh, w.pl_w0tp, s));
+    wplanes(g, w.pl_w0tp);
   }
-  hipLaunchKernelGGL(k_mul_dsilu, dim3(blocks((long long)M * F, 256)), dim3(256), 0, s, (long long)M * F, gL,
-                     w.pre[N - 1]);
-  DR_TRY(dr_check_launch("mul_dsilu"));
-  if (vec) {
-    // MLP stand-in backward: W2 / b2 grads from dL/d pre[N-1], dL/d pre[0] = (gL W2) SiLU'(pre[0]), W1 / b1 grads
-    GemmArgs g = gemm_args();
-    g.M = M; g.N = F; g.K = F; g.A = gL; g.lda = F; g.W = wm->conv[1].w; g.ldb = F; g.Y = w.gp[0]; g.ldy = F;
-    DR_TRY(gemm_launch(G_NN, AM_PLAIN, &g, 1, s));
-    hipLaunchKernelGGL(k_mul_dsilu, dim3(blocks((long long)M * F, 256)), dim3(256), 0, s, (long long)M * F, w.gp[0],
-                       w.pre[0]);
-    DR_TRY(dr_check_launch("mul_dsilu"));
-    GemmArgs p[2];
-    p[0] = bwd_w(F, F, M, gL, F, w.a[0], F, gw->conv[1].w);
-    p[1] = bwd_w(F, Dv, M, w.gp[0], F, w.x0, Dv, gw->conv[0].w);
-    splitk_all(p, 2, w.sk, w.sk_n);
-    DR_TRY(tn_launch(p, 2, w.tn, w.tn_bytes, s, D.terms));
-    ColsumJob cj[2] = {{F, gL, F, nullptr, 0, gw->conv[1].b}, {F, w.gp[0], F, nullptr, 0, gw->conv[0].b}};
-    DR_TRY(op_colsum_multi(M, cj, 2, s));
-  } else {
-    for (int k = N - 1; k >= 0; --k) {
-      const int oh = IH >> (k + 1), ow = IW >> (k + 1);
-      const int cin = enc_cin_st(D, k), cout = D.e[k + 1];
-      const float* hi = k ? w.a[k - 1] : w.x0;  // conv k's input
-      if (k == 0 && cin > D.e[0]) {
-        // conv1: x0's pad channel holds 1, so the weight-gradient product's
-        // pad column is the bias gradient -- the 0.5 GB gradient gp[0] is not
-        // re-read by a channel-sum pass (op_conv_wgrad bias_out)
-        DR_TRY(op_conv_wgrad(M, oh, ow, cout, cin, w.gp[0], cout, 0, hi, cin, gw->conv[0].w, D.e[0], 1.0f, 0, w.cws,
-                             w.cws_n, s, gw->conv[0].b));
-        continue;
-      }
-      DR_TRY(wgrad(M, oh, ow, cout, cin, w.gp[k], cout, hi, cin, gw->conv[k].w, D.e[k], w.cws, w.cws_n, s, D.terms));
-      DR_TRY(op_chan_sum((long long)M * oh * ow, cout, w.gp[k], cout, gw->conv[k].b, 0, w.cws, w.cws_n, s));
-      if (k > 0) {
-        ConvTArgs a = {};
-        a.n = M; a.cin = cout; a.h = oh; a.w = ow; a.cout = cin;
-        a.in = w.gp[k]; a.wq = w.wqe[k]; a.out = w.gp[k - 1]; a.ldc = cin; a.pre = w.pre[k - 1];
-        if (w.t3e[k]) DR_TRY(op_convT_split3(CT_EPI_DSILU, a, w.t3e[k], s, D.terms));
-        else DR_TRY(op_convT_nhwc(CT_EPI_DSILU, a, s));
-      }
+  DR_TRY(run(G_NT, AM_PLAIN, g, s));
+  DR_TRY(mul_dsilu((long long)M * F, gL, w.pre[N - 1], s));
+  if (D.Dv) return wm_vec_encoder_bwd(x, gL);
+  for (int k = N - 1; k >= 0; --k) {
+    const int oh = IH >> (k + 1), ow = IW >> (k + 1);
+    const int cin = enc_cin_st(D, k), cout = D.e[k + 1];
+    const float* hi = k ? w.a[k - 1] : w.x0;  // conv k's input
+    if (k == 0 && cin > D.e[0]) {
+      // conv1: x0's pad channel holds 1, so the weight-gradient product's
+      // pad column is the bias gradient -- the 0.5 GB gradient gp[0] is not
+      // re-read by a channel-sum pass (op_conv_wgrad bias_out)
+      DR_TRY(op_conv_wgrad(M, oh, ow, cout, cin, w.gp[0], cout, 0, hi, cin, gw->conv[0].w, D.e[0], 1.0f, 0, w.cws,
+                           w.cws_n, s, gw->conv[0].b));
+      continue;
+    }
+    DR_TRY(wgrad(M, oh, ow, cout, cin, w.gp[k], cout, hi, cin, gw->conv[k].w, D.e[k], w.cws, w.cws_n, s, D.terms));
+    DR_TRY(op_chan_sum((long long)M * oh * ow, cout, w.gp[k], cout, gw->conv[k].b, 0, w.cws, w.cws_n, s));
+    if (k > 0) {
+      ConvTArgs a = {};
+      a.n = M; a.cin = cout; a.h = oh; a.w = ow; a.cout = cin;
+      a.in = w.gp[k]; a.wq = w.wqe[k]; a.out = w.gp[k - 1]; a.ldc = cin; a.pre = w.pre[k - 1];
+      if (w.t3e[k]) DR_TRY(op_convT_split3(CT_EPI_DSILU, a, w.t3e[k], s, D.terms));
+      else DR_TRY(op_convT_nhwc(CT_EPI_DSILU, a, s));
     }
   }
-  }  // bwd_enc
+  return DR_OK;
+}
 
+static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const dr_decoder* dec, int B, int T,
+                  const dr_frames* src, const dr_wm_batch* bt, dr_noise noise, dr_wm_loss_cfg cfg, float* stats,
+                  int rows_global, float* losses, int* skip, const dr_world_model* gw, const dr_decoder* gd,
+                  float* hiddens_out, float* latents_out, float* post_logits_out, void* ws, size_t ws_bytes,
+                  hipStream_t s) {
+  DR_REQUIRE(d && wm && dec && src && bt && losses && gw && gd && stats && B > 0 && T >= 2, "null argument or T < 2");
+  DR_REQUIRE(bt->actions && bt->rewards && bt->continues, "window actions / rewards / continues required");
+  DR_TRY(dims_envelope("dr_wm_train", d, ENV_GRU | ENV_SAMPLER | ENV_ENCODER | ENV_DECODER));
+  DR_REQUIRE(vae_depth_ok(d), "enc_depth must be 0, 4 or 5");
+  DR_REQUIRE(d->obs_dim > 0 || (d->img_h % (1 << vae_depth(d)) == 0 && d->img_w % (1 << vae_depth(d)) == 0),
+             "image size must be a multiple of 2^depth (16, or 32 for the 5-layer VAE)");
+  DR_REQUIRE(d->enc_f1 % 8 == 0 && d->enc_f2 % 8 == 0 && d->dec_f1 % 8 == 0 && d->dec_f2 % 8 == 0,
+             "encoder / decoder filter counts must be multiples of 8");
+  DR_REQUIRE(d->cols <= 64, "latent classes must be <= 64");
+  DR_REQUIRE(d->obs_dim == 0 || d->obs_dim % 4 == 0, "vector observations: obs_dim % 4 == 0 required");
+  // the NT products that take the tile route stay f32 in both modes (on the
+  // bf16 tile GEMM in bf16 mode they saved 0.1 ms but raised the posterior
+  // flips 1.7e-4 -> 1.7e-3, r04p)
+  GemmBf16Scope bf16_scope(false);
+  WmCtx x;
+  x.d = d; x.wm = wm; x.gw = gw; x.dec = dec; x.gd = gd;
+  x.D = wm_dims(d, B, T);
+  const WmDims& D = x.D;
+  WmWs& w = x.w;
+  Carve c(ws);
+  wm_carve(c, d, D, w);
+  WS_CHECK(c, ws_bytes);
+  if (D.terms == 3) {  // the biases of the layers routed to the six-product kernels (forward and backward)
+    for (int k = 0; k < D.N; ++k) {
+      if (w.s3e[k]) DR_TRY(conv_bias_aligned(__func__, "conv", k, wm->conv[k].b));
+      if (w.t3d[k]) DR_TRY(conv_bias_aligned(__func__, "convt", k, dec->convt[k].b));
+    }
+  }
+  wm_heads(D, wm, gw, x.head);
+  x.src = src; x.bt = bt; x.noise = noise; x.cfg = cfg; x.stats = stats;
+  x.rows_global = rows_global > 0 ? rows_global : D.M1;
+  x.losses = losses; x.skip = skip;
+  x.hiddens_out = hiddens_out; x.latents_out = latents_out; x.post_logits_out = post_logits_out;
+  x.s = s;
+  x.hB = w.h_all + (long long)B * D.Hd; x.zB = w.z_all + (long long)B * D.L;
+  x.gHB = w.gH + (long long)B * D.Hd; x.gZB = w.gZ + (long long)B * D.L;
+  x.cin_t = D.cd; x.cout_t = D.cd + 1;
+  x.Wc = pow2_ge(d->cols);
+  x.post1 = w.plog + (long long)B * D.L;
+
+  if (phases & DR_WM_PREP) DR_TRY(wm_prep(x));
+  if (phases & DR_WM_FWD) {
+    DR_TRY(wm_fwd_encoder(x));
+    DR_TRY(wm_fwd_scan(x));
+    DR_TRY(wm_fwd_heads(x));
+    DR_TRY(wm_fwd_decoder(x));
+    DR_TRY(wm_fwd_losses(x));
+  }
+  const bool bwd_heads = (phases & (DR_WM_BWD | DR_WM_BWD_HEADS)) != 0;
+  const bool bwd_scan = (phases & (DR_WM_BWD | DR_WM_BWD_SCAN)) != 0;
+  const bool bwd_enc = (phases & (DR_WM_BWD | DR_WM_BWD_ENC)) != 0;
+  if (!(bwd_heads || bwd_scan || bwd_enc)) return DR_OK;
+  if (bwd_heads) DR_TRY(wm_bwd_heads(x));
+  if (bwd_scan) DR_TRY(wm_bwd_scan(x));
+  if (bwd_enc) DR_TRY(wm_bwd_encoder(x));
   return DR_OK;
 }
 
@@ -1268,9 +1378,8 @@ extern "C" int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, co
     DR_TRY(run(G_NT, AM_LNSILU, g, s));
   }
   for (int k = 0; k < N; ++k) {
-    ConvTArgs a = {};
-    a.n = M; a.cin = cin_t[k]; a.h = D.IH >> (N - k); a.w = D.IW >> (N - k); a.cout = cout_t[k];
-    a.in = k ? w.q[k - 1] : w.u2; a.silu_in = 0; a.wq = w.wq[k]; a.bias = dec->convt[k].b;
+    ConvTArgs a = dec_convt_args(D, M, k, w.wq[k], dec->convt[k].b);
+    a.in = k ? w.q[k - 1] : w.u2;
     if (k < N - 1) {
       a.out = w.q[k]; a.silu_out = 1; a.ldc = cout_t[k];
       DR_TRY(op_convT_nhwc(CT_EPI_BIAS, a, s));

@@ -167,6 +167,85 @@ def test_wm_step_deterministic(gpu):
         assert torch.equal(p1.grad, p2.grad), n
 
 
+def _phase_inputs(case, gpu):
+    """(wm, obs, act, rew, cont, q) of one phase-boundary case, on the CPU but the model."""
+    if case == "small":  # the small fixture's own B and T
+        fx = load_fixture("small_wm")
+        d, _ = build("small", gpu, fx)
+        obs, act, rew, cont, _ = window(fx)
+        return d.world_model, obs, act, rew, cont, _t(fx["q"])
+    g = torch.Generator().manual_seed(21)
+    if case == "vector":  # test_gpu_vector.test_vector_wm_step_matches_oracle's configuration
+        from test_gpu_vector import D_OBS, _dreamer
+        B, S, T = 4, 8, 6
+        d = _dreamer(gpu, batch_size=B, sequence_length=S, horizon=T)
+        obs = torch.randn(B, S, D_OBS, generator=g)
+    else:  # SMALL widths at 64 x 64, B = 128, T = 9: M1 = 1024 rows (B >= 128 and the tall heads)
+        from formula import SMALL
+        from widths_cases import build_dreamer
+        B, S, T = 128, 9, 9
+        d, _ = build_dreamer(dict(SMALL, observation_dims=[64, 64], batch_size=B, sequence_length=S, horizon=T,
+                                  precision=case), gpu)
+        obs = torch.randint(0, 256, (B, S, 3, 64, 64), generator=g).float()
+    wm = d.world_model
+    act = torch.rand(B, S, d.action_dims, generator=g) * 2 - 1
+    rew = torch.randn(B, S, 1, generator=g)
+    cont = (torch.rand(B, S, 1, generator=g) > 0.1).float()
+    q = torch.empty(T, B * wm.latent_num_rows, wm.latent_num_columns).exponential_(generator=g)
+    return wm, obs, act, rew, cont, q
+
+
+@pytest.mark.parametrize("case", ["small", "vector", "fp32", "bf16"])
+def test_wm_phase_boundaries_bit_identical(case, gpu):
+    """One step three ways from the same weights, window and explicit noise:
+    dr_wm_train_grads, dr_wm_train_phase with phases = 7 (rows_global = 0), and
+    dr_wm_train_phase once per phase bit (1, 2, 8, 16, 32; rows_global =
+    B (T - 1)) on the same workspace.  Losses, the skip flag, every gradient
+    and the three optional outputs are bit-identical: where a phase ends
+    changes nothing that is computed."""
+    from dreamer_amd import _lib as L
+    from dreamer_amd import hip
+    wm, obs, act, rew, cont, q = _phase_inputs(case, gpu)
+    B, S = act.shape[:2]
+    T, A, Hd = wm.horizon, wm.action_dims, wm.hidden_dims
+    R, C = wm.latent_num_rows, wm.latent_num_columns
+    obs, act, q = obs.to(gpu).contiguous(), act.to(gpu).contiguous(), q.to(gpu).contiguous()
+    rew, cont = rew.to(gpu).reshape(B, S).contiguous(), cont.to(gpu).reshape(B, S).contiguous()
+    frame = obs[0, 0].numel()
+    fr = L.dr_frames(None, 0, None, L.ptr(obs), S * frame, frame, 0 if wm.vector_obs else 1, 0)
+    bt = L.dr_wm_batch(L.ptr(act), S * A, A, L.ptr(rew), L.ptr(cont), S, 1)
+    f = wm._ensure_flat()
+    gw, gd = wm._grad_structs()
+    dims = wm.dims()
+    noise = hip.explicit_noise(q=q, device=gpu)
+    cfg = L.dr_wm_loss_cfg(wm.beta_pred, wm.beta_dyn, wm.beta_rep)
+    ws = hip.workspace(gpu).get("wm_train", L.query("dr_wm_train_workspace_bytes", dims, B, T))
+    args = (dims, wm.packed(), wm.packed_decoder(), B, T, fr, bt, noise, cfg)
+
+    def run(phases, rows):
+        nan = float("nan")
+        o = dict(losses=torch.full((4,), nan, device=gpu), skip=torch.full((1,), -1, dtype=torch.int32, device=gpu),
+                 hiddens=torch.full((T, B, Hd), nan, device=gpu), latents=torch.full((T, B, R, C), nan, device=gpu),
+                 post_logits=torch.full((T, B, R, C), nan, device=gpu))
+        stats = torch.zeros(8, device=gpu)
+        tail = (L.ptr(o["losses"]), L.ptr(o["skip"]), gw, gd, L.ptr(o["hiddens"]), L.ptr(o["latents"]),
+                L.ptr(o["post_logits"]), L.ptr(ws), ws.numel(), hip.stream())
+        f.grad.zero_()
+        if phases is None:
+            L.call("dr_wm_train_grads", *args, *tail)
+        for p in phases or ():
+            L.call("dr_wm_train_phase", *args, p, L.ptr(stats), rows, *tail)
+        torch.cuda.synchronize()
+        o.update({"grad " + n: p.grad.clone() for n, p in wm.named_parameters()})
+        return o
+
+    whole = run(None, 0)
+    assert int(whole["skip"].item()) == 0 and bool(torch.isfinite(whole["losses"]).all())
+    for label, got in (("phases = 7", run((7,), 0)), ("one call per phase bit", run((1, 2, 8, 16, 32), B * (T - 1)))):
+        for k, v in whole.items():
+            assert torch.equal(got[k], v), f"{case}, {label} vs dr_wm_train_grads: {k} differs"
+
+
 def test_wm_step_skips_nonfinite(gpu):
     """a non-finite loss leaves the parameters untouched (WorldModel.py:191-193)"""
     fx = load_fixture("small_wm")
