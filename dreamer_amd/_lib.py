@@ -156,6 +156,11 @@ _SIGS = {
                                   _f, fp, _f, _f, _i, fp, fp, fp, fp, fp]),
     "dr_nonfinite": (_i, [_ll, fp, fp, fp]),
     "dr_replay_gather": (_i, [_ll, _i, _i, _i, _i, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp]),
+    "dr_replay_sample_workspace_bytes": (_sz, [_ll]),
+    "dr_replay_sample": (_i, [_ll, _ll, _ll, _i, _i, fp, _d, fp, fp, _i, fp, fp, fp, _sz, fp]),
+    "dr_replay_probabilities": (_i, [_ll, _ll, _ll, _i, fp, _d, fp, fp, _sz, fp]),
+    "dr_replay_priority_update": (_i, [_ll, _i, fp, fp, _d, _d, _d, _d, _d, fp, fp, fp]),
+    "dr_wm_window_scores": (_i, [_P(dr_dims), _i, _i, dr_wm_loss_cfg, fp, _sz, fp, fp]),
     "dr_rng_advance": (_i, [fp, C.c_ulonglong, fp]),
     "dr_persistent_kernels": (_i, [_P(dr_dims), _i, _i, _i]),
     "dr_stream_create_cumask": (_i, [_i, _P(C.c_uint), _P(fp)]),

@@ -6,13 +6,57 @@ write head).  A device mirror of the ring (u8 frames, f32 actions, symlog
 rewards, continues) lives in HBM; new transitions are uploaded lazily before
 sampling, and windows are gathered on the device -- the fused train_Agent path
 never materialises the float32 window at all: the encoder's first conv reads
-the u8 frames straight from the ring (dr_frames)."""
+the u8 frames straight from the ring (dr_frames).
+
+replay = "curious" (Dreamer's config key) adds prioritised
+sampling on the device: one priority (f32) and one visit count (i32) per ring
+slot beside the mirror, sample_start_indices_device / update_priorities /
+sampling_probabilities on libdreamer_hip (include/dreamer_hip.h has the
+semantics).  sample_start_indices and everything else of the uniform path are
+untouched, and in uniform mode no priority tensor is ever allocated."""
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import hip
 from .utils import symlog_np
+
+
+REPLAY_MODES = ("uniform", "curious")
+REPLAY_DEFAULTS = dict(replay_c=1e4, replay_beta=0.7, replay_alpha=0.7, replay_eps=0.01, replay_p_new=1e5)
+
+
+def check_replay(replay, c, beta, alpha, eps, p_new):
+    """ValueError for an unknown mode or a constant outside its range."""
+    if replay not in REPLAY_MODES:
+        raise ValueError(f"replay must be one of {REPLAY_MODES}, got {replay!r}")
+    for name, v, ok in (("replay_beta", beta, 0.0 < beta <= 1.0), ("replay_alpha", alpha, alpha > 0.0),
+                        ("replay_eps", eps, eps > 0.0), ("replay_c", c, c >= 0.0),
+                        ("replay_p_new", p_new, p_new > 0.0)):
+        if not ok:  # a NaN fails every comparison
+            raise ValueError(f"{name} = {v!r} is out of range (beta in (0, 1], alpha > 0, eps > 0, c >= 0, p_new > 0)")
+
+
+def valid_starts(size, capacity, next_idx, seq_len):
+    """Boolean [capacity]: slot i is a valid window start iff 0 <= i < size - S + 1
+    and not (size == capacity and i < next_idx < i + S)."""
+    i = np.arange(capacity, dtype=np.int64)
+    ok = i < size - seq_len + 1
+    if size == capacity:
+        ok &= ~((i < next_idx) & (next_idx < i + seq_len))
+    return ok
+
+
+def valid_window_exists(size, capacity, next_idx, seq_len):
+    """valid_starts(...).any() without the array: the starts before the tail
+    minus those in the straddle zone [next_idx - S + 1, next_idx - 1]."""
+    n = size - seq_len + 1
+    if n <= 0:
+        return False
+    if size != capacity:
+        return True
+    lo, hi = max(0, next_idx - seq_len + 1), min(next_idx - 1, n - 1)
+    return n - max(0, hi - lo + 1) > 0
 
 
 class Buffer:
@@ -31,6 +75,10 @@ class Buffer:
         self.size = 0
         self._dev = None
         self._dirty = []  # slot indices not yet mirrored on the device
+        # prioritised replay (set by Dreamer from the config; the constructor stays the reference's)
+        self.replay = "uniform"
+        self.replay_c, self.replay_beta, self.replay_alpha, self.replay_eps, self.replay_p_new = (
+            REPLAY_DEFAULTS[k] for k in ("replay_c", "replay_beta", "replay_alpha", "replay_eps", "replay_p_new"))
 
     # ---- host side (Buffer.py:19-30) -----------------------------------------
     def add_to_buffer(self, observation, action, reward, continue_):
@@ -70,9 +118,12 @@ class Buffer:
         return starts
 
     # ---- device mirror -------------------------------------------------------
-    def _mirror(self):
+    def _require_gpu(self):
         if not self.device.type == "cuda":
             raise RuntimeError("dreamer_amd: the replay device mirror needs a GPU device")
+
+    def _mirror(self):
+        self._require_gpu()
         if self._dev is None:
             self._dev = dict(
                 frames=torch.zeros(self.observation_buffer.shape, dtype=torch.float32 if self.vector else torch.uint8,
@@ -81,6 +132,11 @@ class Buffer:
                 rewards=torch.zeros(self.reward_buffer.shape, device=self.device),
                 continues=torch.zeros(self.continue_buffer.shape, device=self.device))
             self._dirty = list(range(self.size))
+        curious = self.replay != "uniform"
+        if curious and "priority" not in self._dev:
+            # every slot starts as new; a slot never written is not a valid start
+            self._dev["priority"] = torch.full((self.capacity,), float(self.replay_p_new), device=self.device)
+            self._dev["visits"] = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
         if self._dirty:
             idx = np.unique(np.asarray(self._dirty, dtype=np.int64))
             runs = np.split(idx, np.where(np.diff(idx) != 1)[0] + 1)
@@ -89,8 +145,72 @@ class Buffer:
                 for k, host in (("frames", self.observation_buffer), ("actions", self.action_buffer),
                                 ("rewards", self.reward_buffer), ("continues", self.continue_buffer)):
                     self._dev[k][a:b].copy_(torch.from_numpy(host[a:b]), non_blocking=False)
+                if curious:  # a written slot is a new window; windows that merely contain it keep theirs
+                    self._dev["priority"][a:b] = float(self.replay_p_new)
+                    self._dev["visits"][a:b] = 0
             self._dirty = []
         return self._dev
+
+    # ---- prioritised replay (replay = "curious") -----------------------------
+    def _curious(self):
+        if self.replay == "uniform":
+            raise RuntimeError("dreamer_amd: prioritised sampling needs replay = 'curious'")
+        check_replay(self.replay, self.replay_c, self.replay_beta, self.replay_alpha, self.replay_eps,
+                     self.replay_p_new)
+        self._require_gpu()
+        if not valid_window_exists(self.size, self.capacity, self.next_idx, self.sequence_length):
+            raise ValueError("Not enough data in buffer to sample a full sequence")
+        m = self._mirror()
+        ws = hip.workspace(self.device).get("replay", L.query("dr_replay_sample_workspace_bytes", self.capacity))
+        return m, ws
+
+    def p_floor(self):
+        """What a stored priority that is non-finite or <= 0 counts as."""
+        return float(self.replay_eps) ** float(self.replay_alpha)
+
+    def sample_start_indices_device(self, batch_size, u=None):
+        """Prioritised window starts drawn on the device: (starts int64 (B,),
+        prob f32 (B,)), both device tensors; prob[b] = w / W of the start drawn.
+        No np.random call and no sync: the uniforms are Philox draws on a
+        stream id of the ad-hoc generator (u: explicit float64 uniforms (B,)
+        on the device, for parity tests)."""
+        m, ws = self._curious()
+        B = int(batch_size)
+        starts = torch.empty(B, dtype=torch.int64, device=self.device)
+        prob = torch.empty(B, device=self.device)
+        if u is not None:
+            if u.dtype != torch.float64 or tuple(u.shape) != (B,):
+                raise ValueError(f"u must be float64 of shape ({B},)")
+            u = u.contiguous()
+            rng, sid = None, 0
+        else:
+            nz = hip.adhoc(self.device).noise()
+            rng, sid = nz.rng, nz.stream
+        L.call("dr_replay_sample", self.capacity, self.size, self.next_idx, self.sequence_length, B,
+               L.ptr(m["priority"]), self.p_floor(), L.ptr(u), rng, sid, L.ptr(starts), L.ptr(prob), L.ptr(ws),
+               ws.numel(), hip.stream())
+        return starts, prob
+
+    def update_priorities(self, starts_dev, scores_dev):
+        """priority / visits after a world-model step on windows `starts_dev`
+        (int64 (B,)) whose losses were `scores_dev` (f32 (B,)); no sync."""
+        m, _ = self._curious()
+        B = int(starts_dev.numel())
+        if starts_dev.dtype != torch.int64 or scores_dev.dtype != torch.float32 or int(scores_dev.numel()) != B:
+            raise ValueError("update_priorities takes int64 starts and float32 scores of one length")
+        L.call("dr_replay_priority_update", self.capacity, B, L.ptr(starts_dev.contiguous()),
+               L.ptr(scores_dev.contiguous()), float(self.replay_c), float(self.replay_beta),
+               float(self.replay_alpha), float(self.replay_eps), float(self.replay_p_new), L.ptr(m["priority"]),
+               L.ptr(m["visits"]), hip.stream())
+
+    def sampling_probabilities(self):
+        """f32 device tensor (capacity,): the probability that a draw of
+        sample_start_indices_device returns each slot (0 for an invalid start)."""
+        m, ws = self._curious()
+        prob = torch.empty(self.capacity, device=self.device)
+        L.call("dr_replay_probabilities", self.capacity, self.size, self.next_idx, self.sequence_length,
+               L.ptr(m["priority"]), self.p_floor(), L.ptr(prob), L.ptr(ws), ws.numel(), hip.stream())
+        return prob
 
     def device_key(self):
         m = self._mirror()

@@ -1310,6 +1310,56 @@ extern "C" int dr_wm_train_grads(const dr_dims* d, const dr_world_model* wm, con
                 gw, gd, hiddens_out, latents_out, post_logits_out, ws, ws_bytes, s);
 }
 
+// Per-window loss of the last DR_WM_FWD on this workspace (prioritised replay,
+// DESIGN.md 5n): the terms of k_wm_stats restricted to window b, the KL without
+// the free-bit clamp.  Reads obs_part, rew_row, cont_row, kl_grp and cont_tm;
+// the backward stages write none of the five, so it may follow a whole step.
+// One wave per window, lane t over the steps (row i = (t - 1) B + b).
+__global__ __launch_bounds__(256) void k_wm_window_scores(int B, int T1, int R, int nparts,
+                                                          const float* __restrict__ obs_part,
+                                                          const float* __restrict__ rew_row,
+                                                          const float* __restrict__ cont_row,
+                                                          const float* __restrict__ kl_grp,
+                                                          const float* __restrict__ cont_tm, dr_wm_loss_cfg cfg,
+                                                          float* __restrict__ scores) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  float sp = 0.f, sm = 0.f, sk = 0.f;
+  for (int t = lane; t < T1; t += 64) {
+    const long long i = (long long)t * B + b;
+    const float m = cont_tm[i];
+    float o = 0.f;
+    for (int j = 0; j < nparts; ++j) o += obs_part[i * nparts + j];
+    float k = 0.f;
+    for (int g = 0; g < R; ++g) k += kl_grp[i * R + g];
+    sp += m * ((o - rew_row[i]) + cont_row[i]);
+    sm += m;
+    sk += m * k;
+  }
+  sp = wave_sum(sp);
+  sm = wave_sum(sm);
+  sk = wave_sum(sk);
+  if (lane == 0) {
+    const float pred = sp / (sm + 1e-5f);
+    const float kl = sk / (float)T1;
+    scores[b] = cfg.beta_pred * pred + (cfg.beta_dyn + cfg.beta_rep) * kl;
+  }
+}
+
+extern "C" int dr_wm_window_scores(const dr_dims* d, int B, int T, dr_wm_loss_cfg cfg, void* ws, size_t ws_bytes,
+                                   float* scores_out, hipStream_t s) {
+  DR_REQUIRE(d && ws && scores_out && B > 0 && T >= 2, "null argument or T < 2");
+  const WmDims D = wm_dims(d, B, T);
+  Carve c(ws);
+  WmWs w;
+  wm_carve(c, d, D, w);
+  WS_CHECK(c, ws_bytes);
+  hipLaunchKernelGGL(k_wm_window_scores, dim3(blocks(B, 4)), dim3(256), 0, s, B, T - 1, d->rows,
+                     D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2), w.obs_part, w.rew_row, w.cont_row, w.kl_grp,
+                     w.cont_tm, cfg, scores_out);
+  return dr_check_launch("wm_window_scores");
+}
+
 // ===========================================================================
 // a20  Decoder.forward (VariationalAutoEncoder.py:139-161), inference
 // ===========================================================================

@@ -14,7 +14,7 @@ from tqdm import tqdm
 from . import _lib as L
 from . import hip
 from .agent import Agent
-from .buffer import Buffer
+from .buffer import REPLAY_DEFAULTS, Buffer, check_replay
 from .utils import _sanitize_for_save
 from .world_model import WorldModel
 
@@ -103,6 +103,15 @@ class Dreamer(nn.Module):
         self.world_model.precision = self.precision  # encoder kernels: bf16 MFMA in perf mode
         if self.precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {self.precision!r}")
+        # extra config keys: "uniform" replay (default: the
+        # reference's np.random starts, untouched) or "curious" -- prioritised
+        # window sampling on the device (Curious Replay, Kauvar et al. 2023;
+        # the defaults are the paper's constants)
+        buf = self.buffer
+        buf.replay = c.get("replay", "uniform")
+        for k, v in REPLAY_DEFAULTS.items():
+            setattr(buf, k, float(c.get(k, v)))
+        check_replay(buf.replay, buf.replay_c, buf.replay_beta, buf.replay_alpha, buf.replay_eps, buf.replay_p_new)
         self.device = device
         self.agent_obs = None
         self.agent_hidden = None
@@ -325,7 +334,9 @@ class Dreamer(nn.Module):
         DreamResult (entropy(), curves(), pick(), video()).
 
         starts: window starts (default: buffer.sample_start_indices(batch_size
-        or self.batch_size)); context defaults to S // 2 (the warm start's),
+        or self.batch_size) -- uniform also with replay = "curious": evaluation
+        sees the data distribution, not the training distribution); context
+        defaults to S // 2 (the warm start's),
         1 <= context <= S; horizon defaults to self.horizon, any H >= 1 (a dream
         needs no ring frames).  samples: an integer in 1 .. 64 with B * samples
         <= 4096 (ValueError otherwise, raised before np.random is drawn from,
@@ -420,7 +431,11 @@ class Dreamer(nn.Module):
         return self._engine
 
     def train_Agent(self):
-        """Dreamer.train_Agent (Dreamer.py:264-287): AC_epochs fused epochs."""
+        """Dreamer.train_Agent (Dreamer.py:264-287): AC_epochs fused epochs.
+        replay = "curious": the starts come from the device sampler (the
+        sequential epoch loop; priorities and visits are not touched)."""
+        if self._curious():
+            return self._train_agent_curious()
         if self.AC_epochs > 1 and self.pipeline_epochs and not self.engine.persistent_chain():
             # config key pipeline_epochs (default on): the epochs' window
             # starts are drawn up front (same np.random order); the warm start
@@ -451,8 +466,33 @@ class Dreamer(nn.Module):
             lc.append(c.clone())
         return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
 
+    def _curious(self):
+        """True in prioritised-replay mode (ValueError under data parallelism:
+        per-rank priorities need a design of their own)."""
+        if self.buffer.replay == "uniform":
+            return False
+        if self.world is not None or self.world_model._dp is not None:
+            raise ValueError("replay = 'curious' is not supported under data parallelism")
+        return True
+
+    def _train_agent_curious(self):
+        la, lc = [], []
+        for _ in tqdm(range(self.AC_epochs), desc="Training Agent in Dreams", leave=False):
+            starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
+            a, c = self.engine.run(starts)
+            la.append(a.clone())
+            lc.append(c.clone())
+        return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
+
     def train_world_model(self):  # Dreamer.py:228-242
         out = []
+        if self._curious():
+            # per epoch: device sample -> step with per-window scores -> priority update; no host round trip
+            for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
+                starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
+                out.append(self.world_model.train_step_ring(self.buffer, starts, scores=True))
+                self.buffer.update_priorities(starts, self.world_model.last_window_scores)
+            return out
         for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
             if self.device.type == "cuda":
                 # same np.random draws as sample_sequences; frames stay u8 in HBM
@@ -490,7 +530,7 @@ class Dreamer(nn.Module):
         opt = lambda o: {"exp_avg": cpu(o.exp_avg), "exp_avg_sq": cpu(o.exp_avg_sq), "step": cpu(o.step_dev)}
         name, keys, pos, has_gauss, gauss = np.random.get_state()
         er, ar = hip.rng(self.device), hip.adhoc(self.device)
-        return {
+        st = {
             "format": self.TRAINING_STATE_FORMAT,
             "model": {k: cpu(v) for k, v in self.state_dict().items()},
             "opt_actor": opt(ag.actor_optimiser), "opt_critic": opt(ag.critic_optimiser), "opt_wm": opt(wm.optimiser),
@@ -507,6 +547,10 @@ class Dreamer(nn.Module):
                        "next_idx": int(buf.next_idx), "size": int(buf.size)},
             "seed": int(self.seed),
         }
+        if buf.replay != "uniform":  # prioritised replay: the per-slot state (uniform mode: exactly the keys above)
+            m = buf._mirror()
+            st["buffer"].update(priority=cpu(m["priority"]), visits=cpu(m["visits"]))
+        return st
 
     def save_training_state(self, path):
         torch.save(self.training_state(), path)
@@ -540,6 +584,12 @@ class Dreamer(nn.Module):
         buf.continue_buffer[...] = b["cont"].numpy()
         buf.next_idx, buf.size = int(b["next_idx"]), int(b["size"])
         buf._dirty = list(range(buf.capacity))  # the device mirror re-uploads on next use
+        if buf.replay != "uniform":
+            if "priority" not in b:
+                raise ValueError("the training state was saved in uniform replay mode: it has no priorities")
+            m = buf._mirror()  # the re-upload marks every slot new; the saved per-slot state goes in after it
+            m["priority"].copy_(b["priority"])
+            m["visits"].copy_(b["visits"])
         self.seed = int(st["seed"])
 
     # ------------------------------------------------- acting (batch-1, HIP)

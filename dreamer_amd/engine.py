@@ -440,15 +440,22 @@ class ImaginationEngine:
     def run(self, starts_np, timing=False):
         """One train_Agent epoch from host window starts; returns the device
         loss slots (actor, critic).  With timing=True, HIP events bracket every
-        phase (self.last_events)."""
+        phase (self.last_events).  starts_np may also be a device int64 tensor
+        (B,) (prioritised replay): one device-to-device copy into self.starts,
+        no pinned staging and no wait."""
         self.check_faults(wait=False)
-        i = self.epochs & 1
-        if self.copy_ev[i] is not None:
-            self.copy_ev[i].synchronize()
-        self.starts_host[i].copy_(torch.from_numpy(np.asarray(starts_np, dtype=np.int64)))
-        self.starts.copy_(self.starts_host[i], non_blocking=True)
-        self.copy_ev[i] = torch.cuda.Event()
-        self.copy_ev[i].record()
+        if isinstance(starts_np, torch.Tensor) and starts_np.is_cuda:
+            if starts_np.dtype != torch.int64 or tuple(starts_np.shape) != tuple(self.starts.shape):
+                raise ValueError(f"device starts must be int64 of shape {tuple(self.starts.shape)}")
+            self.starts.copy_(starts_np)
+        else:
+            i = self.epochs & 1
+            if self.copy_ev[i] is not None:
+                self.copy_ev[i].synchronize()
+            self.starts_host[i].copy_(torch.from_numpy(np.asarray(starts_np, dtype=np.int64)))
+            self.starts.copy_(self.starts_host[i], non_blocking=True)
+            self.copy_ev[i] = torch.cuda.Event()
+            self.copy_ev[i].record()
         self.epochs += 1
         ag = self.dr.agent
         key = (ag.params_key(), self.dr.world_model.params_key(), self.dr.buffer.device_key())

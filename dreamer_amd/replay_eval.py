@@ -79,7 +79,10 @@ def window_prologue(dr, starts, batch_size, T, draws, mark, check=None):
     """starts: the window starts, or None to sample batch_size (default
     dr.batch_size) of them.  check(B), if given, runs before the sampling and
     on the final B.  draws(B, dev) resolves the call's noise (resolve_noise)
-    once B is known, before the gather.  Marks "gather" and "encoder"."""
+    once B is known, before the gather.  Marks "gather" and "encoder".
+    The sampled starts are uniform (buffer.sample_start_indices) also with
+    replay = "curious": evaluation sees the data distribution, not the
+    training distribution."""
     buf, wmod = dr.buffer, dr.world_model
     dev = buf.device
     if starts is None:

@@ -52,6 +52,7 @@ class WorldModel(nn.Module):
         self._flat = None
         self._dp = None  # (rank, world, group) under data parallelism
         self.last_losses = None  # device [total, loss_pred, KL_dyn, KL_rep] of the last training_step
+        self.last_window_scores = None  # device (B,): per-window losses of the last step run with scores=True
 
     # ---- libdreamer_hip packing ---------------------------------------------
     def dims(self, agent=None):
@@ -350,13 +351,13 @@ class WorldModel(nn.Module):
         Returns the total loss as a 0-d device tensor."""
         return self.train_step_hip(observation_sequences, action_sequences, reward_sequences, continue_sequences)
 
-    def train_step_hip(self, obs, act, rew, cont, noise_q=None, outputs=None, step=True):
+    def train_step_hip(self, obs, act, rew, cont, noise_q=None, outputs=None, step=True, scores=False):
         """obs (B,S,3,H,W) holding 0..255 (Buffer.sample_sequences), act
         (B,S,A), rew / cont (B,S,1).  noise_q: explicit Exp(1) draws
         (T, B*rows, cols) for the posterior samples (parity tests), else
         Philox.  outputs: optional dict that receives the time-major posterior
         hiddens / latents / logits.  step=False leaves the parameters alone
-        (gradients only)."""
+        (gradients only).  scores=True: train_step_ring's."""
         L.require_gpu(obs)
         B, S = act.shape[:2]
         Hh, Ww, A = self.observation_dim_x, self.observation_dim_y, self.action_dims
@@ -369,13 +370,17 @@ class WorldModel(nn.Module):
         else:
             fr = L.dr_frames(None, 0, None, L.ptr(obs), S * 3 * Hh * Ww, 3 * Hh * Ww, 1, 0)
         bt = L.dr_wm_batch(L.ptr(act), S * A, A, L.ptr(rew), L.ptr(cont), S, 1)
-        return self._train(fr, bt, B, S, obs.device, noise_q, outputs, step)
+        return self._train(fr, bt, B, S, obs.device, noise_q, outputs, step, scores)
 
-    def train_step_ring(self, buffer, starts, noise_q=None, outputs=None, step=True):
+    def train_step_ring(self, buffer, starts, noise_q=None, outputs=None, step=True, scores=False):
         """The same step fed straight from the device replay ring: frames are
         read as u8 by the first conv's loader, actions / rewards / continues
         gathered for the first `horizon` steps of each window (no float32
-        observation tensor is materialised, Buffer.py:58-61)."""
+        observation tensor is materialised, Buffer.py:58-61).  scores=True
+        also leaves the per-window losses of this step in last_window_scores
+        (f32 (B,), on the device; dr_wm_window_scores): one more
+        launch after the step, which reads what the forward left in the
+        workspace -- parameters, gradients and losses keep their bits."""
         dev = buffer.device
         B, T = len(starts), self.horizon
         st = torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev, non_blocking=True) \
@@ -392,10 +397,12 @@ class WorldModel(nn.Module):
                hip.stream())
         fr = buffer.frames_struct(st)
         bt = L.dr_wm_batch(L.ptr(act), T * self.action_dims, self.action_dims, L.ptr(rew), L.ptr(cont), T, 1)
-        return self._train(fr, bt, B, T, dev, noise_q, outputs, step)
+        return self._train(fr, bt, B, T, dev, noise_q, outputs, step, scores)
 
-    def _train(self, fr, bt, B, S, dev, noise_q, outputs, step):
+    def _train(self, fr, bt, B, S, dev, noise_q, outputs, step, scores=False):
         T = self.horizon
+        if scores and self._dp is not None:
+            raise ValueError("per-window scores (prioritised replay) are not supported under data parallelism")
         if S < T or T < 2:
             raise ValueError(f"training_step needs sequences of at least horizon={T} >= 2 steps (got {S})")
         Hd, R, C = self.hidden_dims, self.latent_num_rows, self.latent_num_columns
@@ -439,6 +446,9 @@ class WorldModel(nn.Module):
                 w.wait()
         if outputs is not None:
             outputs.update(hiddens=hid, latents=lat, post_logits=plog)
+        if scores:  # the backward stages write none of the loss terms it reads (wm.hip)
+            self.last_window_scores = torch.empty(B, device=dev)
+            L.call("dr_wm_window_scores", d, B, T, cfg, L.ptr(ws), ws.numel(), L.ptr(self.last_window_scores), st)
         if step:
             # GradScaler semantics: no update when the loss or a gradient is non-finite
             L.call("dr_nonfinite", f.numel, f.grad.data_ptr(), skip.data_ptr(), st)

@@ -523,6 +523,20 @@ int dr_wm_train_grads(const dr_dims* d, const dr_world_model* wm, const dr_decod
                       float* hiddens_out, float* latents_out, float* post_logits_out, void* ws, size_t ws_bytes,
                       hipStream_t stream);
 
+/* Per-window loss of the last DR_WM_FWD on this workspace (prioritised replay,
+ * below): scores_out[b], b < B, over the window's first T steps, from the
+ * per-row loss terms the forward left in the workspace (the backward stages
+ * write none of them, so the call may follow a whole dr_wm_train_phase).  Rows
+ * are time-major, i = (t-1) B + b; m_{b,t} is the mask of WorldModel.py:170:
+ *   pred_b = sum_t m (sqerr - rew_ll + cont_bce) / (sum_t m + 1e-5)
+ *   kl_b   = 1/(T-1) sum_t m sum_g KL_{b,t,g}
+ *   L_b    = beta_pred pred_b + (beta_dyn + beta_rep) kl_b
+ * The free-bit clamp max(1, KL) is left out on purpose: it would give every
+ * window the same KL term once the batch mean is under one nat.  (d, B, T) and
+ * the workspace are those of the step. */
+int dr_wm_window_scores(const dr_dims* d, int B, int T, dr_wm_loss_cfg cfg, void* ws, size_t ws_bytes,
+                        float* scores_out, hipStream_t stream);
+
 /* ---- a20  Decoder.forward (VAE.py:139-161), inference: mu [M][3][H][W] (NCHW)
  * from cat(h, flatten z) rows (h row stride ldh, z row stride ldz). */
 size_t dr_decoder_workspace_bytes(const dr_dims* d, int M);
@@ -888,6 +902,52 @@ int dr_replay_gather(long long cap, int B, int S, int frame_elems, int A, const 
                      const float* actions, const float* rewards, const float* continues,
                      const long long* starts, float* obs_out, float* act_out, float* rew_out,
                      float* cont_out, hipStream_t stream);
+
+/* ---- prioritised ("curious") replay: window sampling on the device ---------
+ * (Curious Replay, Kauvar et al. 2023.)  One priority and one visit count per
+ * ring slot; slot i stands for the window that starts at i.  priority is f32
+ * [cap], visits i32 [cap], both on the device beside the ring mirror.
+ *
+ * Valid starts: validity is the reference's (Buffer.py:33-48) with the
+ * straddle made exact instead of "one redraw".  Slot i is a valid start iff
+ *   0 <= i < size - S + 1 (S = sequence_length), and
+ *   not (size == cap and i < next_idx < i + S).
+ * Weight: w_i = priority[i] if i is valid, else 0; a stored priority that is
+ * non-finite or <= 0 counts as p_floor (= eps^alpha), so the total W is
+ * positive whenever a valid start exists.
+ * Draw: for a uniform u in [0, 1) the start is the least valid i with
+ * C_i > u W, C_i the inclusive running sum of w in slot order; if rounding
+ * leaves u W >= C_last, the last valid slot.  A draw never returns an invalid
+ * slot.  prob[b] = w_i / W.  Sums are float64 in a fixed order (priorities
+ * span 1e5 .. 4e-2 over up to 1e6 slots: an f32 running sum would make
+ * low-priority windows unreachable), so the same inputs give the same bits.
+ * Philox uniforms are 53-bit doubles from two words keyed (seed, offset,
+ * stream_id, row b).
+ * Priority update after a step on starts s_b with scores L_b:
+ *   visits[s] += number of rows b with s_b = s
+ *   priority[s] = c beta^visits[s] + (max_b |L_b| + eps)^alpha
+ * (the maximum over the rows with s_b = s, visits[s] the updated count); a
+ * non-finite score among them gives priority[s] = p_new.  The result does not
+ * depend on the order of the rows and is bitwise repeatable (no float
+ * atomics: the first row that holds a start writes its slot).  A start outside
+ * [0, cap) is ignored.
+ * Every call is asynchronous on `stream` and capturable; the caller owns the
+ * memory.  priority must be 16-byte aligned; cap <= 2^30. */
+size_t dr_replay_sample_workspace_bytes(long long cap);
+/* u: the uniforms [B] (parity, tests) or NULL: Philox on rng = the device
+ * {seed, offset} pair.  starts_out int64 [B]; prob_out f32 [B] or NULL.  Two
+ * stages: the masked sums of 1024-slot chunks into ws (the whole ring is
+ * re-summed on every call: the mask depends on size and next_idx), then one
+ * workgroup per draw. */
+int dr_replay_sample(long long cap, long long size, long long next_idx, int S, int B, const float* priority,
+                     double p_floor, const double* u, const unsigned long long* rng, int stream_id,
+                     long long* starts_out, float* prob_out, void* ws, size_t ws_bytes, hipStream_t stream);
+/* prob_out[i] = w_i / W for every slot i < cap (the same first stage and W). */
+int dr_replay_probabilities(long long cap, long long size, long long next_idx, int S, const float* priority,
+                            double p_floor, float* prob_out, void* ws, size_t ws_bytes, hipStream_t stream);
+int dr_replay_priority_update(long long cap, int B, const long long* starts, const float* scores, double c,
+                              double beta, double alpha, double eps, double p_new, float* priority, int* visits,
+                              hipStream_t stream);
 
 /* Which parts of a train_Agent epoch (Dreamer.py:264-287) run as ONE persistent
  * launch for these dims and shapes (the stream's CU mask aside): bit 0 the warm
