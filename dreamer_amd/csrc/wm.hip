@@ -84,7 +84,9 @@ __global__ void k_wm_kl(int M1, int R, int C, int W, const float* __restrict__ p
   const float mp = group_max(xp, W), mq = group_max(xq, W);
   const float ep = act ? expf(xp - mp) : 0.0f, eq = act ? expf(xq - mq) : 0.0f;
   const float sp = group_sum(ep, W), sq = group_sum(eq, W);
-  const float lp = xp - (mp + logf(sp)), lq = xq - (mq + logf(sq));
+  // (x - max) first: exact for nearby logits, so a constant offset on a group's logits changes no bit of the result
+  // (x - (max + log sum) rounds at the size of the logits: 1e-3 of absolute error at logits of 1e4)
+  const float lp = (xp - mp) - logf(sp), lq = (xq - mq) - logf(sq);
   const float p = ep / sp;
   const float term = act ? p * (lp - lq) : 0.0f;
   const float klg = group_sum(term, W);
@@ -180,7 +182,9 @@ __global__ void k_wm_final(const float* stats, int rows, dr_wm_loss_cfg cfg, flo
   const float denom = stats[0] + 1e-5f;
   const float pred = (stats[1] - stats[2] + stats[3]) / denom;
   const float kl = stats[4] / (float)rows;
-  const float total = cfg.beta_pred * pred + cfg.beta_dyn * fmaxf(1.0f, kl) + cfg.beta_rep * fmaxf(1.0f, kl);
+  // torch.max(1, kl) keeps a NaN KL (fmaxf would drop it: a finite total, no skip, and the KL gradient silently off)
+  const float fb = kl < 1.0f ? 1.0f : kl;
+  const float total = cfg.beta_pred * pred + cfg.beta_dyn * fb + cfg.beta_rep * fb;
   const float wk = kl > 1.0f ? 1.0f : (kl == 1.0f ? 0.5f : 0.0f);
   scal[1] = cfg.beta_dyn * wk / (float)rows;
   scal[2] = cfg.beta_rep * wk / (float)rows;
@@ -274,6 +278,80 @@ static int pow2_ge(int c) {
   int w = 1;
   while (w < c) w <<= 1;
   return w;
+}
+
+// ---------------------------------------------------------------------------
+// launchers of the loss kernels: each owns its kernel's grid, block and group
+// width, and is the only place that kernel is launched from (the step's
+// stages and the dr_internal_wm_loss_run test hook both go through them)
+// ---------------------------------------------------------------------------
+static int wm_gather(int B, int T, int A, const dr_wm_batch& bt, float* act_tm, float* rew_tm, float* cont_tm,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_gather, dim3(blocks((long long)B * T, 256)), dim3(256), 0, s, B, T, A, bt, act_tm, rew_tm,
+                     cont_tm);
+  return dr_check_launch("wm_gather");
+}
+static int wm_masksum(int M1, const float* cont_tm, float* stats, hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_masksum, dim3(1), dim3(256), 0, s, M1, cont_tm, stats);
+  return dr_check_launch("wm_masksum");
+}
+static int wm_coef(int M1, const float* cont_tm, float beta_pred, const float* stats, float* scal, float* coef_row,
+                   float* coef_obs, hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_coef, dim3(1), dim3(256), 0, s, M1, cont_tm, beta_pred, stats, scal, coef_row, coef_obs);
+  return dr_check_launch("wm_coef");
+}
+// one latent group on W = pow2 >= C lanes (group_sum / group_max reach 64 lanes: C <= 64)
+static int wm_kl_fwd(int M1, int R, int C, const float* prior, const float* post, float* kl_grp, hipStream_t s) {
+  DR_REQUIRE(C >= 1 && C <= 64, "latent classes must be in [1,64]");
+  const int W = pow2_ge(C);
+  if ((long long)M1 * R == 0) return DR_OK;
+  hipLaunchKernelGGL(k_wm_kl<0>, dim3(blocks((long long)M1 * R * W, 256)), dim3(256), 0, s, M1, R, C, W, prior, post,
+                     nullptr, nullptr, kl_grp, nullptr, nullptr);
+  return dr_check_launch("wm_kl");
+}
+static int wm_kl_bwd(int M1, int R, int C, const float* prior, const float* post, const float* cont_tm,
+                     const float* scal, float* g_prior, float* g_post, hipStream_t s) {
+  DR_REQUIRE(C >= 1 && C <= 64, "latent classes must be in [1,64]");
+  const int W = pow2_ge(C);
+  if ((long long)M1 * R == 0) return DR_OK;
+  hipLaunchKernelGGL(k_wm_kl<1>, dim3(blocks((long long)M1 * R * W, 256)), dim3(256), 0, s, M1, R, C, W, prior, post,
+                     cont_tm, scal, nullptr, g_prior, g_post);
+  return dr_check_launch("wm_kl_bwd");
+}
+static int wm_heads_loss(int M1, int nb, const float* rlog, const float* clog, const float* rew_tm,
+                         const float* cont_tm, const float* buckets, const float* coef_row, float* rew_row,
+                         float* cont_row, float* g_rew, float* g_cont, hipStream_t s) {
+  DR_REQUIRE(nb >= 2, "the reward head needs at least two buckets");
+  if (M1 == 0) return DR_OK;
+  hipLaunchKernelGGL(k_wm_heads, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, nb, rlog, clog, rew_tm, cont_tm, buckets,
+                     coef_row, rew_row, cont_row, g_rew, g_cont);
+  return dr_check_launch("wm_heads");
+}
+static int wm_stats(int M1, int R, int nparts, const float* obs_part, const float* rew_row, const float* cont_row,
+                    const float* kl_grp, const float* cont_tm, float* stats, hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_stats, dim3(1), dim3(256), 0, s, M1, R, nparts, obs_part, rew_row, cont_row, kl_grp, cont_tm,
+                     stats);
+  return dr_check_launch("wm_stats");
+}
+static int wm_final(const float* stats, int rows, dr_wm_loss_cfg cfg, float* scal, float* losses, int* skip,
+                    hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_final, dim3(1), dim3(64), 0, s, stats, rows, cfg, scal, losses, skip);
+  return dr_check_launch("wm_final");
+}
+static int ste_bwd_add(int M, int R, int C, const float* gz, long long ldg, const float* soft, long long lds,
+                       const float* extra, long long lde, float* gl, long long ldl, hipStream_t s) {
+  DR_REQUIRE(C >= 1 && C <= 64, "latent classes must be in [1,64]");
+  const int W = pow2_ge(C);
+  if ((long long)M * R == 0) return DR_OK;
+  hipLaunchKernelGGL(k_ste_bwd_add, dim3(blocks((long long)M * R * W, 256)), dim3(256), 0, s, M, R, C, W, gz, ldg, soft,
+                     lds, extra, lde, gl, ldl);
+  return dr_check_launch("ste_bwd_add");
+}
+static int vec_mse(int M1, int D, const float* mu, const float* x, const float* coef, float* g, float* part,
+                   hipStream_t s) {
+  if (M1 == 0) return DR_OK;
+  hipLaunchKernelGGL(k_vec_mse, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, D, mu, x, coef, g, part);
+  return dr_check_launch("vec_mse");
 }
 
 // ---------------------------------------------------------------------------
@@ -631,7 +709,6 @@ struct WmCtx {
   const float *hB, *zB, *post1;  // rows t >= 1 of h_all / z_all / plog
   float *gHB, *gZB;              // ... of gH / gZ
   const int *cin_t, *cout_t;     // convT k: cd[k] -> cd[k + 1] channels
-  int Wc;                        // latent classes rounded up to a power of two (the KL / sampler kernels' group width)
   WmCtx() = default;
   WmCtx(const WmCtx&) = delete;
 };
@@ -705,11 +782,9 @@ static int wm_prep(const WmCtx& x) {
   DR_TRY(perm_rows(D.e[N], D.Pf, eh, w.t_map0, w.w0tp, 1, s));
 
   // ---- window data ----
-  hipLaunchKernelGGL(k_wm_gather, dim3(blocks(M, 256)), dim3(256), 0, s, B, D.T, A, *x.bt, w.act_tm, w.rew_tm, w.cont_tm);
-  DR_TRY(dr_check_launch("wm_gather"));
+  DR_TRY(wm_gather(B, D.T, A, *x.bt, w.act_tm, w.rew_tm, w.cont_tm, s));
   DR_TRY(zero(w.zeros, (long long)B * (L + A + Hd), s));
-  hipLaunchKernelGGL(k_wm_masksum, dim3(1), dim3(256), 0, s, M1, w.cont_tm, x.stats);
-  return dr_check_launch("wm_masksum");
+  return wm_masksum(M1, w.cont_tm, x.stats, s);
 }
 
 // vector observations, encoder stand-in: pre[0] = X W1^T + b1, a[0] = SiLU, pre[N-1] = a[0] W2^T + b2, a[N-1] = SiLU
@@ -730,9 +805,7 @@ static int wm_fwd_encoder(const WmCtx& x) {
   const dr_world_model* wm = x.wm;
   const int B = D.B, M = D.M, Hd = D.Hd, eh = D.eh, F = D.F, IH = D.IH, IW = D.IW, N = D.N;
   // the forward's first launch: the rows' prediction-loss factors, from the (all-reduced) mask sum of wm_prep
-  hipLaunchKernelGGL(k_wm_coef, dim3(1), dim3(256), 0, s, D.M1, w.cont_tm, x.cfg.beta_pred, x.stats, w.scal, w.coef_row,
-                     w.coef_obs);
-  DR_TRY(dr_check_launch("wm_coef"));
+  DR_TRY(wm_coef(D.M1, w.cont_tm, x.cfg.beta_pred, x.stats, w.scal, w.coef_row, w.coef_obs, s));
   float* aL = w.a[N - 1];  // the flattened features (NCHW; vector mode: the MLP's last activation)
   if (D.Dv) {
     DR_TRY(wm_vec_encoder_fwd(x));
@@ -881,9 +954,7 @@ static int wm_vec_decoder_fwd(const WmCtx& x) {
   DR_TRY(run(G_NT, AM_PLAIN, lin(M1, D.Fd, D.Fd, w.du2p, D.Fd, dec->convt[0].w, D.Fd, dec->convt[0].b, w.dq[0], D.Fd), s));
   DR_TRY(silu(MF, w.dq[0], w.dqp[0], s));
   DR_TRY(run(G_NT, AM_PLAIN, lin(M1, Dv, D.Fd, w.dqp[0], D.Fd, dec->convt[1].w, D.Fd, dec->convt[1].b, w.dq[1], Dv), s));
-  hipLaunchKernelGGL(k_vec_mse, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, Dv, w.dq[1], w.x0 + (long long)D.B * Dv,
-                     w.coef_obs, w.dgout, w.obs_part);
-  return dr_check_launch("vec_mse");
+  return vec_mse(M1, Dv, w.dq[1], w.x0 + (long long)D.B * Dv, w.coef_obs, w.dgout, w.obs_part, s);
 }
 
 // convT k of the decoder over n frames: geometry, weights and bias (the caller sets the input and the outputs)
@@ -935,15 +1006,11 @@ static int wm_fwd_losses(const WmCtx& x) {
   const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
   const dr_dims* d = x.d;
   const int M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, R = d->rows;
-  hipLaunchKernelGGL(k_wm_kl<0>, dim3(blocks((long long)M1 * R * x.Wc, 256)), dim3(256), 0, s, M1, R, d->cols, x.Wc,
-                     w.head[0].lg, x.post1, w.cont_tm, w.scal, w.kl_grp, nullptr, nullptr);
-  DR_TRY(dr_check_launch("wm_kl"));
-  hipLaunchKernelGGL(k_wm_heads, dim3(blocks(M1, 4)), dim3(256), 0, s, M1, D.nb, w.head[1].lg, w.head[2].lg, w.rew_tm,
-                     w.cont_tm, x.wm->buckets_rew, w.coef_row, w.rew_row, w.cont_row, w.head[1].g, w.head[2].g);
-  DR_TRY(dr_check_launch("wm_heads"));
-  hipLaunchKernelGGL(k_wm_stats, dim3(1), dim3(256), 0, s, M1, R, D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2),
-                     w.obs_part, w.rew_row, w.cont_row, w.kl_grp, w.cont_tm, x.stats);
-  DR_TRY(dr_check_launch("wm_stats"));
+  DR_TRY(wm_kl_fwd(M1, R, d->cols, w.head[0].lg, x.post1, w.kl_grp, s));
+  DR_TRY(wm_heads_loss(M1, D.nb, w.head[1].lg, w.head[2].lg, w.rew_tm, w.cont_tm, x.wm->buckets_rew, w.coef_row,
+                       w.rew_row, w.cont_row, w.head[1].g, w.head[2].g, s));
+  DR_TRY(wm_stats(M1, R, D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2), w.obs_part, w.rew_row, w.cont_row, w.kl_grp,
+                  w.cont_tm, x.stats, s));
   if (x.hiddens_out) DR_TRY(copy2d(x.hiddens_out, Hd, w.h_all, Hd, Hd, M, s));
   if (x.latents_out) DR_TRY(copy2d(x.latents_out, L, w.z_all, L, L, M, s));
   if (x.post_logits_out) DR_TRY(copy2d(x.post_logits_out, L, w.plog, L, L, M, s));
@@ -1095,11 +1162,8 @@ static int wm_bwd_heads(const WmCtx& x) {
   const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
   const dr_dims* d = x.d;
   const int M1 = D.M1, R = d->rows;
-  hipLaunchKernelGGL(k_wm_final, dim3(1), dim3(64), 0, s, x.stats, x.rows_global, x.cfg, w.scal, x.losses, x.skip);
-  DR_TRY(dr_check_launch("wm_final"));
-  hipLaunchKernelGGL(k_wm_kl<1>, dim3(blocks((long long)M1 * R * x.Wc, 256)), dim3(256), 0, s, M1, R, d->cols, x.Wc,
-                     w.head[0].lg, x.post1, w.cont_tm, w.scal, nullptr, w.head[0].g, w.gpost);
-  DR_TRY(dr_check_launch("wm_kl_bwd"));
+  DR_TRY(wm_final(x.stats, x.rows_global, x.cfg, w.scal, x.losses, x.skip, s));
+  DR_TRY(wm_kl_bwd(M1, R, d->cols, w.head[0].lg, x.post1, w.cont_tm, w.scal, w.head[0].g, w.gpost, s));
   DR_TRY(zero(w.gH, (long long)D.M * D.Hd, s));
   DR_TRY(zero(w.gZ, (long long)D.M * D.L, s));
   for (int i = 0; i < 3; ++i) DR_TRY(head_bwd(x, i));
@@ -1112,7 +1176,7 @@ static int wm_bwd_scan(const WmCtx& x) {
   const WmDims& D = x.D; const WmWs& w = x.w; hipStream_t s = x.s;
   const dr_dims* d = x.d; const dr_world_model *wm = x.wm, *gw = x.gw;
   const int B = D.B, T = D.T, M = D.M, M1 = D.M1, L = D.L, Hd = D.Hd, A = D.A, eh = D.eh, F = D.F, N = D.N;
-  const int R = d->rows, Wc = x.Wc;
+  const int R = d->rows;
   // B >= 128: the per-step input-gradient products (K = 3 Hd) on the split3
   // wave-K kernel from weight planes split once per step (the f32 wave-K
   // kernel took 30.7 us per grouped launch at B = 256)
@@ -1125,10 +1189,8 @@ static int wm_bwd_scan(const WmCtx& x) {
     const long long rb = (long long)t * B;
     float* gH_t = w.gH + rb * Hd;
     // straight-through sampler (+ KL-rep on rows t >= 1) -> dL/d logits
-    hipLaunchKernelGGL(k_ste_bwd_add, dim3(blocks((long long)B * R * Wc, 256)), dim3(256), 0, s, B, R, d->cols, Wc,
-                       w.gZ + rb * L, (long long)L, w.soft + rb * L, (long long)L,
-                       t > 0 ? w.gpost + (rb - B) * L : nullptr, (long long)L, w.glog + rb * L, (long long)L);
-    DR_TRY(dr_check_launch("ste_bwd_add"));
+    DR_TRY(ste_bwd_add(B, R, d->cols, w.gZ + rb * L, (long long)L, w.soft + rb * L, (long long)L,
+                       t > 0 ? w.gpost + (rb - B) * L : nullptr, (long long)L, w.glog + rb * L, (long long)L, s));
     // latent_mapper.3, then LN-SiLU(.1) fused into latent_mapper.0's h-columns input gradient
     DR_TRY(run(G_NT, AM_PLAIN, bwd_nt(B, eh, L, w.glog + rb * L, L, w.t_map3, w.gx_s, eh, 0), s));
     DR_TRY(lnbwd_nt(B, Hd, eh, w.gx_s, eh, w.pre_m + rb * eh, eh, wm->map1, w.t_map0 + (long long)F * eh, gH_t, Hd, 1,
@@ -1265,7 +1327,6 @@ static int wm_run(int phases, const dr_dims* d, const dr_world_model* wm, const 
   x.hB = w.h_all + (long long)B * D.Hd; x.zB = w.z_all + (long long)B * D.L;
   x.gHB = w.gH + (long long)B * D.Hd; x.gZB = w.gZ + (long long)B * D.L;
   x.cin_t = D.cd; x.cout_t = D.cd + 1;
-  x.Wc = pow2_ge(d->cols);
   x.post1 = w.plog + (long long)B * D.L;
 
   if (phases & DR_WM_PREP) DR_TRY(wm_prep(x));
@@ -1346,6 +1407,14 @@ __global__ __launch_bounds__(256) void k_wm_window_scores(int B, int T1, int R, 
   }
 }
 
+static int wm_window_scores(int B, int T1, int R, int nparts, const float* obs_part, const float* rew_row,
+                            const float* cont_row, const float* kl_grp, const float* cont_tm, dr_wm_loss_cfg cfg,
+                            float* scores, hipStream_t s) {
+  hipLaunchKernelGGL(k_wm_window_scores, dim3(blocks(B, 4)), dim3(256), 0, s, B, T1, R, nparts, obs_part, rew_row,
+                     cont_row, kl_grp, cont_tm, cfg, scores);
+  return dr_check_launch("wm_window_scores");
+}
+
 extern "C" int dr_wm_window_scores(const dr_dims* d, int B, int T, dr_wm_loss_cfg cfg, void* ws, size_t ws_bytes,
                                    float* scores_out, hipStream_t s) {
   DR_REQUIRE(d && ws && scores_out && B > 0 && T >= 2, "null argument or T < 2");
@@ -1354,10 +1423,8 @@ extern "C" int dr_wm_window_scores(const dr_dims* d, int B, int T, dr_wm_loss_cf
   WmWs w;
   wm_carve(c, d, D, w);
   WS_CHECK(c, ws_bytes);
-  hipLaunchKernelGGL(k_wm_window_scores, dim3(blocks(B, 4)), dim3(256), 0, s, B, T - 1, d->rows,
-                     D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2), w.obs_part, w.rew_row, w.cont_row, w.kl_grp,
-                     w.cont_tm, cfg, scores_out);
-  return dr_check_launch("wm_window_scores");
+  return wm_window_scores(B, T - 1, d->rows, D.Dv ? 1 : op_convT_mse_parts(D.IH / 2, D.IW / 2), w.obs_part, w.rew_row,
+                          w.cont_row, w.kl_grp, w.cont_tm, cfg, scores_out, s);
 }
 
 // ===========================================================================
@@ -1439,4 +1506,155 @@ extern "C" int dr_decoder_fwd(const dr_dims* d, const dr_decoder* dec, int M, co
     }
   }
   return DR_OK;
+}
+
+// ===========================================================================
+// Test hook of the loss stage and of the reverse scan's row kernels
+// (tests/test_gpu_wm_loss.py): run exactly one of them on caller-made
+// operands, through the launcher the step itself uses (above; ops.h for the
+// row kernels of ops.hip).  Not in the public header.
+//
+// v: ints, num: doubles, ptrs: device pointers; per op (tests/wm_loss_ref.py
+// mirrors the op codes):
+//   WL_GATHER          v B T A act_sb act_st rc_sb rc_st; ptrs actions rewards continues act_tm rew_tm cont_tm
+//   WL_PREP            k_wm_masksum then k_wm_coef.  v M1 set_stats0; num beta_pred stats0 (written over stats[0]
+//                      between the two when set_stats0: the all-reduced mask sum of a data-parallel caller);
+//                      ptrs cont_tm stats scal coef_row coef_obs
+//   WL_KL_FWD          v M1 R C; ptrs prior post kl_grp
+//   WL_HEADS           v M1 nb; ptrs rlog clog rew_tm cont_tm buckets coef_row rew_row cont_row g_rew g_cont
+//   WL_STATS           v M1 R nparts; ptrs obs_part rew_row cont_row kl_grp cont_tm stats
+//   WL_FINAL           v rows; num beta_pred beta_dyn beta_rep; ptrs stats scal losses skip (skip may be NULL)
+//   WL_KL_BWD          v M1 R C; ptrs prior post cont_tm scal g_prior g_post
+//   WL_STE_BWD_ADD     v M R C ldg lds lde ldl; ptrs gz soft extra gl (extra may be NULL)
+//   WL_VEC_MSE         v M1 D; ptrs mu x coef g part
+//   WL_WINDOW_SCORES   v B T1 R nparts; num beta_pred beta_dyn beta_rep; ptrs obs_part rew_row cont_row kl_grp
+//                      cont_tm scores
+//   WL_GRU_BWD         v B Hd ldg ldh ldo accumulate; ptrs g_hp h sr su sn sghn g_gi g_gh gh_out (h may be NULL)
+//   WL_LN_SILU_BWD     v M K ldgx ldp ldgp; ptrs gx pre gamma beta g_pre gy xhat g_pre16 (gy and xhat both or
+//                      neither; g_pre16 may be NULL)
+//   WL_SOFTMAX_STE_BWD v M R C ldg lds; ptrs gz soft gl
+//   WL_COLSUM_MULTI    v M njobs accumulate, then (N ldx ldy) per job; ptrs (X Y out) per job (Y may be NULL).
+//                      accumulate (one job only): op_colsum, the one caller of colsum_slab that adds to `out`
+// A size, stride or pointer combination that is refused returns DR_E_INVALID
+// before anything is launched, dr_set_error's text in msg.
+// ===========================================================================
+enum {
+  WL_GATHER, WL_PREP, WL_KL_FWD, WL_HEADS, WL_STATS, WL_FINAL, WL_KL_BWD, WL_STE_BWD_ADD, WL_VEC_MSE,
+  WL_WINDOW_SCORES, WL_GRU_BWD, WL_LN_SILU_BWD, WL_SOFTMAX_STE_BWD, WL_COLSUM_MULTI, WL_COUNT
+};
+
+static int wm_loss_run(int op, const int* v, const double* num, void* const* ptrs, hipStream_t s) {
+  DR_REQUIRE(v && ptrs, "null descriptor or pointer array");
+  DR_REQUIRE(op >= 0 && op < WL_COUNT, "unknown op");
+  auto F = [&](int i) { return (float*)ptrs[i]; };
+  // every slot 0 .. n - 1 but those in the `optional` bit mask must be set
+  auto given = [&](int n, unsigned optional) {
+    for (int i = 0; i < n; ++i)
+      if (!ptrs[i] && !(optional >> i & 1)) return false;
+    return true;
+  };
+  const bool grouped = op == WL_KL_FWD || op == WL_KL_BWD || op == WL_STE_BWD_ADD || op == WL_SOFTMAX_STE_BWD;
+  if (grouped) {
+    DR_REQUIRE(v[0] >= 1 && v[1] >= 1, "rows and latent groups must be positive");
+    DR_REQUIRE(v[2] >= 1 && v[2] <= 64, "latent classes must be in [1,64]");
+  }
+  const bool scalars = op == WL_PREP || op == WL_FINAL || op == WL_WINDOW_SCORES;
+  DR_REQUIRE(!scalars || num, "this op reads its scalars from num");
+  switch (op) {
+    case WL_GATHER: {
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1 && v[2] >= 0, "B, T must be positive, A non-negative");
+      DR_REQUIRE(given(6, 0), "null operand");
+      dr_wm_batch bt = {};
+      bt.actions = F(0); bt.act_sb = v[3]; bt.act_st = v[4];
+      bt.rewards = F(1); bt.continues = F(2); bt.rc_sb = v[5]; bt.rc_st = v[6];
+      return wm_gather(v[0], v[1], v[2], bt, F(3), F(4), F(5), s);
+    }
+    case WL_PREP: {
+      DR_REQUIRE(v[0] >= 1, "M1 must be positive");
+      DR_REQUIRE(given(5, 0), "null operand");
+      DR_TRY(wm_masksum(v[0], F(0), F(1), s));
+      if (v[1]) {
+        const float f = (float)num[1];
+        DR_TRY_HIP(hipMemsetD32Async((hipDeviceptr_t)F(1), __builtin_bit_cast(int, f), 1, s));
+      }
+      return wm_coef(v[0], F(0), (float)num[0], F(1), F(2), F(3), F(4), s);
+    }
+    case WL_KL_FWD:
+      DR_REQUIRE(given(3, 0), "null operand");
+      return wm_kl_fwd(v[0], v[1], v[2], F(0), F(1), F(2), s);
+    case WL_HEADS:
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 2, "M1 must be positive, nb at least 2");
+      DR_REQUIRE(given(10, 0), "null operand");
+      return wm_heads_loss(v[0], v[1], F(0), F(1), F(2), F(3), F(4), F(5), F(6), F(7), F(8), F(9), s);
+    case WL_STATS:
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1 && v[2] >= 1, "M1, R, nparts must be positive");
+      DR_REQUIRE(given(6, 0), "null operand");
+      return wm_stats(v[0], v[1], v[2], F(0), F(1), F(2), F(3), F(4), F(5), s);
+    case WL_FINAL: {
+      DR_REQUIRE(v[0] >= 1, "rows must be positive");
+      DR_REQUIRE(given(4, 1u << 3), "null operand");
+      const dr_wm_loss_cfg cfg = {(float)num[0], (float)num[1], (float)num[2]};
+      return wm_final(F(0), v[0], cfg, F(1), F(2), (int*)ptrs[3], s);
+    }
+    case WL_KL_BWD:
+      DR_REQUIRE(given(6, 0), "null operand");
+      return wm_kl_bwd(v[0], v[1], v[2], F(0), F(1), F(2), F(3), F(4), F(5), s);
+    case WL_STE_BWD_ADD: {
+      const int L = v[1] * v[2];
+      DR_REQUIRE(v[3] >= L && v[4] >= L && v[6] >= L && (!ptrs[2] || v[5] >= L), "row stride below R * C");
+      DR_REQUIRE(given(4, 1u << 2), "null operand");
+      return ste_bwd_add(v[0], v[1], v[2], F(0), v[3], F(1), v[4], F(2), v[5], F(3), v[6], s);
+    }
+    case WL_VEC_MSE:
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1, "M1, D must be positive");
+      DR_REQUIRE(given(5, 0), "null operand");
+      return vec_mse(v[0], v[1], F(0), F(1), F(2), F(3), F(4), s);
+    case WL_WINDOW_SCORES: {
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1 && v[2] >= 1 && v[3] >= 1, "B, T - 1, R, nparts must be positive");
+      DR_REQUIRE(given(6, 0), "null operand");
+      const dr_wm_loss_cfg cfg = {(float)num[0], (float)num[1], (float)num[2]};
+      return wm_window_scores(v[0], v[1], v[2], v[3], F(0), F(1), F(2), F(3), F(4), cfg, F(5), s);
+    }
+    case WL_GRU_BWD:
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1, "B, Hd must be positive");
+      DR_REQUIRE(v[2] >= v[1] && v[4] >= v[1] && (!ptrs[1] || v[3] >= v[1]), "row stride below Hd");
+      DR_REQUIRE(given(9, 1u << 1), "null operand");
+      return op_gru_bwd(v[0], v[1], F(0), v[2], F(1), v[3], F(2), F(3), F(4), F(5), F(6), F(7), F(8), v[4], v[5], s);
+    case WL_LN_SILU_BWD:
+      DR_REQUIRE(v[0] >= 1 && v[1] >= 1, "M, K must be positive");
+      DR_REQUIRE(v[2] >= v[1] && v[3] >= v[1] && v[4] >= v[1], "row stride below K");
+      DR_REQUIRE(given(8, 7u << 5), "null operand");
+      DR_REQUIRE(!ptrs[5] == !ptrs[6], "gy and xhat are written together: both or neither");
+      return op_ln_silu_bwd(v[0], v[1], F(0), v[2], F(1), v[3], F(2), F(3), F(4), v[4], F(5), F(6), s,
+                            (unsigned short*)ptrs[7]);
+    case WL_SOFTMAX_STE_BWD:
+      DR_REQUIRE(v[3] >= v[1] * v[2] && v[4] >= v[1] * v[2], "row stride below R * C");
+      DR_REQUIRE(given(3, 0), "null operand");
+      return op_softmax_ste_bwd(v[0], v[1], v[2], F(0), v[3], F(1), v[4], F(2), s);
+    case WL_COLSUM_MULTI: {
+      const int M = v[0], n = v[1], acc = v[2];
+      DR_REQUIRE(M >= 1 && n >= 1 && n <= DR_MAX_CSJOBS, "M must be positive, 1 to DR_MAX_CSJOBS jobs");
+      DR_REQUIRE(!acc || n == 1, "accumulate: one job (op_colsum)");
+      ColsumJob cj[DR_MAX_CSJOBS];
+      for (int j = 0; j < n; ++j) {
+        const int N = v[3 + 3 * j], ldx = v[4 + 3 * j], ldy = v[5 + 3 * j];
+        const float *X = F(3 * j), *Y = F(3 * j + 1);
+        float* out = F(3 * j + 2);
+        DR_REQUIRE(N >= 1 && X && out, "a job needs N >= 1, X and out");
+        DR_REQUIRE(ldx >= N && (!Y || ldy >= N), "row stride below N");
+        cj[j] = {N, X, ldx, Y, ldy, out};
+      }
+      if (acc) return op_colsum(M, cj[0].N, cj[0].X, cj[0].ldx, cj[0].Y, cj[0].ldy, cj[0].out, 1, s);
+      return op_colsum_multi(M, cj, n, s);
+    }
+  }
+  return DR_OK;
+}
+
+extern "C" int dr_internal_wm_loss_run(int op, const int* v, const double* num, void* const* ptrs, void* stream,
+                                       char* msg, int msg_cap) {
+  if (msg && msg_cap > 0) msg[0] = 0;
+  const int rc = wm_loss_run(op, v, num, ptrs, (hipStream_t)stream);
+  if (rc != DR_OK && msg && msg_cap > 0) snprintf(msg, msg_cap, "%s", dr_last_error());
+  return rc;
 }

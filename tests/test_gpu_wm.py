@@ -331,3 +331,68 @@ def test_wm_step_bf16_vs_fp32_oracle(gpu):
     assert abs(m["norm"][0] - m["norm"][1]) <= 5e-3 * m["norm"][1], m
     assert m["grad_all"] <= 1e-3, m
     assert worst[0][1] <= 0.1, m
+
+
+# ----------------------------------------------------------------------------
+# the KL path on its own: beta_pred = 0, so every gradient of the step is KL gradient
+# ----------------------------------------------------------------------------
+KL_BETAS = (0.0, 0.5, 0.1)
+
+
+def _run_kl_only(which, gpu):
+    """The fixture's step with the prediction loss off (step=False: gradients only, unclipped in p.grad)."""
+    fx = load_fixture(which + "_wm")
+    d, _ = build(which, gpu, fx)
+    wm = d.world_model
+    wm.beta_pred, wm.beta_dyn, wm.beta_rep = KL_BETAS
+    obs, act, rew, cont, T = window(fx)
+    wm.train_step_hip(obs.to(gpu), act.to(gpu), rew.to(gpu), cont.to(gpu), noise_q=_t(fx["q"], gpu), step=False)
+    torch.cuda.synchronize()
+    return fx, d, wm, (obs, act, rew, cont, T)
+
+
+def test_wm_kl_gradients_match_oracle_with_prediction_loss_off(gpu):
+    """`full` fixture windows (B = 3, T = 6, R = C = 32; KL 1.43, the free-bit clamp open) at betas (0, 0.5, 0.1):
+    the KL-dyn gradient of the prior and the KL-rep gradient of the posterior logits are all there is, so a wrong
+    factor or a missing term of either moves every tensor it reaches.  Every clipped gradient against the oracle's
+    step at the same betas, at the per-tensor band of the module doc (the fixture's stored gradients are for
+    beta_pred = 1 and are not used)."""
+    fx, d, wm, (obs, act, rew, cont, T) = _run_kl_only("full", gpu)
+    R, C = int(fx["cfg_rows"]), int(fx["cfg_cols"])
+    keys = [str(k) for k in fx["wm_keys"]]
+    P = fixture_params("full", fx)
+    for k in keys:
+        P[k] = P[k].clone().requires_grad_(True)
+    ref = O.wm_train_step(obs, act, rew, cont, P, _t(fx["q"]), R, C, T, keys, betas=KL_BETAS)
+    assert float(ref["kl_dyn"]) > 1.0 and float(ref["kl_rep"]) > 1.0  # the clamp is open: the gradient exists
+    ls = cpu(wm.last_losses)
+    for i, k in ((0, "total"), (1, "loss_pred"), (2, "kl_dyn"), (3, "kl_rep")):
+        r = float(ref[k])
+        assert abs(float(ls[i]) - r) <= 1e-4 * max(1.0, abs(r)), (k, float(ls[i]), r)
+    assert int(wm.last_skip.item()) == 0
+    named = dict(d.named_parameters())
+    # clip_grad_norm_(100) on the GPU's own gradients, as the fused optimiser step would
+    norm = float(torch.sqrt(sum(cpu(named[k].grad).double().pow(2).sum() for k in keys)))
+    assert abs(norm - float(ref["norm"])) <= 2e-4 * float(ref["norm"]), (norm, float(ref["norm"]))
+    coef = min(1.0, 100.0 / (norm + 1e-6))
+    n_live = 0
+    for k, g_ref in zip(keys, ref["grads_clipped"]):
+        atol = 2e-4 * max(float(g_ref.abs().max()), 1e-6)
+        close(cpu(named[k].grad) * coef, g_ref, 2e-3, atol, f"KL-only grad {k}")
+        n_live += int(float(g_ref.abs().max()) > 0)
+    print(f"KL-only step: gradient norm {norm:.6f} (oracle {float(ref['norm']):.6f}), {n_live}/{len(keys)} tensors "
+          f"with a KL gradient")
+    assert n_live > 0
+
+
+def test_wm_kl_gradients_vanish_under_the_free_bit_clamp(gpu):
+    """`small` fixture windows (KL 0.895: the clamp is shut) at the same betas: max(1, KL) is flat, so every gradient
+    is exactly 0.0, the loss is beta_dyn + beta_rep to float32, and the step is not skipped."""
+    fx, d, wm, _ = _run_kl_only("small", gpu)
+    ls = cpu(wm.last_losses)
+    assert float(ls[2]) < 1.0 and float(ls[3]) < 1.0
+    want = float(np.float32(KL_BETAS[1]) + np.float32(KL_BETAS[2]))
+    assert abs(float(ls[0]) - want) <= 2.0 ** -23 * want, (float(ls[0]), want)
+    assert int(wm.last_skip.item()) == 0
+    for n, p in d.world_model.named_parameters():
+        assert p.grad is not None and bool((p.grad == 0.0).all()), n
