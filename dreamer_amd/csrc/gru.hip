@@ -29,6 +29,10 @@ __global__ void k_transpose(int rows, int cols, const float* __restrict__ in, fl
 }
 
 int op_transpose(int rows, int cols, const float* in, float* out, hipStream_t s) {
+  if (rows <= 0 || cols <= 0) {
+    dr_set_error("transpose: rows and cols must be positive, got %d x %d", rows, cols);
+    return DR_E_INVALID;
+  }
   dim3 grid((cols + 31) / 32, (rows + 31) / 32);
   hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, s, rows, cols, in, out);
   return dr_check_launch("transpose");
@@ -63,6 +67,11 @@ int op_transpose_multi(const TransposeJob* jobs, int n, hipStream_t s) {
   TransposeBatch tb;
   int gx = 1, gy = 1;
   for (int i = 0; i < n; ++i) {
+    if (jobs[i].rows <= 0 || jobs[i].cols <= 0 || jobs[i].ldo < jobs[i].rows) {
+      dr_set_error("transpose_multi: job %d: rows and cols must be positive and ldo >= rows (%d x %d, ldo %d)", i,
+                   jobs[i].rows, jobs[i].cols, jobs[i].ldo);
+      return DR_E_INVALID;
+    }
     tb.j[i] = jobs[i];
     gx = std::max(gx, (jobs[i].cols + 31) / 32);
     gy = std::max(gy, (jobs[i].rows + 31) / 32);
@@ -97,6 +106,10 @@ __global__ void k_onehot_index(int M, int R, int C, const float* z, long long ld
 
 int op_onehot_index(int M, int R, int C, const float* z, long long ldz, int* idx, float* zval, hipStream_t s) {
   if (M * R == 0) return DR_OK;
+  if (M < 0 || R < 0 || C < 1) {
+    dr_set_error("onehot_index: M, R >= 0 and C >= 1 required (M=%d R=%d C=%d)", M, R, C);
+    return DR_E_INVALID;
+  }
   hipLaunchKernelGGL(k_onehot_index, dim3((M * R + 255) / 256), dim3(256), 0, s, M, R, C, z, ldz, idx, zval);
   return dr_check_launch("onehot_index");
 }

@@ -45,11 +45,6 @@ int op_actor_head_bwd_x(int M, int A, int N, const float* g_a, long long ldga, c
                         const float* g_sig_l, long long ldgl, const float* a, long long lda, const float* ls_raw,
                         long long ldl, const float* eps, float* g_heads, long long ldh, const float* wt, float* gx,
                         long long ldx, hipStream_t s);
-int op_actor_head_bwd(int M, int A, const float* g_a, long long ldga, const float* g_mu_l, const float* g_sig_l,
-                      long long ldgl, const float* a, long long lda, const float* sigma, long long lds,
-                      const float* ls_raw, long long ldl, const float* eps, float* g_heads, long long ldh,
-                      hipStream_t s);
-int op_conv_repack(int cout, int cin, const float* w, float* wr, hipStream_t s);
 int op_fill(long long n, float* x, float v, hipStream_t s);
 int op_copy2d(float* dst, long long dp, const float* src, long long sp, long long width, long long rows,
               hipStream_t s);

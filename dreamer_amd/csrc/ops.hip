@@ -64,6 +64,10 @@ int op_gru_fwd(int B, int Hd, const float* gi, const float* gh, const float* h, 
                long long ldo, float* sr, float* su, float* sn, float* sghn, hipStream_t s) {
   const long long n = (long long)B * Hd;
   if (n == 0) return DR_OK;
+  if (B < 0 || Hd < 0) {
+    dr_set_error("gru_fwd: negative dims B=%d Hd=%d", B, Hd);
+    return DR_E_INVALID;
+  }
   hipLaunchKernelGGL(k_gru_fwd, dim3(blocks_for(n, 256)), dim3(256), 0, s, B, Hd, gi, gh, h, ldh, hout, ldo, sr,
                      su, sn, sghn);
   return dr_check_launch("gru_fwd");
@@ -158,6 +162,10 @@ int op_sample(int M, int R, int C, const float* logits, long long ldl, const dr_
               long long ldz, int* idx, float* soft, long long lds, hipStream_t s) {
   if (C < 1 || C > 64) {
     dr_set_error("sample: latent classes must be in [1,64], got %d", C);
+    return DR_E_INVALID;
+  }
+  if (M < 0 || R < 0) {
+    dr_set_error("sample: negative dims M=%d R=%d", M, R);
     return DR_E_INVALID;
   }
   const int W = pow2_at_least(C);
@@ -467,6 +475,10 @@ __global__ void k_sigmoid(int M, const float* x, long long ldx, float* out, long
 
 int op_sigmoid(int M, const float* x, long long ldx, float* out, long long ostride, hipStream_t s) {
   if (M == 0) return DR_OK;
+  if (M < 0) {
+    dr_set_error("sigmoid: negative row count %d", M);
+    return DR_E_INVALID;
+  }
   hipLaunchKernelGGL(k_sigmoid, dim3(dr_cdiv(M, 256)), dim3(256), 0, s, M, x, ldx, out, ostride);
   return dr_check_launch("sigmoid");
 }
@@ -501,50 +513,18 @@ int op_actor_head(int M, int A, const float* mu_raw, long long ldm, const float*
                   const dr_noise* nz, int step, int deterministic, float* a, long long lda, float* mu,
                   long long ldmu, float* sigma, long long lds, float* eps_save, hipStream_t s) {
   if (M * A == 0) return DR_OK;
+  if (M < 0 || A < 0) {
+    dr_set_error("actor_head: negative dims M=%d A=%d", M, A);
+    return DR_E_INVALID;
+  }
   hipLaunchKernelGGL(k_actor_head, dim3(dr_cdiv(M * A, 256)), dim3(256), 0, s, M, A, mu_raw, ldm, ls_raw, ldl, *nz,
                      step, deterministic, a, lda, mu, ldmu, sigma, lds, eps_save);
   return dr_check_launch("actor_head");
 }
 
 // backward of a = tanh(mu + eps*sigma), sigma = softplus(clamp(ls)) + 1e-3,
-// plus the loss gradients on mu/sigma; g_heads [M][2A] = [g_mu | g_ls]
-__global__ void k_actor_head_bwd(int M, int A, const float* g_a, long long ldga, const float* g_mu_l,
-                                 const float* g_sig_l, long long ldgl, const float* a, long long lda,
-                                 const float* sigma, long long lds, const float* ls_raw, long long ldl,
-                                 const float* eps, float* g_heads, long long ldh) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= M * A) return;
-  const int m = i / A, k = i - m * A;
-  float gmu = g_mu_l ? g_mu_l[(long long)m * ldgl + k] : 0.0f;
-  float gsg = g_sig_l ? g_sig_l[(long long)m * ldgl + k] : 0.0f;
-  if (g_a) {
-    const float av = a[(long long)m * lda + k];
-    const float gp = g_a[(long long)m * ldga + k] * (1.0f - av * av);
-    gmu = gmu + gp;
-    gsg = gsg + gp * eps[i];
-  }
-  const float lr = ls_raw[(long long)m * ldl + k];
-  const float lc = fminf(fmaxf(lr, -5.0f), 2.0f);
-  float gls = 0.0f;
-  if (lr >= -5.0f && lr <= 2.0f) {
-    const float ez = expf(lc);
-    gls = (lc > 20.0f) ? gsg : gsg * ez / (ez + 1.0f);
-  }
-  g_heads[(long long)m * ldh + k] = gmu;
-  g_heads[(long long)m * ldh + A + k] = gls;
-}
-
-int op_actor_head_bwd(int M, int A, const float* g_a, long long ldga, const float* g_mu_l, const float* g_sig_l,
-                      long long ldgl, const float* a, long long lda, const float* sigma, long long lds,
-                      const float* ls_raw, long long ldl, const float* eps, float* g_heads, long long ldh,
-                      hipStream_t s) {
-  if (M * A == 0) return DR_OK;
-  hipLaunchKernelGGL(k_actor_head_bwd, dim3(dr_cdiv(M * A, 256)), dim3(256), 0, s, M, A, g_a, ldga, g_mu_l, g_sig_l,
-                     ldgl, a, lda, sigma, lds, ls_raw, ldl, eps, g_heads, ldh);
-  return dr_check_launch("actor_head_bwd");
-}
-
-// The same head backward fused with the input gradient of the stacked
+// plus the loss gradients on mu/sigma; g_heads [M][2A] = [g_mu | g_ls],
+// fused with the input gradient of the stacked
 // mu / log-sigma heads: gx[m][n] = sum_k g_heads[m][k] * wt[n][k] (wt = the
 // heads' weights transposed, [N][2A]).  A block owns 16 rows x 64 columns:
 // it forms the 16 x 2A head gradients in LDS (the blockIdx.x == 0 column of
@@ -607,8 +587,8 @@ int op_actor_head_bwd_x(int M, int A, int N, const float* g_a, long long ldga, c
                         long long ldl, const float* eps, float* g_heads, long long ldh, const float* wt, float* gx,
                         long long ldx, hipStream_t s) {
   if (M == 0) return DR_OK;
-  if (A > 8) {
-    dr_set_error("actor_head_bwd_x: at most 8 actions");
+  if (M < 0 || A < 1 || A > 8 || N < 1) {
+    dr_set_error("actor_head_bwd_x: 1 to 8 actions and N >= 1 (M=%d A=%d N=%d)", M, A, N);
     return DR_E_INVALID;
   }
   hipLaunchKernelGGL(k_actor_head_bwd_x, dim3(dr_cdiv(N, 64), dr_cdiv(M, 16)), dim3(256), 0, s, M, A, N, g_a, ldga,
@@ -890,6 +870,10 @@ __global__ __launch_bounds__(1024) void k_mean(int n, const float* x, float* out
 }
 
 int op_mean(int n, const float* x, float* out, hipStream_t s) {
+  if (n <= 0) {
+    dr_set_error("mean: n must be positive, got %d", n);
+    return DR_E_INVALID;
+  }
   hipLaunchKernelGGL(k_mean, dim3(1), dim3(1024), 0, s, n, x, out);
   return dr_check_launch("mean");
 }
@@ -1378,20 +1362,6 @@ int op_copy2d(float* dst, long long dp, const float* src, long long sp, long lon
   if (v4) hipLaunchKernelGGL(k_copy2d<true>, dim3(blocks), dim3(256), 0, s, dst, dp, src, sp, width, rows);
   else hipLaunchKernelGGL(k_copy2d<false>, dim3(blocks), dim3(256), 0, s, dst, dp, src, sp, width, rows);
   return dr_check_launch("copy2d");
-}
-
-// Conv2d weight [co][ci][4][4] -> [co][tap][ci] for NHWC implicit GEMM
-__global__ void k_conv_repack(int cout, int cin, const float* w, float* wr) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cout * cin * 16) return;
-  const int co = i / (cin * 16), rem = i - co * cin * 16;
-  const int ci = rem / 16, tap = rem - ci * 16;
-  wr[(long long)co * cin * 16 + tap * cin + ci] = w[i];
-}
-
-int op_conv_repack(int cout, int cin, const float* w, float* wr, hipStream_t s) {
-  hipLaunchKernelGGL(k_conv_repack, dim3(dr_cdiv(cout * cin * 16, 256)), dim3(256), 0, s, cout, cin, w, wr);
-  return dr_check_launch("conv_repack");
 }
 
 // Buffer.sample_sequences gather (Buffer.py:49-61): u8 frames -> f32 0..255
