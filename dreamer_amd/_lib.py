@@ -27,6 +27,13 @@ class dr_mlp3(C.Structure):
     _fields_ = [("l0", dr_linear), ("n1", dr_linear), ("l3", dr_linear), ("n4", dr_linear), ("l6", dr_linear)]
 
 
+DR_DISAG_MAX_MEMBERS = 16  # include/dreamer_hip.h: members of a dr_ensemble
+
+
+class dr_ensemble(C.Structure):
+    _fields_ = [("K", C.c_int), ("W", C.c_int), ("m", dr_mlp3 * DR_DISAG_MAX_MEMBERS)]
+
+
 class dr_dims(C.Structure):
     _fields_ = [(n, C.c_int) for n in (
         "hidden", "rows", "cols", "action", "img_h", "img_w", "enc_f1", "enc_f2", "enc_hidden",
@@ -161,6 +168,9 @@ _SIGS = {
     "dr_replay_probabilities": (_i, [_ll, _ll, _ll, _i, fp, _d, fp, fp, _sz, fp]),
     "dr_replay_priority_update": (_i, [_ll, _i, fp, fp, _d, _d, _d, _d, _d, fp, fp, fp]),
     "dr_wm_window_scores": (_i, [_P(dr_dims), _i, _i, dr_wm_loss_cfg, fp, _sz, fp, fp]),
+    "dr_disag_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "dr_disag_fwd": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, fp, fp, _i, _i, _ll, _ll, _f, _f, fp, _sz, fp]),
+    "dr_disag_train_grads": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, _ll, _P(dr_ensemble), fp, fp, _sz, fp]),
     "dr_rng_advance": (_i, [fp, C.c_ulonglong, fp]),
     "dr_persistent_kernels": (_i, [_P(dr_dims), _i, _i, _i]),
     "dr_stream_create_cumask": (_i, [_i, _P(C.c_uint), _P(fp)]),

@@ -112,6 +112,19 @@ class Dreamer(nn.Module):
         for k, v in REPLAY_DEFAULTS.items():
             setattr(buf, k, float(c.get(k, v)))
         check_replay(buf.replay, buf.replay_c, buf.replay_beta, buf.replay_alpha, buf.replay_eps, buf.replay_p_new)
+        # extra config keys: explore = "none" (default: nothing below exists) or
+        # "disagreement" -- Plan2Explore's ensemble; its disagreement on imagined states is added to the
+        # reward train_Agent learns from (engine.returns); Agent.train_step, the reference-API path, is left alone
+        from .networks import explore_config
+        ex = explore_config(c)
+        self.explore = ex["explore"]
+        if self.explore != "none":
+            from .networks import DisagreementEnsemble
+            self.explore_scale, self.explore_extrinsic = ex["explore_scale"], ex["explore_extrinsic"]
+            self.explorer = DisagreementEnsemble(
+                c["hidden_state_dims"], c["latent_state_dims"][0] * c["latent_state_dims"][1], ex["explore_ensemble"],
+                ex["explore_width"], ex["explore_lr"], tuple(c["world_model_betas"]), c["world_model_eps"],
+                seed=c["seed"], device=device)
         self.device = device
         self.agent_obs = None
         self.agent_hidden = None
@@ -422,6 +435,24 @@ class Dreamer(nn.Module):
         from .saliency import evaluate_saliency
         return evaluate_saliency(self, batches=batches, batch_size=batch_size, length=length, steps=steps, **kw)
 
+    # ------------------------------------------------------- exploration read-outs
+    def disagreement(self, hidden):
+        """Ensemble disagreement of hidden states: any (..., hidden) device tensor -> (...).  Needs explore =
+        "disagreement"."""
+        return self._explorer().disagreement(hidden)
+
+    def novelty(self, starts=None, batch_size=None, length=None):
+        """Per-step disagreement of the posterior filter's hidden states on replay windows (where the ensemble has
+        seen too little data): see dreamer_amd/novelty.py.  Needs explore = "disagreement"."""
+        from .novelty import novelty
+        return novelty(self, starts=starts, batch_size=batch_size, length=length)
+
+    def evaluate_novelty(self, batches=1, batch_size=None, length=None):
+        """novelty over `batches` batches of windows drawn without disturbing the training run's random state, like
+        the other evaluate_*; returns the mean per-step disagreement (length,) and its overall mean."""
+        from .novelty import evaluate_novelty
+        return evaluate_novelty(self, batches=batches, batch_size=batch_size, length=length)
+
     # --------------------------------------------------------------- training
     @property
     def engine(self):
@@ -433,7 +464,10 @@ class Dreamer(nn.Module):
     def train_Agent(self):
         """Dreamer.train_Agent (Dreamer.py:264-287): AC_epochs fused epochs.
         replay = "curious": the starts come from the device sampler (the
-        sequential epoch loop; priorities and visits are not touched)."""
+        sequential epoch loop; priorities and visits are not touched).
+        explore = "disagreement": the epochs learn from explore_extrinsic * reward +
+        explore_scale * disagreement (engine.returns)."""
+        self._exploring()  # (ValueError under data parallelism)
         if self._curious():
             return self._train_agent_curious()
         if self.AC_epochs > 1 and self.pipeline_epochs and not self.engine.persistent_chain():
@@ -484,20 +518,45 @@ class Dreamer(nn.Module):
             lc.append(c.clone())
         return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
 
+    def _exploring(self):
+        """True with explore = "disagreement" (ValueError under data parallelism: the ensemble's gradients have no
+        all-reduce)."""
+        if self.explore == "none":
+            return False
+        if self.world is not None or self.world_model._dp is not None:
+            raise ValueError("explore = 'disagreement' is not supported under data parallelism")
+        return True
+
+    def _explorer(self):
+        if not self._exploring():
+            raise RuntimeError("this Dreamer has no disagreement ensemble: set the config key explore = 'disagreement'")
+        return self.explorer
+
+    def _train_explorer(self, outputs):
+        """One ensemble step on rows t >= 1 of the world-model step's posterior trace (time-major copies the step
+        handed out: the world model's own launches, and so its bits, are what they are without exploration)."""
+        self.explorer.train_step(outputs["hiddens"][1:], outputs["latents"][1:])
+
     def train_world_model(self):  # Dreamer.py:228-242
         out = []
+        explore = self._exploring()
+        trace = {} if explore else None
         if self._curious():
             # per epoch: device sample -> step with per-window scores -> priority update; no host round trip
             for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
                 starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
-                out.append(self.world_model.train_step_ring(self.buffer, starts, scores=True))
+                out.append(self.world_model.train_step_ring(self.buffer, starts, scores=True, outputs=trace))
                 self.buffer.update_priorities(starts, self.world_model.last_window_scores)
+                if explore:
+                    self._train_explorer(trace)
             return out
         for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
             if self.device.type == "cuda":
                 # same np.random draws as sample_sequences; frames stay u8 in HBM
                 starts = self.buffer.sample_start_indices(self.batch_size)
-                out.append(self.world_model.train_step_ring(self.buffer, starts))
+                out.append(self.world_model.train_step_ring(self.buffer, starts, outputs=trace))
+                if explore:
+                    self._train_explorer(trace)
             else:
                 obs, act, rew, cont, _ = self.buffer.sample_sequences(batch_size=self.batch_size)
                 out.append(self.world_model.training_step(obs, act, rew, cont))
@@ -550,6 +609,9 @@ class Dreamer(nn.Module):
         if buf.replay != "uniform":  # prioritised replay: the per-slot state (uniform mode: exactly the keys above)
             m = buf._mirror()
             st["buffer"].update(priority=cpu(m["priority"]), visits=cpu(m["visits"]))
+        if self.explore != "none":  # the ensemble's AdamW state (its weights are in "model"); absent otherwise
+            self.explorer._ensure_flat()
+            st["opt_explorer"] = opt(self.explorer.optimiser)
         return st
 
     def save_training_state(self, path):
@@ -559,11 +621,17 @@ class Dreamer(nn.Module):
         st = path_or_state if isinstance(path_or_state, dict) else torch.load(path_or_state, weights_only=True)
         if st.get("format") != self.TRAINING_STATE_FORMAT:
             raise ValueError(f"not a {self.TRAINING_STATE_FORMAT} file: {st.get('format')!r}")
+        if self.explore != "none" and "opt_explorer" not in st:
+            raise ValueError("the training state was saved without exploration: it has no ensemble optimiser state")
         self.load_state_dict({k: v.to(self.device) for k, v in st["model"].items()})
         ag, wm, buf = self.agent, self.world_model, self.buffer
         ag._ensure_flat()
         wm._ensure_flat()
-        for o, k in ((ag.actor_optimiser, "opt_actor"), (ag.critic_optimiser, "opt_critic"), (wm.optimiser, "opt_wm")):
+        opts = [(ag.actor_optimiser, "opt_actor"), (ag.critic_optimiser, "opt_critic"), (wm.optimiser, "opt_wm")]
+        if self.explore != "none":
+            self.explorer._ensure_flat()
+            opts.append((self.explorer.optimiser, "opt_explorer"))
+        for o, k in opts:
             o.exp_avg.copy_(st[k]["exp_avg"])
             o.exp_avg_sq.copy_(st[k]["exp_avg_sq"])
             o.step_dev.copy_(st[k]["step"])

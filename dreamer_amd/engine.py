@@ -87,6 +87,12 @@ class ImaginationEngine:
         # inside the epoch graph (~6 % slower replays, r01_ab_overlap.txt).
         self.side = torch.cuda.Stream(self.dev)
         self.chunks = [(0, self.T)]
+        # explore = "disagreement" (DESIGN.md 5o): the ensemble whose disagreement returns() adds to the rewards
+        self.explorer = dreamer.explorer if getattr(dreamer, "explore", "none") != "none" else None
+        if self.explorer is not None and world is not None:
+            raise ValueError("explore = 'disagreement' is not supported under data parallelism")
+        if self.explorer is not None:
+            self.explorer._ensure_flat()  # (before the first capture: the graphs hold the flat buffer's addresses)
         self._alloc()
     # ------------------------------------------------------------------ setup
     @staticmethod
@@ -137,6 +143,10 @@ class ImaginationEngine:
         # beside the target critic and the BPTT (run_many): own workspace
         self.ws_cr2 = hip.workspace(dev).get("e_cr2", L.query("dr_critic_workspace_bytes", d, B, H))
         self.rng = hip.rng(dev)
+        if self.explorer is not None:  # own scratch, not the grow-only named one: the phase graphs keep its address
+            ex = self.explorer
+            n = L.query("dr_disag_workspace_bytes", ex.members, ex.width, d.hidden, L_, M, 0)
+            self.ws_disag = torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------- the phases
     def encode_and_warm(self, frames, noise_q=None):
@@ -170,10 +180,18 @@ class ImaginationEngine:
                L.ptr(self.sigmas), L.ptr(self.tape), L.ptr(self.ws_im), self.ws_im.numel(), hip.stream())
 
     def returns(self):
-        """target-critic values and lambda returns (Agent.py:156-172)."""
+        """target-critic values and lambda returns (Agent.py:156-172); with exploration on, the intrinsic reward
+        first."""
         ag, d, st = self.dr.agent, self.d, hip.stream()
         M = self.B * (self.H + 1)
         L_ = d.rows * d.cols
+        if self.explorer is not None:
+            # r' = explore_extrinsic r + explore_scale d(h) in place, before anything reads the rewards: the
+            # ensemble over all B (H + 1) hidden states; rewards[b][t] belongs to hiddens[b][t + 1] (dr_imagine_fwd)
+            dr = self.dr
+            L.call("dr_disag_fwd", self.explorer.struct(), d.hidden, L_, M, L.ptr(self.hiddens), d.hidden, None, None,
+                   L.ptr(self.rewards), self.H + 1, 1, self.H, 1, dr.explore_extrinsic, dr.explore_scale,
+                   L.ptr(self.ws_disag), self.ws_disag.numel(), st)
         L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(self.hiddens), d.hidden,
                L.ptr(self.latents), L_, None, L.ptr(self.V_t), None, L.ptr(self.ws_cr), self.ws_cr.numel(), st)
         L.call("dr_lambda_returns", self.B, self.H, L.ptr(self.rewards), L.ptr(self.continues), L.ptr(self.V_t),
@@ -437,6 +455,13 @@ class ImaginationEngine:
         ag.loss_buffer.div_(self.wsize)
 
     # ----------------------------------------------------------------- driver
+    def _graph_key(self):
+        """What the captured graphs hold pointers to: a change means a new capture."""
+        key = (self.dr.agent.params_key(), self.dr.world_model.params_key(), self.dr.buffer.device_key())
+        if self.explorer is not None:
+            key += (self.explorer.params_key(), self.dr.explore_extrinsic, self.dr.explore_scale)
+        return key
+
     def run(self, starts_np, timing=False):
         """One train_Agent epoch from host window starts; returns the device
         loss slots (actor, critic).  With timing=True, HIP events bracket every
@@ -458,7 +483,7 @@ class ImaginationEngine:
             self.copy_ev[i].record()
         self.epochs += 1
         ag = self.dr.agent
-        key = (ag.params_key(), self.dr.world_model.params_key(), self.dr.buffer.device_key())
+        key = self._graph_key()
         if self.use_graph and (self.graph is None or self.graph_key != key):
             self._capture(key)
         evs = [torch.cuda.Event(enable_timing=True)] if timing else None
@@ -587,7 +612,7 @@ class ImaginationEngine:
         above).  Returns a [K, 2] device tensor of (actor, critic) losses."""
         self.check_faults(wait=False)
         ag = self.dr.agent
-        key = (ag.params_key(), self.dr.world_model.params_key(), self.dr.buffer.device_key())
+        key = self._graph_key()
         P = self._pipe_capture(key)
         G = P["graphs"]
         outer = torch.cuda.current_stream(self.dev)

@@ -387,3 +387,158 @@ class Decoder(nn.Module):
 
     def decode(self, hidden_state, latent_state):
         return self.forward(hidden_state, latent_state)
+
+
+EXPLORE_DEFAULTS = dict(explore="none", explore_ensemble=8, explore_width=None, explore_scale=0.1,
+                        explore_extrinsic=1.0, explore_lr=None)
+
+
+def explore_config(c):
+    """The exploration keys of a config with their defaults, validated: explore "none" |
+    "disagreement", explore_ensemble K in 1..16, explore_width W >= 1 (default dyn_pred_hidden_num_nodes_1),
+    explore_scale / explore_extrinsic >= 0, explore_lr > 0 (default world_model_lr)."""
+    e = {k: c.get(k, v) for k, v in EXPLORE_DEFAULTS.items()}
+    if e["explore_width"] is None:
+        e["explore_width"] = c["dyn_pred_hidden_num_nodes_1"]
+    if e["explore_lr"] is None:
+        e["explore_lr"] = c["world_model_lr"]
+    if e["explore"] not in ("none", "disagreement"):
+        raise ValueError(f"explore must be 'none' or 'disagreement', got {e['explore']!r}")
+    K, W = e["explore_ensemble"], e["explore_width"]
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= L.DR_DISAG_MAX_MEMBERS:
+        raise ValueError(f"explore_ensemble must be an integer in 1..{L.DR_DISAG_MAX_MEMBERS}, got {K!r}")
+    if not isinstance(W, int) or isinstance(W, bool) or W < 1:
+        raise ValueError(f"explore_width must be a positive integer, got {W!r}")
+    for k in ("explore_scale", "explore_extrinsic"):
+        e[k] = float(e[k])
+        if not e[k] >= 0.0 or e[k] == float("inf"):
+            raise ValueError(f"{k} must be a finite number >= 0, got {e[k]!r}")
+    e["explore_lr"] = float(e["explore_lr"])
+    if not 0.0 < e["explore_lr"] < float("inf"):
+        raise ValueError(f"explore_lr must be a finite number > 0, got {e['explore_lr']!r}")
+    return e
+
+
+class DisagreementEnsemble(nn.Module):
+    """Plan2Explore's latent-disagreement ensemble (Sekar et al. 2020) in the form of DreamerV3's expl.Disag with
+    disag_target = stoch: K members Linear(hidden -> W) LN SiLU Linear(W -> W) LN SiLU Linear(W -> L), each predicting
+    the posterior sample z_t (0/1 floats, L = rows * cols) from h_t alone -- h_t = GRU(h_{t-1}, z_{t-1}, a_{t-1}) is
+    a function of Plan2Explore's (h, z, a) input.  Every member sees every row; they differ by initialisation only.
+    The members' parameters are stacked along a leading K axis (the first layer as one (K W, hidden) weight: one
+    product for all members).  Initialised like nn.Linear / nn.LayerNorm from a PRIVATE generator seeded from `seed`:
+    constructing it draws nothing from torch's, numpy's or the Philox generators.  f32 in both precision modes.
+    No reference definition: the reference learns from the environment's reward alone."""
+
+    def __init__(self, hidden, latent, members, width, lr, betas, eps, weight_decay=1e-6, seed=0, device="cpu"):
+        super().__init__()
+        K, W, Hd, Lt = int(members), int(width), int(hidden), int(latent)
+        self.members, self.width, self.hidden, self.latent = K, W, Hd, Lt
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed((int(seed) * 0x9E3779B1 + 0x5D15A6) & (2 ** 63 - 1))
+
+        def uni(fan_in, *shape):  # nn.Linear's default: U(-1/sqrt(fan_in), 1/sqrt(fan_in)) for weight and bias
+            b = 1.0 / fan_in ** 0.5
+            return nn.Parameter(((torch.rand(*shape, generator=gen) * 2.0 - 1.0) * b).to(device))
+
+        self.l0_weight, self.l0_bias = uni(Hd, K * W, Hd), uni(Hd, K * W)
+        self.n1_weight = nn.Parameter(torch.ones(K, W, device=device))
+        self.n1_bias = nn.Parameter(torch.zeros(K, W, device=device))
+        self.l3_weight, self.l3_bias = uni(W, K, W, W), uni(W, K, W)
+        self.n4_weight = nn.Parameter(torch.ones(K, W, device=device))
+        self.n4_bias = nn.Parameter(torch.zeros(K, W, device=device))
+        self.l6_weight, self.l6_bias = uni(W, K, Lt, W), uni(W, K, Lt)
+        self._opt = (float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay))
+        self._flat = None
+        self.optimiser = None
+        self.last_losses = None  # device [total, loss_0 .. loss_{K-1}] of the last train_step
+        self.last_skip = None
+        self._scratch = None
+
+    def _ensure_flat(self):
+        """Parameters as views of one flat buffer with the fused AdamW over it (WorldModel._ensure_flat)."""
+        from .agent import FlatAdamW, _Flat
+        if self._flat is not None and self._flat.intact():
+            return self._flat
+        self._flat = _Flat(self)
+        self.optimiser = FlatAdamW(self._flat, *self._opt)
+        return self._flat
+
+    def params_key(self):
+        return tuple(p.data_ptr() for p in self.parameters())
+
+    def struct(self, grad=False):
+        """dr_ensemble over the parameters (grad=True: over their .grad views in the flat gradient buffer)."""
+        K, W, Hd, Lt = self.members, self.width, self.hidden, self.latent
+        e = L.dr_ensemble()
+        e.K, e.W = K, W
+        t = (lambda p: p.grad) if grad else (lambda p: p)
+        base = {n: L.ptr(t(getattr(self, n))) for n in ("l0_weight", "l0_bias", "n1_weight", "n1_bias", "l3_weight",
+                                                       "l3_bias", "n4_weight", "n4_bias", "l6_weight", "l6_bias")}
+        per = dict(l0_weight=W * Hd, l0_bias=W, n1_weight=W, n1_bias=W, l3_weight=W * W, l3_bias=W, n4_weight=W,
+                   n4_bias=W, l6_weight=Lt * W, l6_bias=Lt)
+        at = lambda n, k: base[n] + 4 * k * per[n]
+        for k in range(K):
+            e.m[k] = L.dr_mlp3(*(L.dr_linear(at(a + "_weight", k), at(a + "_bias", k))
+                                 for a in ("l0", "n1", "l3", "n4", "l6")))
+        return e
+
+    def _ws(self, M, train):
+        n = L.query("dr_disag_workspace_bytes", self.members, self.width, self.hidden, self.latent, M, int(train))
+        return hip.workspace(self.l0_weight.device).get("disag_train" if train else "disag", n)
+
+    def forward_rows(self, h_rows, predictions=False):
+        """h_rows (M, hidden) on the device -> disagreement (M,) (and the predictions (K, M, L))."""
+        L.require_gpu(h_rows)
+        h = h_rows.detach().float()
+        if h.stride(-1) != 1:
+            h = h.contiguous()
+        M = h.shape[0]
+        d = torch.empty(M, device=h.device)
+        pred = torch.empty(self.members, M, self.latent, device=h.device) if predictions else None
+        if M == 0:
+            return (d, pred) if predictions else d
+        ws = self._ws(M, False)
+        L.call("dr_disag_fwd", self.struct(), self.hidden, self.latent, M, L.ptr(h), h.stride(0), L.ptr(pred),
+               L.ptr(d), None, 0, 0, 0, 0, 0.0, 0.0, L.ptr(ws), ws.numel(), hip.stream())
+        return (d, pred) if predictions else d
+
+    def disagreement(self, hidden):
+        """Any (..., hidden) device tensor -> (...) disagreement: the mean over the latent's columns of the members'
+        population std (include/dreamer_hip.h, dr_disag_fwd)."""
+        if hidden.shape[-1] != self.hidden:
+            raise ValueError(f"hidden states must end in {self.hidden} features, got {tuple(hidden.shape)}")
+        return self.forward_rows(hidden.reshape(-1, self.hidden)).view(hidden.shape[:-1])
+
+    def grads(self, h_rows, z_rows):
+        """dr_disag_train_grads on rows of (h, z): the flat gradient buffer and last_losses; no update."""
+        L.require_gpu(h_rows)
+        f = self._ensure_flat()
+        h = h_rows.detach().reshape(-1, self.hidden).float()
+        z = z_rows.detach().reshape(h.shape[0], self.latent).float()
+        h = h if h.stride(-1) == 1 else h.contiguous()
+        z = z if z.stride(-1) == 1 else z.contiguous()
+        M, dev = h.shape[0], h.device
+        if self._scratch is None or self._scratch[0].device != dev:
+            self._scratch = (torch.zeros(1 + self.members, device=dev), torch.zeros(1, dtype=torch.int32, device=dev),
+                             torch.zeros(1, device=dev), torch.empty(512, device=dev))
+        losses = self._scratch[0]
+        ws = self._ws(M, True)
+        L.call("dr_disag_train_grads", self.struct(), self.hidden, self.latent, M, L.ptr(h), h.stride(0), L.ptr(z),
+               z.stride(0), self.struct(grad=True), L.ptr(losses), L.ptr(ws), ws.numel(), hip.stream())
+        self.last_losses = losses
+        return f
+
+    def train_step(self, h_rows, z_rows):
+        """One update on rows of (h_t, z_t), both detached: the gradients, then the world model's sequence -- no
+        update when a gradient is non-finite, clip_grad_norm_(100), fused AdamW.  Returns the loss as a 0-d device
+        tensor (no host sync)."""
+        f = self.grads(h_rows, z_rows)
+        losses, skip, sq, sq_part = self._scratch
+        st = hip.stream()
+        skip.zero_()
+        L.call("dr_nonfinite", f.numel, f.grad.data_ptr(), skip.data_ptr(), st)
+        sq.zero_()
+        L.call("dr_sqnorm_multi", f.numel, f.grad.data_ptr(), sq.data_ptr(), sq_part.data_ptr(), st)
+        self.optimiser.fused_step(sqnorm=sq, max_norm=100.0, skip=skip)
+        self.last_skip = skip
+        return losses[0].clone()

@@ -949,6 +949,56 @@ int dr_replay_priority_update(long long cap, int B, const long long* starts, con
                               double beta, double alpha, double eps, double p_new, float* priority, int* visits,
                               hipStream_t stream);
 
+/* ---- latent-disagreement ensemble (Plan2Explore, Sekar et al. 2020, in the
+ *      form of DreamerV3's expl.Disag; config key explore = "disagreement",
+ *      DESIGN.md 5o).  No reference definition: the reference learns from the
+ *      environment's reward alone.
+ * K members, each a dr_mlp3 Linear(Hd -> W) LN SiLU Linear(W -> W) LN SiLU
+ * Linear(W -> L) on a hidden state h alone; L = rows * cols.  Always f32, in
+ * both precision modes.  The members' l0 parameters are contiguous:
+ *   m[k].l0.w = m[0].l0.w + k W Hd,  m[k].l0.b = m[0].l0.b + k W
+ * (the first layer of all members is one product with N = K W); the same holds
+ * for a gradient dr_ensemble.  Checked; DR_E_INVALID otherwise.
+ * Predictions p_k = m[k](h) [M][L].  Disagreement of a row:
+ *   mu_j = (1/K) sum_k p_kj,  d = (1/L) sum_j sqrt((1/K) sum_k (p_kj - mu_j)^2)
+ * (population std over the members, mean over the columns).  The deviations are
+ * taken from member 0 (dev_k = p_kj - p_0j, minus their mean), scaled by a
+ * power of two before they are squared: d is exactly 0 where the members agree
+ * (for every K, and for K = 1), never negative, does not lose small or large
+ * magnitudes to the squares, and a NaN / Inf prediction makes its row's d
+ * non-finite and no other row's.  One wave per row, columns lane-strided in
+ * ascending order, a fixed wave tree: the same bits on every run.
+ * Loss (training): loss_k = mean over rows and columns of (p_k - z)^2,
+ * loss = mean_k loss_k; dL/dp_k = 2 (p_k - z) / (K M L) (exactly 0 where
+ * p_k == z).  Sums in a fixed order, no float atomics. */
+#define DR_DISAG_MAX_MEMBERS 16
+typedef struct {
+  int K, W;                          /* members (1 .. 16), width of both hidden layers */
+  dr_mlp3 m[DR_DISAG_MAX_MEMBERS];   /* m[k], k < K */
+} dr_ensemble;
+/* train = 0: dr_disag_fwd's scratch; 1: dr_disag_train_grads'. */
+size_t dr_disag_workspace_bytes(int K, int W, int Hd, int L, int M, int train);
+/* h [M] rows of Hd floats, ldh apart.  pred_out [K][M][L] and disag_out [M]
+ * may be NULL.  Reward update (rew may be NULL): for row m with b = m / rew_T,
+ * t = m % rew_T and t >= rew_skip,
+ *   rew[b rew_sb + (t - rew_skip) rew_st] = w_ext * rew[..] + w_int * d_m
+ * in place (two products and one sum, each rounded); rew_T = 0: every row m
+ * updates rew[m rew_st].  The engine passes its hiddens [B][H+1][Hd] with
+ * rew_T = H + 1, rew_skip = 1 and its rewards [B][H]: rewards[b][t] is the
+ * reward head's value on hiddens[b][t+1] (dr_imagine_fwd).  Plain launches on
+ * `stream` (the shared first layer, 2 ceil(K / 4) grouped products, the row
+ * kernel), capturable. */
+int dr_disag_fwd(const dr_ensemble* e, int Hd, int L, int M, const float* h, long long ldh, float* pred_out,
+                 float* disag_out, float* rew, int rew_T, int rew_skip, long long rew_sb, long long rew_st,
+                 float w_ext, float w_int, void* ws, size_t ws_bytes, hipStream_t stream);
+/* Forward on M rows of h, the loss against z (rows of L floats, ldz apart; the
+ * posterior samples as 0/1 floats) and the gradient of every weight, bias and
+ * LayerNorm parameter into g (overwritten; no input gradient exists).
+ * losses [1 + K]: the total, then loss_k. */
+int dr_disag_train_grads(const dr_ensemble* e, int Hd, int L, int M, const float* h, long long ldh, const float* z,
+                         long long ldz, const dr_ensemble* g, float* losses, void* ws, size_t ws_bytes,
+                         hipStream_t stream);
+
 /* Which parts of a train_Agent epoch (Dreamer.py:264-287) run as ONE persistent
  * launch for these dims and shapes (the stream's CU mask aside): bit 0 the warm
  * start's posterior scan over T steps (Dreamer.py:255-261), bit 1 the
