@@ -171,6 +171,10 @@ _SIGS = {
     "dr_disag_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dr_disag_fwd": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, fp, fp, _i, _i, _ll, _ll, _f, _f, fp, _sz, fp]),
     "dr_disag_train_grads": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, _ll, _P(dr_ensemble), fp, fp, _sz, fp]),
+    "dr_knn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "dr_knn": (_i, [_i, _i, _i, fp, _ll, fp, _i, fp, _ll, fp, fp, fp, fp, _sz, fp]),
+    "dr_state_entropy_fwd": (_i, [_i, _i, _i, fp, _ll, fp, _i, fp, _ll, fp, fp, fp, fp, fp, _i, _i, _ll, _ll, _f, _f,
+                                  fp, _sz, fp]),
     "dr_rng_advance": (_i, [fp, C.c_ulonglong, fp]),
     "dr_persistent_kernels": (_i, [_P(dr_dims), _i, _i, _i]),
     "dr_stream_create_cumask": (_i, [_i, _P(C.c_uint), _P(fp)]),
@@ -227,7 +231,8 @@ DR_PLAN_MAX_CANDIDATES = 2048  # include/dreamer_hip.h: candidates per environme
 DR_ENSEMBLE_MAX_SAMPLES = 64  # include/dreamer_hip.h: futures per window of dr_ensemble_metrics
 DR_DREAM_STATS_MAX_DREAMS = 64  # include/dreamer_hip.h: dreams per window of dr_dream_stats (= DR_ENSEMBLE_MAX_SAMPLES)
 DR_DREAM_STATS_MAX_LDS_FLOATS = 15360  # include/dreamer_hip.h: (M | 1) * (3 H + 2) of one dr_dream_stats window
-DR_PLAN_MAX_ELEMS = 1024  # include/dreamer_hip.h: H * A of one planned action sequence
+DR_KNN_MAX_K = 32  # include/dreamer_hip.h: neighbours per query of dr_knn / dr_state_entropy_fwd
+DR_PLAN_MAX_ELEMS = 1024 # include/dreamer_hip.h: H * A of one planned action sequence
 DR_SALIENCY_MAX_CELLS = 1024  # include/dreamer_hip.h: cells of one frame's saliency grid
 DR_SALIENCY_MAX_RADIUS = 15  # include/dreamer_hip.h: widest blur radius of dr_occlude_frames
 

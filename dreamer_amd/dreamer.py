@@ -118,9 +118,13 @@ class Dreamer(nn.Module):
         from .networks import explore_config
         ex = explore_config(c)
         self.explore = ex["explore"]
+        # "entropy" (DESIGN.md 5p): the particle-entropy reward of the imagined states among themselves; no module,
+        # parameter, optimiser or state of its own
+        self.explore_knn, self.explore_knn_exclude = ex["explore_knn"], ex["explore_knn_exclude"]
         if self.explore != "none":
-            from .networks import DisagreementEnsemble
             self.explore_scale, self.explore_extrinsic = ex["explore_scale"], ex["explore_extrinsic"]
+        if self.explore == "disagreement":
+            from .networks import DisagreementEnsemble
             self.explorer = DisagreementEnsemble(
                 c["hidden_state_dims"], c["latent_state_dims"][0] * c["latent_state_dims"][1], ex["explore_ensemble"],
                 ex["explore_width"], ex["explore_lr"], tuple(c["world_model_betas"]), c["world_model_eps"],
@@ -441,9 +445,25 @@ class Dreamer(nn.Module):
         "disagreement"."""
         return self._explorer().disagreement(hidden)
 
+    def knn(self, queries, bank=None, k=None, query_groups=None, bank_groups=None):
+        """k nearest neighbours (include/dreamer_hip.h, dr_knn) of any device tensors (..., D): (dist (..., k)
+        Euclidean, not squared; idx (..., k) int32 rows of the flattened bank, -1 / inf past the eligible rows).
+        bank = None: the queries among themselves, a row never its own neighbour.  Groups are int tensors of the
+        rows' shapes: a bank row of the query's group is not eligible.  k defaults to explore_knn.  Works in every
+        explore mode."""
+        from .novelty import knn
+        return knn(queries, bank, self.explore_knn if k is None else k, query_groups, bank_groups)
+
+    def state_entropy(self, hidden, k=None):
+        """Particle-entropy reward log1p(mean distance to the k nearest other rows) of hidden states among
+        themselves: any (..., hidden) device tensor -> (...) (dr_state_entropy_fwd).  Works in every explore mode."""
+        from .novelty import state_entropy
+        return state_entropy(hidden, self.explore_knn if k is None else k)
+
     def novelty(self, starts=None, batch_size=None, length=None):
         """Per-step disagreement of the posterior filter's hidden states on replay windows (where the ensemble has
-        seen too little data): see dreamer_amd/novelty.py.  Needs explore = "disagreement"."""
+        seen too little data): see dreamer_amd/novelty.py.  Needs explore = "disagreement", or "entropy": then the
+        per-step entropy reward of the hidden states among the B * length states of the batch."""
         from .novelty import novelty
         return novelty(self, starts=starts, batch_size=batch_size, length=length)
 
@@ -519,13 +539,13 @@ class Dreamer(nn.Module):
         return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
 
     def _exploring(self):
-        """True with explore = "disagreement" (ValueError under data parallelism: the ensemble's gradients have no
-        all-reduce)."""
+        """True with explore = "disagreement" (ValueError under data parallelism in either exploring mode: the
+        ensemble's gradients have no all-reduce, the entropy's bank would be one rank's states)."""
         if self.explore == "none":
             return False
         if self.world is not None or self.world_model._dp is not None:
-            raise ValueError("explore = 'disagreement' is not supported under data parallelism")
-        return True
+            raise ValueError(f"explore = {self.explore!r} is not supported under data parallelism")
+        return self.explore == "disagreement"
 
     def _explorer(self):
         if not self._exploring():
@@ -609,7 +629,7 @@ class Dreamer(nn.Module):
         if buf.replay != "uniform":  # prioritised replay: the per-slot state (uniform mode: exactly the keys above)
             m = buf._mirror()
             st["buffer"].update(priority=cpu(m["priority"]), visits=cpu(m["visits"]))
-        if self.explore != "none":  # the ensemble's AdamW state (its weights are in "model"); absent otherwise
+        if self.explore == "disagreement":  # the ensemble's AdamW state (its weights are in "model"); absent otherwise
             self.explorer._ensure_flat()
             st["opt_explorer"] = opt(self.explorer.optimiser)
         return st
@@ -621,14 +641,14 @@ class Dreamer(nn.Module):
         st = path_or_state if isinstance(path_or_state, dict) else torch.load(path_or_state, weights_only=True)
         if st.get("format") != self.TRAINING_STATE_FORMAT:
             raise ValueError(f"not a {self.TRAINING_STATE_FORMAT} file: {st.get('format')!r}")
-        if self.explore != "none" and "opt_explorer" not in st:
+        if self.explore == "disagreement" and "opt_explorer" not in st:
             raise ValueError("the training state was saved without exploration: it has no ensemble optimiser state")
         self.load_state_dict({k: v.to(self.device) for k, v in st["model"].items()})
         ag, wm, buf = self.agent, self.world_model, self.buffer
         ag._ensure_flat()
         wm._ensure_flat()
         opts = [(ag.actor_optimiser, "opt_actor"), (ag.critic_optimiser, "opt_critic"), (wm.optimiser, "opt_wm")]
-        if self.explore != "none":
+        if self.explore == "disagreement":
             self.explorer._ensure_flat()
             opts.append((self.explorer.optimiser, "opt_explorer"))
         for o, k in opts:

@@ -88,9 +88,12 @@ class ImaginationEngine:
         self.side = torch.cuda.Stream(self.dev)
         self.chunks = [(0, self.T)]
         # explore = "disagreement" (DESIGN.md 5o): the ensemble whose disagreement returns() adds to the rewards
-        self.explorer = dreamer.explorer if getattr(dreamer, "explore", "none") != "none" else None
-        if self.explorer is not None and world is not None:
-            raise ValueError("explore = 'disagreement' is not supported under data parallelism")
+        mode = getattr(dreamer, "explore", "none")
+        self.explorer = dreamer.explorer if mode == "disagreement" else None
+        # explore = "entropy" (DESIGN.md 5p): the particle-entropy reward of the B (H + 1) imagined states
+        self.entropy = mode == "entropy"
+        if mode != "none" and world is not None:
+            raise ValueError(f"explore = {mode!r} is not supported under data parallelism")
         if self.explorer is not None:
             self.explorer._ensure_flat()  # (before the first capture: the graphs hold the flat buffer's addresses)
         self._alloc()
@@ -147,6 +150,11 @@ class ImaginationEngine:
             ex = self.explorer
             n = L.query("dr_disag_workspace_bytes", ex.members, ex.width, d.hidden, L_, M, 0)
             self.ws_disag = torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
+        if self.entropy:  # own scratch like ws_disag; the group ids are built once
+            row = torch.arange(M, dtype=torch.int32, device=dev)
+            self.knn_groups = row // (H + 1) if self.dr.explore_knn_exclude == "dream" else row
+            n = L.query("dr_knn_workspace_bytes", M, M, d.hidden, self.dr.explore_knn)
+            self.ws_knn = torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------- the phases
     def encode_and_warm(self, frames, noise_q=None):
@@ -192,6 +200,13 @@ class ImaginationEngine:
             L.call("dr_disag_fwd", self.explorer.struct(), d.hidden, L_, M, L.ptr(self.hiddens), d.hidden, None, None,
                    L.ptr(self.rewards), self.H + 1, 1, self.H, 1, dr.explore_extrinsic, dr.explore_scale,
                    L.ptr(self.ws_disag), self.ws_disag.numel(), st)
+        if self.entropy:
+            # r' = explore_extrinsic r + explore_scale e(h) in place: e the entropy reward of a state among all
+            # B (H + 1) imagined states of the epoch (queries = bank), the same row mapping as above
+            dr, g = self.dr, L.ptr(self.knn_groups)
+            L.call("dr_state_entropy_fwd", d.hidden, dr.explore_knn, M, L.ptr(self.hiddens), d.hidden, g, M,
+                   L.ptr(self.hiddens), d.hidden, g, None, None, None, L.ptr(self.rewards), self.H + 1, 1, self.H, 1,
+                   dr.explore_extrinsic, dr.explore_scale, L.ptr(self.ws_knn), self.ws_knn.numel(), st)
         L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(self.hiddens), d.hidden,
                L.ptr(self.latents), L_, None, L.ptr(self.V_t), None, L.ptr(self.ws_cr), self.ws_cr.numel(), st)
         L.call("dr_lambda_returns", self.B, self.H, L.ptr(self.rewards), L.ptr(self.continues), L.ptr(self.V_t),
@@ -460,6 +475,9 @@ class ImaginationEngine:
         key = (self.dr.agent.params_key(), self.dr.world_model.params_key(), self.dr.buffer.device_key())
         if self.explorer is not None:
             key += (self.explorer.params_key(), self.dr.explore_extrinsic, self.dr.explore_scale)
+        if self.entropy:
+            key += ("entropy", self.dr.explore_knn, self.dr.explore_knn_exclude, self.dr.explore_extrinsic,
+                    self.dr.explore_scale)
         return key
 
     def run(self, starts_np, timing=False):

@@ -390,20 +390,26 @@ class Decoder(nn.Module):
 
 
 EXPLORE_DEFAULTS = dict(explore="none", explore_ensemble=8, explore_width=None, explore_scale=0.1,
-                        explore_extrinsic=1.0, explore_lr=None)
+                        explore_extrinsic=1.0, explore_lr=None, explore_knn=12, explore_knn_exclude="self")
 
 
 def explore_config(c):
     """The exploration keys of a config with their defaults, validated: explore "none" |
-    "disagreement", explore_ensemble K in 1..16, explore_width W >= 1 (default dyn_pred_hidden_num_nodes_1),
-    explore_scale / explore_extrinsic >= 0, explore_lr > 0 (default world_model_lr)."""
+    "disagreement" | "entropy", explore_ensemble K in 1..16, explore_width W >= 1 (default
+    dyn_pred_hidden_num_nodes_1), explore_scale / explore_extrinsic >= 0, explore_lr > 0 (default world_model_lr),
+    explore_knn k in 1..32, explore_knn_exclude "self" | "dream".  Every key is validated in every mode."""
     e = {k: c.get(k, v) for k, v in EXPLORE_DEFAULTS.items()}
     if e["explore_width"] is None:
         e["explore_width"] = c["dyn_pred_hidden_num_nodes_1"]
     if e["explore_lr"] is None:
         e["explore_lr"] = c["world_model_lr"]
-    if e["explore"] not in ("none", "disagreement"):
-        raise ValueError(f"explore must be 'none' or 'disagreement', got {e['explore']!r}")
+    if e["explore"] not in ("none", "disagreement", "entropy"):
+        raise ValueError(f"explore must be 'none', 'disagreement' or 'entropy', got {e['explore']!r}")
+    k = e["explore_knn"]
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= L.DR_KNN_MAX_K:
+        raise ValueError(f"explore_knn must be an integer in 1..{L.DR_KNN_MAX_K}, got {k!r}")
+    if e["explore_knn_exclude"] not in ("self", "dream"):
+        raise ValueError(f"explore_knn_exclude must be 'self' or 'dream', got {e['explore_knn_exclude']!r}")
     K, W = e["explore_ensemble"], e["explore_width"]
     if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= L.DR_DISAG_MAX_MEMBERS:
         raise ValueError(f"explore_ensemble must be an integer in 1..{L.DR_DISAG_MAX_MEMBERS}, got {K!r}")

@@ -999,6 +999,58 @@ int dr_disag_train_grads(const dr_ensemble* e, int Hd, int L, int M, const float
                          long long ldz, const dr_ensemble* g, float* losses, void* ws, size_t ws_bytes,
                          hipStream_t stream);
 
+/* ---- k-nearest-neighbour search and the particle-entropy reward (APT, Liu &
+ *      Abbeel 2021; config key explore = "entropy").  No
+ *      reference definition.
+ * Inputs.  Queries x_m: Mq rows of D floats, ldq apart.  Bank y_j: Nb rows,
+ * ldb apart.  Optional int32 group ids qg[Mq], bg[Nb] (either may be NULL).
+ * Eligibility.  Bank row j is eligible for query m iff every one of its D
+ * values is finite, and it is not the case that both group arrays are given
+ * and bg[j] == qg[m].  Groups are the only exclusion mechanism: self-exclusion
+ * is "group = row index", excluding a whole dream is "group = row / (H + 1)".
+ * Selection.  Per query the k eligible bank rows of smallest squared Euclidean
+ * distance, in ascending (distance^2, index) order, into d2_out [Mq][k] (f32)
+ * and idx_out [Mq][k] (int32); 1 <= k <= DR_KNN_MAX_K.  With fewer than k
+ * eligible rows the remaining slots hold +inf and -1.  A query row with a
+ * non-finite value gets NaN and -1 in all of its slots; no other row is
+ * affected by it.
+ * Two-stage precision.  The selection uses the Gram form |x|^2 + |y|^2 - 2 x.y,
+ * clamped at 0, on the exact-f32 MFMA; the norms are the same k-ascending fmaf
+ * chain as the dot product, so two bit-identical rows get exactly 0, and on
+ * operands whose products and sums are exact in f32 the selection is the exact
+ * one.  The reported d2_out values are recomputed for the k chosen indices in
+ * the direct form sum (x - y)^2 (columns lane-strided in ascending order, a
+ * fixed wave tree, no atomics): they carry the direct form's relative error,
+ * not the Gram form's cancellation error, and the final order is by the
+ * recomputed value, then the index.  The distance of a pair, in either form,
+ * is a function of that pair's two rows and D only, not of Mq, Nb, the tile
+ * position or the bank split: a query's output is the same bits whatever else
+ * is in the batch, and on every run.  Rows whose squared norm overflows f32
+ * are outside the contract.
+ * Entropy reward.  d_m = (1 / k_m) sum_n sqrt(d2_out[m][n]) over the
+ * k_m = min(k, eligible) filled slots, e_m = log1p(d_m) (APT's log(c + .) with
+ * c = 1); k_m = 0 gives e_m = 0; a non-finite query row gives a non-finite e_m
+ * for that row alone; e_m is exactly 0 when all of the row's neighbours are
+ * bit-identical to it.
+ * Launches: the tile kernel (grid = query tiles x bank splits; the split count
+ * is a function of (Mq, Nb) alone), the merge / recompute kernel, and for the
+ * reward the row kernel; plain launches on `stream`, capturable, no host
+ * synchronisation, no allocation, no process-wide state. */
+#define DR_KNN_MAX_K 32
+size_t dr_knn_workspace_bytes(int Mq, int Nb, int D, int k);
+int dr_knn(int D, int k, int Mq, const float* q, long long ldq, const int* qg, int Nb, const float* bank,
+           long long ldb, const int* bg, float* d2_out, int* idx_out, void* ws, size_t ws_bytes, hipStream_t stream);
+/* d2_out, idx_out, ent_out [Mq] and rew may be NULL (not all four).  The reward
+ * update is dr_disag_fwd's with e_m in the place of d_m:
+ *   rew[b rew_sb + (t - rew_skip) rew_st] = w_ext * rew[..] + w_int * e_m
+ * for b = m / rew_T, t = m % rew_T >= rew_skip (two products and one sum, each
+ * rounded); rew_T = 0: every row m updates rew[m rew_st].  Workspace:
+ * dr_knn_workspace_bytes. */
+int dr_state_entropy_fwd(int D, int k, int Mq, const float* q, long long ldq, const int* qg, int Nb, const float* bank,
+                         long long ldb, const int* bg, float* d2_out, int* idx_out, float* ent_out, float* rew,
+                         int rew_T, int rew_skip, long long rew_sb, long long rew_st, float w_ext, float w_int,
+                         void* ws, size_t ws_bytes, hipStream_t stream);
+
 /* Which parts of a train_Agent epoch (Dreamer.py:264-287) run as ONE persistent
  * launch for these dims and shapes (the stream's CU mask aside): bit 0 the warm
  * start's posterior scan over T steps (Dreamer.py:255-261), bit 1 the
