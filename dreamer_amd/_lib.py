@@ -148,6 +148,10 @@ _SIGS = {
     "dr_critic_tape_bytes": (_sz, [_P(dr_dims), _i]),
     "dr_critic_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
     "dr_critic_fwd": (_i, [_P(dr_dims), _P(dr_critic), _i, fp, _ll, fp, _ll, fp, fp, fp, fp, _sz, fp]),
+    "dr_heads_supported": (_i, [_P(dr_dims), _i, _i]),
+    "dr_heads_workspace_bytes": (_sz, [_P(dr_dims), _i, _i]),
+    "dr_heads_fwd": (_i, [_P(dr_dims), _P(dr_world_model), _P(dr_critic), _P(dr_critic), _i, _i, fp, fp, fp, fp,
+                          fp, fp, fp, fp, _sz, fp, _sz, fp, _sz, fp]),
     "dr_lambda_returns": (_i, [_i, _i, fp, fp, fp, _f, _f, fp, fp]),
     "dr_update_S": (_i, [_i, fp, fp, fp, fp, _sz, fp]),
     "dr_actor_loss_grad": (_i, [_i, _i, _i, fp, fp, fp, fp, fp, fp, _f, _f, fp, fp, fp, fp]),

@@ -97,6 +97,27 @@ int op_gemm_nt_split3_sk(int M, int N, int K, const float* A, int lda, const flo
 int op_gemm_nt_split3_ex(int M, int N, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
                          const void* wr, const float* bias, int act, float* Y, int ldy, int accumulate, float* Y2,
                          int ldy2, int nsplitY, float* part, size_t part_floats, hipStream_t s, int splits_fixed = 0);
+// up to DR_S3_HEADS heads over one A: Y_i = A W_i^T + bias_i, the heads' columns side by side in one
+// product (one repack launch, one GEMM, one finish).  The K partition is op_s3_heads_splits(M, K),
+// whatever the widths and the head count, so a head sums the same in any group and in
+// op_gemm_nt_split3_sk(..., splits_fixed = op_s3_heads_splits(M, K)).  wr: op_nt_split3_heads_ws_bytes,
+// part: op_gemm_nt_split3_heads_part_floats floats, both 16-byte aligned.
+#define DR_S3_HEADS 4
+#define DR_S3_HEADS_SPLITS 4
+struct S3Head {
+  const float* W;     // [N][K], row stride ldw
+  int ldw, N;         // N % 4 == 0
+  const float* bias;  // [N] or NULL
+  float* Y;           // [M][N], row stride ldy (% 4 == 0)
+  int ldy;
+};
+int op_s3_heads_splits(int M, int K);
+bool op_gemm_nt_split3_heads_supported(int M, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                                       const S3Head* heads, int nh);
+size_t op_nt_split3_heads_ws_bytes(const int* widths, int nh, int K);
+size_t op_gemm_nt_split3_heads_part_floats(int M, const int* widths, int nh, int K);
+int op_gemm_nt_split3_heads(int M, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                            const S3Head* heads, int nh, void* wr, float* part, size_t part_floats, hipStream_t s);
 
 // ---- conv_bf16.hip (bf16 perf mode; activations bf16, accumulation f32) ----
 // weights: Conv2d [co][ci][4][4] f32 -> bf16 [co][tap][cin_pad]; matrix slice -> bf16 [rows][cols]

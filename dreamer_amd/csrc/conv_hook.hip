@@ -128,3 +128,27 @@ extern "C" int dr_internal_conv_run(const int* v, const double* num, void* const
   if (rc != DR_OK && msg && msg_cap > 0) snprintf(msg, msg_cap, "%s", dr_last_error());
   return rc;
 }
+
+// Test hook of the grouped first Linear (tests/test_gpu_heads_fused.py): op_gemm_nt_split3_heads on caller-made
+// operands.  need[0] / need[1]: the bytes of weight planes and the floats of partial sums the op asks for; with
+// A == NULL nothing is launched and they alone are reported.  need[2]: op_s3_heads_splits(M, K).
+extern "C" int dr_internal_s3_heads_run(int M, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                                        int nh, const int* widths, void* const* W, void* const* bias, void* const* Y,
+                                        const int* ldy, void* wr, float* part, long long part_floats, long long* need,
+                                        void* stream, char* msg, int msg_cap) {
+  if (msg && msg_cap > 0) msg[0] = 0;
+  if (nh < 1 || nh > DR_S3_HEADS || !widths) return DR_E_INVALID;
+  if (need) {
+    need[0] = (long long)op_nt_split3_heads_ws_bytes(widths, nh, K);
+    need[1] = (long long)op_gemm_nt_split3_heads_part_floats(M, widths, nh, K);
+    need[2] = op_s3_heads_splits(M, K);
+  }
+  if (!A) return DR_OK;
+  S3Head h[DR_S3_HEADS];
+  for (int i = 0; i < nh; ++i)
+    h[i] = {(const float*)W[i], K, widths[i], bias ? (const float*)bias[i] : nullptr, (float*)Y[i], ldy[i]};
+  const int rc = op_gemm_nt_split3_heads(M, K, A, lda, A2, lda2, ksA, h, nh, wr, part, (size_t)part_floats,
+                                         (hipStream_t)stream);
+  if (rc != DR_OK && msg && msg_cap > 0) snprintf(msg, msg_cap, "%s", dr_last_error());
+  return rc;
+}

@@ -2358,6 +2358,146 @@ int op_gemm_nt_split3_ex(int M, int N, int K, const float* A, int lda, const flo
 }
 
 // ---------------------------------------------------------------------------
+// Up to four heads over ONE A operand (the reward, continue and critic heads'
+// first Linears over the imagined states): the heads' columns side by side
+// (N = sum of the widths), so a staged and split A chunk feeds 128 columns of
+// whichever heads lie in the tile; one repack launch, one product, one finish
+// pass that routes each column to its head's bias and output.  The K
+// partition is op_s3_heads_splits(M, K) whatever the widths and the head
+// count: an element's sum (k_gemm_split3's chunk order within a split, the
+// splits in order, then the bias) is the same in a group of four, alone, and
+// in op_gemm_nt_split3_sk with that splits_fixed.
+// ---------------------------------------------------------------------------
+struct S3Group {
+  int nh, ntot;
+  int n0[DR_S3_HEADS + 1];  // first column of head i; [nh..] = ntot
+  int ldw[DR_S3_HEADS], ldy[DR_S3_HEADS];
+  const float* W[DR_S3_HEADS];
+  const float* bias[DR_S3_HEADS];
+  float* Y[DR_S3_HEADS];
+};
+__device__ __forceinline__ int s3_group_head(const S3Group& r, int n) {
+  int h = 0;
+#pragma unroll
+  for (int i = 1; i < DR_S3_HEADS; ++i)
+    if (i < r.nh && n >= r.n0[i]) h = i;
+  return h;
+}
+
+// the heads' W [N_i][K] -> one set of planes [K/32][3][Np][32], zero past ntot and K
+__global__ __launch_bounds__(256) void k_nt_repack_split3_heads(S3Group r, int K, int Np, u16* __restrict__ wr) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int KC = (K + 31) / 32;
+  if (i >= (long long)KC * 32 * Np) return;
+  const int n = (int)(i / (KC * 32)), k = (int)(i - (long long)n * KC * 32);
+  unsigned hh = 0, mm = 0, ll = 0;
+  if (n < r.ntot && k < K) {
+    const int h = s3_group_head(r, n);
+    split3(r.W[h][(long long)(n - r.n0[h]) * r.ldw[h] + k], hh, mm, ll);
+  }
+  const long long plane = (long long)Np * 32;
+  const long long base = ((long long)(k >> 5) * 3 * Np + n) * 32 + (k & 31);
+  wr[base] = (u16)hh;
+  wr[base + plane] = (u16)mm;
+  wr[base + 2 * plane] = (u16)ll;
+}
+
+// partial planes [splits][M][ntot] -> each head's Y (k_s3_finish's order: the splits, then the bias)
+__global__ __launch_bounds__(256) void k_s3_finish_heads(S3Group r, int M, int splits, const float* __restrict__ part) {
+  const long long i4 = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int N = r.ntot, N4 = N / 4;
+  if (i4 >= (long long)M * N4) return;
+  const int m = (int)(i4 / N4), n = 4 * (int)(i4 - (long long)m * N4);
+  f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int sp = 0; sp < splits; ++sp) v += *reinterpret_cast<const f32x4*>(part + ((long long)sp * M + m) * N + n);
+  const int h = s3_group_head(r, n), nl = n - r.n0[h];
+  if (r.bias[h]) v += *reinterpret_cast<const f32x4*>(r.bias[h] + nl);
+  *reinterpret_cast<f32x4*>(r.Y[h] + (long long)m * r.ldy[h] + nl) = v;
+}
+
+int op_s3_heads_splits(int M, int K) {
+  (void)M;  // every M takes the same partition: a chunk of rows sums like the whole
+  const int nch = (K + 31) / 32;
+  int sp = 1;
+  while (sp < DR_S3_HEADS_SPLITS && nch / (2 * sp) >= 8) sp *= 2;
+  return sp;
+}
+
+bool op_gemm_nt_split3_heads_supported(int M, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                                       const S3Head* heads, int nh) {
+  if (nh < 1 || nh > DR_S3_HEADS || !heads) return false;
+  long long ntot = 0;
+  for (int i = 0; i < nh; ++i) {
+    const S3Head& h = heads[i];
+    if (h.N < 4 || h.N % 4 || h.ldy % 4 || h.ldy < h.N || h.ldw < K || !h.W || !h.Y || ((uintptr_t)h.Y & 15) ||
+        ((uintptr_t)h.bias & 15))
+      return false;
+    ntot += h.N;
+  }
+  return ntot <= (1 << 16) && (long long)M * ntot < (1LL << 29) &&
+         op_gemm_nt_split3_supported(M, (int)ntot, K, A, lda, A2, lda2, ksA, 4);
+}
+
+static int s3_heads_ntot(const int* widths, int nh) {
+  int n = 0;
+  for (int i = 0; i < nh; ++i) n += widths[i];
+  return n;
+}
+size_t op_nt_split3_heads_ws_bytes(const int* widths, int nh, int K) {
+  return op_nt_split3_ws_bytes(s3_heads_ntot(widths, nh), K);
+}
+size_t op_gemm_nt_split3_heads_part_floats(int M, const int* widths, int nh, int K) {
+  return (size_t)op_s3_heads_splits(M, K) * M * s3_heads_ntot(widths, nh);
+}
+
+int op_gemm_nt_split3_heads(int M, int K, const float* A, int lda, const float* A2, int lda2, int ksA,
+                            const S3Head* heads, int nh, void* wr, float* part, size_t part_floats, hipStream_t s) {
+  if (!op_gemm_nt_split3_heads_supported(M, K, A, lda, A2, lda2, ksA, heads, nh) || !wr || !part ||
+      ((uintptr_t)wr & 15) || ((uintptr_t)part & 15)) {
+    dr_set_error("gemm_nt_split3_heads: unsupported problem (M=%d K=%d heads=%d)", M, K, nh);
+    return DR_E_INVALID;
+  }
+  S3Group r = {};
+  r.nh = nh;
+  for (int i = 0; i < nh; ++i) {
+    r.n0[i] = r.ntot;
+    r.ntot += heads[i].N;
+    r.ldw[i] = heads[i].ldw;
+    r.ldy[i] = heads[i].ldy;
+    r.W[i] = heads[i].W;
+    r.bias[i] = heads[i].bias;
+    r.Y[i] = heads[i].Y;
+  }
+  for (int i = nh; i <= DR_S3_HEADS; ++i) r.n0[i] = r.ntot;
+  const int N = r.ntot, Np = s3_np(N), splits = op_s3_heads_splits(M, K);
+  if ((size_t)splits * M * N > part_floats) {
+    dr_set_error("gemm_nt_split3_heads: workspace too small");
+    return DR_E_WORKSPACE;
+  }
+  const long long total = (long long)((K + 31) / 32) * 32 * Np;
+  hipLaunchKernelGGL(k_nt_repack_split3_heads, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, r, K, Np,
+                     (u16*)wr);
+  DR_TRY(dr_check_launch("nt_repack_split3_heads"));
+  // raw sums to the partial planes: blockIdx.y's plane with splits > 1; one split stores its
+  // sums (no bias, no activation) to plane 0 through the plain epilogue (Y = part, ldy = N)
+  GemmS3 g = {M, N, K, ksA < K ? ksA : K, lda, lda2, N, 0, Np, A, A2, (const u16*)wr, nullptr, part, splits, part,
+              0, 0, INT_MAX, 0, nullptr};
+  // 256-row tiles while they fill the chip (two waves per SIMD, as op_gemm_nt_split3_ex), else 128
+  const long long w256 = (long long)((M + 255) / 256) * ((N + 127) / 128) * 8 * splits;
+  if (w256 >= 2048) {
+    const int tiles = ((M + 255) / 256) * ((N + 127) / 128);
+    hipLaunchKernelGGL((k_gemm_split3<256, 128>), dim3(dr_xcd_grid(tiles), (unsigned)splits), dim3(512), 0, s, g);
+  } else {
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    hipLaunchKernelGGL((k_gemm_split3<128, 128>), dim3(dr_xcd_grid(tiles), (unsigned)splits), dim3(256), 0, s, g);
+  }
+  DR_TRY(dr_check_launch("gemm_nt_split3_heads"));
+  hipLaunchKernelGGL(k_s3_finish_heads, dim3((unsigned)(((long long)M * (N / 4) + 255) / 256)), dim3(256), 0, s, r, M,
+                     splits, part);
+  return dr_check_launch("s3_finish_heads");
+}
+
+// ---------------------------------------------------------------------------
 // TN products (the weight gradients of the Linears over many rows:
 // dW[m][n] = sum_k G[k][m] X[k][n], k = rows, WorldModel.training_step's
 // heads / decoder / posterior-scan layers, Agent.train_step's actor and

@@ -676,7 +676,7 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
                               const float* z0, const float* h0, dr_noise noise, int deterministic, float* latents,
                               float* hiddens, float* actions, float* rewards, float* continues, float* mus,
                               float* sigmas, void* tape, void* ws, size_t ws_bytes, hipStream_t s) {
-  DR_REQUIRE(d && wm && ac && z0 && h0 && latents && hiddens && actions && rewards && continues && mus && sigmas &&
+  DR_REQUIRE(d && wm && ac && z0 && h0 && latents && hiddens && actions && !rewards == !continues && mus && sigmas &&
                  tape && B > 0 && H > 0,
              "null argument or empty batch");
   DR_TRY(dims_envelope(__func__, d, ENV_GRU | ENV_SAMPLER | ENV_ACTOR));
@@ -723,6 +723,7 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
   }
   if (!unrolled) DR_TRY(imagine_launch_form(d, wm, ac, B, H, noise, nq, deterministic, latents, hiddens, actions, mus,
                                             sigmas, tp, w, split_gru, zg, s));
+  if (!rewards) return DR_OK;  // the caller runs the heads itself (dr_heads_fwd)
   return imagine_heads(d, wm, B, H, latents, hiddens, rewards, continues, w, s);
 }
 
@@ -730,25 +731,70 @@ extern "C" int dr_imagine_fwd(const dr_dims* d, const dr_world_model* wm, const 
 // on every imagined state (h_{t+1}, z_{t+1}) at once: rows m = b (H+1) + t'
 // of the contiguous [B][H+1] hiddens / latents (t' = 0 rides along unused);
 // forward only -- the actor loss takes no gradient through the heads
+// the heads' layers after the first Linear (w.p1r / w.p1c hold its outputs) and the [B][H] stores
+static int imagine_heads_tail(const dr_dims* d, const dr_world_model* wm, int B, int H, float* rewards,
+                              float* continues, ImWs& w, hipStream_t s, bool keep0);
+
 static int imagine_heads(const dr_dims* d, const dr_world_model* wm, int B, int H, const float* latents,
                          const float* hiddens, float* rewards, float* continues, ImWs& w, hipStream_t s, bool keep0) {
   const int L = latent(d), Hd = d->hidden;
+  const int M1 = B * (H + 1);
+  if (s3_first_layer(d, M1, d->rew_h1, hiddens, Hd, latents, L) &&
+      s3_first_layer(d, M1, d->cont_h1, hiddens, Hd, latents, L)) {
+    // the K partition of the grouped form (dr_heads_fwd): the same sums here and there
+    const int sp = op_s3_heads_splits(M1, Hd + L);
+    DR_TRY(op_nt_repack_split3(d->rew_h1, Hd + L, wm->reward.l0.w, Hd + L, w.s3r, s));
+    DR_TRY(op_nt_repack_split3(d->cont_h1, Hd + L, wm->cont.l0.w, Hd + L, w.s3c, s));
+    DR_TRY(op_gemm_nt_split3_sk(M1, d->rew_h1, Hd + L, hiddens, Hd, latents, L, Hd, w.s3r, wm->reward.l0.b, 0,
+                                w.p1r, d->rew_h1, w.s3part, w.s3part_n, s, sp));
+    DR_TRY(op_gemm_nt_split3_sk(M1, d->cont_h1, Hd + L, hiddens, Hd, latents, L, Hd, w.s3c, wm->cont.l0.b, 0,
+                                w.p1c, d->cont_h1, w.s3part, w.s3part_n, s, sp));
+  } else {
+    GemmArgs p[2];
+    p[0] = lin2(M1, d->rew_h1, hiddens, Hd, Hd, latents, L, L, wm->reward.l0.w, wm->reward.l0.b, w.p1r, d->rew_h1);
+    p[1] = lin2(M1, d->cont_h1, hiddens, Hd, Hd, latents, L, L, wm->cont.l0.w, wm->cont.l0.b, w.p1c, d->cont_h1);
+    DR_TRY(gemm_launch(G_NT, AM_PLAIN, p, 2, s));
+  }
+  return imagine_heads_tail(d, wm, B, H, rewards, continues, w, s, keep0);
+}
+
+// test hook (dr_internal_heads_tail_enable): 0 = the tails take the launches k_heads_tail succeeded
+static bool g_heads_tail = true;
+// fp32 mode only: bf16 mode keeps its launches (the critic's LN-SiLU layers run on the bf16 tile route there)
+static bool heads_tail_on(const dr_dims* d) { return g_heads_tail && d->precision != DR_PREC_BF16; }
+
+// the reward / continue tails as k_heads_tail problems: rewards / continues in their [B][Ho] layouts
+static void reward_cont_tails(const dr_dims* d, const dr_world_model* wm, int B, int H, float* rewards,
+                              float* continues, const ImWs& w, bool keep0, HeadTail ht[2]) {
+  const int M1 = B * (H + 1);
+  GemmArgs e[2];
+  e[0] = lin_ln(M1, d->buckets, d->rew_h2, nullptr, d->rew_h2, wm->reward.n4, wm->reward.l6.w, wm->reward.l6.b, nullptr,
+                d->buckets);
+  e[1] = lin_ln(M1, 1, d->cont_h2, nullptr, d->cont_h2, wm->cont.n4, wm->cont.l6.w, wm->cont.l6.b, continues, 1);
+  e[1].act = 2;  // sigmoid
+  memset(ht, 0, 2 * sizeof(HeadTail));
+  ht[0].a = mlp2(M1, d->rew_h1, d->rew_h2, w.p1r, d->rew_h1, wm->reward.n1, wm->reward.l3, wm->reward.n4, e[0]);
+  ht[1].a = mlp2(M1, d->cont_h1, d->cont_h2, w.p1c, d->cont_h1, wm->cont.n1, wm->cont.l3, wm->cont.n4, e[1]);
+  ht[0].buckets = wm->buckets_rew;
+  ht[0].val = rewards;
+  for (int i = 0; i < 2; ++i) {
+    ht[i].rm_h1 = H + 1;
+    ht[i].rm_k0 = keep0 ? 0 : 1;
+  }
+}
+
+static int imagine_heads_tail(const dr_dims* d, const dr_world_model* wm, int B, int H, float* rewards,
+                              float* continues, ImWs& w, hipStream_t s, bool keep0) {
+  {
+    // LN-SiLU, Linear, LN-SiLU, Linear, bucket expectation / sigmoid and the [B][H] stores of both heads in
+    // one launch (k_heads_tail) where both fit it; the launches below are the general path
+    HeadTail ht[2];
+    reward_cont_tails(d, wm, B, H, rewards, continues, w, keep0, ht);
+    if (heads_tail_on(d) && heads_tail_ok(ht[0]) && heads_tail_ok(ht[1])) return heads_tail_launch(ht, 2, s);
+  }
   {
     const int M1 = B * (H + 1);
     GemmArgs p[2];
-    if (s3_first_layer(d, M1, d->rew_h1, hiddens, Hd, latents, L) &&
-        s3_first_layer(d, M1, d->cont_h1, hiddens, Hd, latents, L)) {
-      DR_TRY(op_nt_repack_split3(d->rew_h1, Hd + L, wm->reward.l0.w, Hd + L, w.s3r, s));
-      DR_TRY(op_nt_repack_split3(d->cont_h1, Hd + L, wm->cont.l0.w, Hd + L, w.s3c, s));
-      DR_TRY(op_gemm_nt_split3_sk(M1, d->rew_h1, Hd + L, hiddens, Hd, latents, L, Hd, w.s3r, wm->reward.l0.b, 0,
-                                  w.p1r, d->rew_h1, w.s3part, w.s3part_n, s));
-      DR_TRY(op_gemm_nt_split3_sk(M1, d->cont_h1, Hd + L, hiddens, Hd, latents, L, Hd, w.s3c, wm->cont.l0.b, 0,
-                                  w.p1c, d->cont_h1, w.s3part, w.s3part_n, s));
-    } else {
-      p[0] = lin2(M1, d->rew_h1, hiddens, Hd, Hd, latents, L, L, wm->reward.l0.w, wm->reward.l0.b, w.p1r, d->rew_h1);
-      p[1] = lin2(M1, d->cont_h1, hiddens, Hd, Hd, latents, L, L, wm->cont.l0.w, wm->cont.l0.b, w.p1c, d->cont_h1);
-      DR_TRY(gemm_launch(G_NT, AM_PLAIN, p, 2, s));
-    }
     p[0] = lin_ln(M1, d->buckets, d->rew_h2, w.p2r, d->rew_h2, wm->reward.n4, wm->reward.l6.w, wm->reward.l6.b, w.rlog,
                   d->buckets);
     p[1] = lin_ln(M1, 1, d->cont_h2, w.p2c, d->cont_h2, wm->cont.n4, wm->cont.l6.w, wm->cont.l6.b, w.clog, 1);
@@ -1168,6 +1214,10 @@ static size_t critic_ws_bytes(const dr_dims* d, int M) {
 }
 
 
+// the critic's layers after the first Linear (t.pre1 holds its output), the logits and the values
+static int critic_tail(const dr_dims* d, const dr_critic* cr, int M, const CTape& t, float* logits, float* values,
+                       bool tape, hipStream_t s);
+
 extern "C" int dr_critic_fwd(const dr_dims* d, const dr_critic* cr, int M, const float* h, long long ldh,
                              const float* z, long long ldz, float* logits, float* values, void* tape, void* ws,
                              size_t ws_bytes, hipStream_t s) {
@@ -1207,13 +1257,51 @@ extern "C" int dr_critic_fwd(const dr_dims* d, const dr_critic* cr, int M, const
   DR_REQUIRE(tape || ws, "dr_critic_fwd needs a tape or a workspace");
   const int L = latent(d), Hd = d->hidden, c1 = d->critic_h1, c2 = d->critic_h2, nb = d->buckets;
   if (s3w && s3_first_layer(d, M, c1, h, ldh, z, ldz)) {
+    // the K partition of the grouped form (dr_heads_fwd): the same sums here and there
+    const int sp = s3part ? op_s3_heads_splits(M, Hd + L) : 0;
     DR_TRY(op_nt_repack_split3(c1, Hd + L, cr->net.l0.w, Hd + L, s3w, s));
     DR_TRY(op_gemm_nt_split3_sk(M, c1, Hd + L, h, (int)ldh, z, (int)ldz, Hd, s3w, cr->net.l0.b, 0, t.pre1, c1,
-                                s3part, s3part_n, s));
+                                s3part, s3part_n, s, sp));
   } else {
     GemmArgs g1 = lin2(M, c1, h, ldh, Hd, z, ldz, L, cr->net.l0.w, cr->net.l0.b, t.pre1, c1);
     give_splitk(g1, sk, skn);
     DR_TRY(run(G_NT, AM_PLAIN, g1, s));
+  }
+  return critic_tail(d, cr, M, t, logits, values, tape != nullptr, s);
+}
+
+// the same as a k_heads_tail problem: the tape's saves and logits only where a tape (or the caller) asks for
+// them, the value straight from the tile
+static void critic_tail_args(const dr_dims* d, const dr_critic* cr, int M, const CTape& t, float* logits,
+                             float* values, bool tape, HeadTail& ht) {
+  const int c1 = d->critic_h1, c2 = d->critic_h2, nb = d->buckets;
+  float* lg = logits ? logits : (tape || !values) ? t.logits : nullptr;
+  GemmArgs e = lin_ln(M, nb, c2, nullptr, c2, cr->net.n4, cr->net.l6.w, cr->net.l6.b, lg, nb);
+  memset(&ht, 0, sizeof(HeadTail));
+  ht.a = mlp2(M, c1, c2, t.pre1, c1, cr->net.n1, cr->net.l3, cr->net.n4, e);
+  if (tape) {
+    ht.a.a1_out = t.x1; ht.a.ld_a1 = c1;
+    ht.a.pre2 = t.pre2; ht.a.ld_pre2 = c2;
+    ht.a.a2_out = t.x2; ht.a.ld_a2 = c2;
+  }
+  if (values) {
+    ht.buckets = cr->buckets;
+    ht.val = values;
+  }
+  ht.chain1 = 1;  // the sums of the LN-SiLU tile route below: at the shapes it serves, the same bits
+}
+
+static int critic_tail(const dr_dims* d, const dr_critic* cr, int M, const CTape& t, float* logits, float* values,
+                       bool tape, hipStream_t s) {
+  const int c1 = d->critic_h1, c2 = d->critic_h2, nb = d->buckets;
+  {
+    HeadTail ht;
+    critic_tail_args(d, cr, M, t, logits, values, tape, ht);
+    if (heads_tail_on(d) && heads_tail_ok(ht)) {
+      DR_TRY(heads_tail_launch(&ht, 1, s));
+      if (tape && logits && logits != t.logits) DR_TRY(copy2d(t.logits, nb, logits, nb, nb, M, s));
+      return DR_OK;
+    }
   }
   GemmArgs g2 = lin_ln(M, c2, c1, t.pre1, c1, cr->net.n1, cr->net.l3.w, cr->net.l3.b, t.pre2, c2);
   g2.a_out = t.x1; g2.ld_aout = c1;
@@ -1225,6 +1313,161 @@ extern "C" int dr_critic_fwd(const dr_dims* d, const dr_critic* cr, int M, const
   if (tape && logits && logits != t.logits) DR_TRY(copy2d(t.logits, nb, logits, nb, nb, M, s));
   if (values) DR_TRY(op_bucket_value(M, nb, lg, nb, cr->buckets, values, 1, s));
   return DR_OK;
+}
+
+// ===========================================================================
+// the four heads that read the imagined states -- reward, continue, target
+// critic, online critic -- on one pass over [h | z]: their first Linears as
+// ONE grouped split3 product (op_gemm_nt_split3_heads: one repack launch, one
+// GEMM over the 800 columns side by side, one finish), then the tails of
+// imagine_heads and dr_critic_fwd on its outputs.  Every output holds the bits
+// dr_imagine_fwd's heads and two dr_critic_fwd calls give (the same K
+// partition, the same tails).
+// ===========================================================================
+struct HeadsWs {
+  void* planes;
+  float* part;
+  size_t part_n;
+};
+static void heads_widths(const dr_dims* d, int* wd) {
+  wd[0] = d->rew_h1; wd[1] = d->cont_h1; wd[2] = d->critic_h1; wd[3] = d->critic_h1;
+}
+static void headsws_carve(Carve& c, const dr_dims* d, int M, HeadsWs& w) {
+  int wd[4];
+  heads_widths(d, wd);
+  const int K = d->hidden + latent(d);
+  w.planes = c.raw(op_nt_split3_heads_ws_bytes(wd, 4, K));
+  w.part_n = op_gemm_nt_split3_heads_part_floats(M, wd, 4, K);
+  w.part = c.f((long long)w.part_n);
+}
+// fp32 mode, the split3 first layer for all four heads (M >= 1024, widths % 4 == 0) and the
+// reward / continue tail kernel's widths; pointers and strides are those of the engine's own arrays
+static bool heads_shape_ok(const dr_dims* d, int B, int H) {
+  if (!d || B < 1 || H < 1 || d->precision == DR_PREC_BF16) return false;
+  const long long M = (long long)B * (H + 1);
+  const int Hd = d->hidden, L = latent(d);
+  if (M < 1024 || M * std::max(Hd, L) >= (1LL << 31)) return false;
+  int wd[4];
+  heads_widths(d, wd);
+  for (int i = 0; i < 4; ++i)
+    if (wd[i] < 4 || wd[i] % 4) return false;
+  return Hd % 4 == 0 && L % 4 == 0 && d->buckets >= 1 && mlp2_widths_ok(d->rew_h1, d->rew_h2) &&
+         mlp2_widths_ok(d->cont_h1, d->cont_h2);
+}
+extern "C" int dr_heads_supported(const dr_dims* d, int B, int H) { return heads_shape_ok(d, B, H) ? 1 : 0; }
+extern "C" int dr_internal_s3_heads_splits(int M, int K) { return op_s3_heads_splits(M, K); }
+
+extern "C" size_t dr_heads_workspace_bytes(const dr_dims* d, int B, int H) {
+  if (!heads_shape_ok(d, B, H)) return 0;
+  Carve c(nullptr);
+  HeadsWs w;
+  headsws_carve(c, d, B * (H + 1), w);
+  return c.off;
+}
+
+extern "C" int dr_heads_fwd(const dr_dims* d, const dr_world_model* wm, const dr_critic* target,
+                            const dr_critic* online, int B, int H, const float* latents, const float* hiddens,
+                            float* rewards, float* continues, float* V_t, float* V_c, void* ctape, void* ws_im,
+                            size_t ws_im_bytes, void* ws_cr, size_t ws_cr_bytes, void* ws, size_t ws_bytes,
+                            hipStream_t s) {
+  DR_REQUIRE(d && wm && target && online && latents && hiddens && rewards && continues && V_t && V_c && ctape &&
+                 ws_im && ws_cr && ws && B > 0 && H > 0,
+             "null argument or empty batch");
+  if (!heads_shape_ok(d, B, H)) {
+    dr_set_error("dr_heads_fwd: shape outside the grouped heads (fp32 mode, B (H + 1) >= 1024, widths %% 4 == 0)");
+    return DR_E_UNSUPPORTED;
+  }
+  const int M = B * (H + 1), L = latent(d), Hd = d->hidden, c1 = d->critic_h1;
+  Carve ci(ws_im);
+  ImWs w;
+  imws_carve(ci, d, B, H, w);
+  WS_CHECK(ci, ws_im_bytes);
+  CTape tt, to;  // the target critic's scratch tape (dr_critic_fwd's carve of its workspace), the online critic's tape
+  {
+    Carve c(ws_cr);
+    ctape_carve(c, d, M, tt);
+    WS_CHECK(c, ws_cr_bytes);
+    Carve ct(ctape);
+    ctape_carve(ct, d, M, to);
+  }
+  Carve c(ws);
+  HeadsWs hw;
+  headsws_carve(c, d, M, hw);
+  WS_CHECK(c, ws_bytes);
+  const S3Head heads[4] = {{wm->reward.l0.w, Hd + L, d->rew_h1, wm->reward.l0.b, w.p1r, d->rew_h1},
+                           {wm->cont.l0.w, Hd + L, d->cont_h1, wm->cont.l0.b, w.p1c, d->cont_h1},
+                           {target->net.l0.w, Hd + L, c1, target->net.l0.b, tt.pre1, c1},
+                           {online->net.l0.w, Hd + L, c1, online->net.l0.b, to.pre1, c1}};
+  if (!op_gemm_nt_split3_heads_supported(M, Hd + L, hiddens, Hd, latents, L, Hd, heads, 4)) {
+    dr_set_error("dr_heads_fwd: operands outside the grouped first Linear (alignment)");
+    return DR_E_UNSUPPORTED;
+  }
+  GemmBf16Scope bf16_scope(false);
+  DR_TRY(op_gemm_nt_split3_heads(M, Hd + L, hiddens, Hd, latents, L, Hd, heads, 4, hw.planes, hw.part, hw.part_n, s));
+  {  // the four tails as one launch
+    HeadTail ht[4];
+    reward_cont_tails(d, wm, B, H, rewards, continues, w, false, ht);
+    critic_tail_args(d, target, M, tt, nullptr, V_t, false, ht[2]);
+    critic_tail_args(d, online, M, to, nullptr, V_c, true, ht[3]);
+    bool ok = heads_tail_on(d);
+    for (int i = 0; i < 4; ++i) ok = ok && heads_tail_ok(ht[i]);
+    if (ok) return heads_tail_launch(ht, 4, s);
+  }
+  DR_TRY(imagine_heads_tail(d, wm, B, H, rewards, continues, w, s, false));
+  DR_TRY(critic_tail(d, target, M, tt, nullptr, V_t, false, s));
+  return critic_tail(d, online, M, to, nullptr, V_c, true, s);
+}
+
+// Test hooks (tests/test_gpu_heads_fused.py), not in the public header.  dr_internal_heads_tail_enable: 0 makes
+// every tail take the launches k_heads_tail succeeded (k_mlp2_tail / the LN-SiLU routes, k_bucket_value, the
+// copies); returns the previous setting.  dr_internal_heads_tail_run: one k_heads_tail launch (old_path = 0) or, per
+// head, k_mlp2_tail and k_bucket_value (old_path = 1; no row map, Y required) on caller-made operands.  v: per head
+// K1, K2, N, act, rm_h1, rm_k0, chain1, 0; p: per head X, ln1_g, ln1_b, W3, b3, ln4_g, ln4_b, W6, b6, buckets, Y, val,
+// a1_out, pre2, a2_out, 0 (contiguous rows: ldx = K1, W3 [K2][K1], W6 [N][K2], ldy = N).
+extern "C" int dr_internal_heads_tail_enable(int on) {
+  const int prev = g_heads_tail ? 1 : 0;
+  g_heads_tail = on != 0;
+  return prev;
+}
+extern "C" int dr_internal_heads_tail_run(int M, int nh, const int* v, void* const* p, int old_path, void* stream,
+                                          char* msg, int msg_cap) {
+  if (msg && msg_cap > 0) msg[0] = 0;
+  if (nh < 1 || nh > DR_HT_HEADS || !v || !p) return DR_E_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  HeadTail ht[DR_HT_HEADS];
+  memset(ht, 0, sizeof(ht));
+  for (int i = 0; i < nh; ++i) {
+    const int* vi = v + 8 * i;
+    auto P = [&](int k) { return (float*)p[16 * i + k]; };
+    const int K1 = vi[0], K2 = vi[1], N = vi[2];
+    GemmArgs e = gemm_args();
+    e.M = M; e.N = N; e.K = K2;
+    e.W = P(7); e.ldb = K2; e.bias = P(8);
+    e.Y = P(10); e.ldy = N; e.act = vi[3];
+    Mlp2Args& a = ht[i].a;
+    a.M = M; a.K1 = K1; a.K2 = K2;
+    a.X = P(0); a.ldx = K1;
+    a.ln1_g = P(1); a.ln1_b = P(2); a.W3 = P(3); a.b3 = P(4); a.ln4_g = P(5); a.ln4_b = P(6);
+    a.a1_out = P(12); a.ld_a1 = K1; a.pre2 = P(13); a.ld_pre2 = K2; a.a2_out = P(14); a.ld_a2 = K2;
+    a.e = e;
+    ht[i].buckets = P(9);
+    ht[i].val = P(11);
+    ht[i].rm_h1 = vi[4];
+    ht[i].rm_k0 = vi[5];
+    ht[i].chain1 = vi[6];
+  }
+  int rc = DR_OK;
+  if (!old_path) {
+    rc = heads_tail_launch(ht, nh, s);
+  } else {
+    for (int i = 0; i < nh && rc == DR_OK; ++i) {
+      rc = mlp2_launch(&ht[i].a, 1, s);
+      if (rc == DR_OK && ht[i].buckets)
+        rc = op_bucket_value(M, ht[i].a.e.N, ht[i].a.e.Y, ht[i].a.e.N, ht[i].buckets, ht[i].val, 1, s);
+    }
+  }
+  if (rc != DR_OK && msg && msg_cap > 0) snprintf(msg, msg_cap, "%s", dr_last_error());
+  return rc;
 }
 
 struct CBws {

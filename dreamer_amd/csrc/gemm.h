@@ -147,4 +147,24 @@ struct alignas(16) Mlp2Args {
   GemmArgs e;                        // last Linear: e.N, e.W [N][K2] (e.ldb), e.bias, epilogue
 };
 bool mlp2_ok(const Mlp2Args& a);  // the shapes and alignments mlp2_launch takes
+bool mlp2_widths_ok(int K1, int K2);  // its rule for the two hidden widths alone (host only)
+
+// The same tail for 1 to DR_HT_HEADS heads over the same rows in ONE launch (k_heads_tail): a workgroup computes
+// all e.N <= DR_HT_NMAX output columns of its 32 rows, so the middle layer runs once; k_mlp2_tail's arithmetic
+// per row and per output element.  e.Y (optional with buckets): the last Linear's output through e.act;
+// buckets / val: symexp(sum(softmax(out) * buckets)) per row (k_bucket_value's arithmetic) from the tile, no
+// logits round trip.  Both stores take the row map m = b rm_h1 + t -> b (rm_h1 - rm_k0) + t - rm_k0 for
+// t >= rm_k0, rows with t < rm_k0 are not stored (rm_h1 = 0: row m).  a1_out / pre2 / a2_out as Mlp2Args.
+#define DR_HT_HEADS 4
+#define DR_HT_NMAX 256
+struct alignas(16) HeadTail {
+  Mlp2Args a;            // a.e.epi == EPI_NONE
+  const float* buckets;  // [e.N] or NULL
+  float* val;            // with buckets
+  int rm_h1, rm_k0;
+  int chain1;            // 1: one MFMA accumulator chain per tile, k ascending (k_gemm_tile's sums); 0: k_mlp2_tail's four
+  int pad_;
+};
+bool heads_tail_ok(const HeadTail& h);
+int heads_tail_launch(const HeadTail* heads, int count, hipStream_t s);
 int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s);

@@ -2154,6 +2154,27 @@ __device__ __forceinline__ f32x4 mlp2_tile(const float (*ys)[LP], const float4 (
   return o;
 }
 
+// the same tile on ONE accumulator chain, k ascending: k_gemm_tile's order per output element (the critics'
+// LN-SiLU layers ran there: k_ln_silu_rows, whose row arithmetic is mlp2_ln_silu's, then the 64 x 64 tile GEMM),
+// so a head that asks for it keeps that route's bits.  (The tile GEMM pads K to 32 with zero products, which add
+// nothing.)
+template <int LP>
+__device__ __forceinline__ f32x4 mlp2_tile1(const float (*ys)[LP], const float4 (&wv)[MLP2_KS], int K, int r, int q) {
+  const int ks = (K + 15) >> 4;
+  f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < MLP2_KS; ++s) {
+    if (s < ks) {
+      const float4 a = *reinterpret_cast<const float4*>(&ys[r][16 * s + 4 * q]);
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wv[s].x, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wv[s].y, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wv[s].z, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wv[s].w, c, 0, 0, 0);
+    }
+  }
+  return c;
+}
+
 __global__ __launch_bounds__(512) void k_mlp2_tail(Mlp2Batch mb) {
   __shared__ Mlp2Args s_a;
   dr_stage_args(mb.p[blockIdx.z], s_a, threadIdx.x);
@@ -2324,6 +2345,9 @@ __global__ __launch_bounds__(512) void k_mlp2_tail(Mlp2Batch mb) {
 
 // what k_mlp2_tail takes: both hidden widths staged as float4 rows of at most
 // MLP2_KMAX floats, 16-byte aligned operands, a plain, sampler or actor epilogue
+bool mlp2_widths_ok(int K1, int K2) {
+  return !(K1 < 4 || K2 < 4 || K1 > MLP2_KMAX || K2 > MLP2_KMAX || K1 % 4 || K2 % 4);
+}
 bool mlp2_ok(const Mlp2Args& a) {
   const GemmArgs& g = a.e;
   const bool al = !(((uintptr_t)a.X | (uintptr_t)a.W3 | (uintptr_t)g.W | (uintptr_t)a.ln1_g | (uintptr_t)a.ln1_b |
@@ -2356,6 +2380,203 @@ int mlp2_launch(const Mlp2Args* probs, int count, hipStream_t s) {
   }
   hipLaunchKernelGGL(k_mlp2_tail, dim3(gx, gy, count), dim3(512), 0, s, mb);
   return dr_check_launch("mlp2_tail");
+}
+
+// ---------------------------------------------------------------------------
+// k_heads_tail: k_mlp2_tail's layers for 1 to 4 heads over the same rows (the
+// reward, continue and critic heads over the imagined states), a workgroup per
+// 32 rows and head computing ALL output columns of its rows: the middle layer
+// once, each weight fragment loaded once for both 16-row groups, and the
+// bucket expectation (k_bucket_value) straight from the logits in the tile.
+// Per row and per output element the arithmetic is k_mlp2_tail's (the same
+// LayerNorm reduction, the same f32 MFMA chains in the same k order, the same
+// bias add) and k_bucket_value's, so neither the tile height nor the column
+// blocking changes a bit; with chain1 the products run on one accumulator
+// chain instead, the order of the tile GEMM the critics' layers ran on.  Outputs: e.Y (logits or the activated value, may be
+// NULL with buckets) and val (symexp of the bucket expectation), both through
+// the row map m = b rm_h1 + t -> b (rm_h1 - rm_k0) + t - rm_k0, t >= rm_k0
+// (rm_h1 = 0: row m): the [B][H] layouts of the rewards and continues.
+// ---------------------------------------------------------------------------
+#define HT_RG 2
+#define HT_ROWS (16 * HT_RG)
+struct HeadTailBatch {
+  HeadTail p[DR_HT_HEADS];
+};
+
+__device__ __forceinline__ long long ht_row(const HeadTail& h, int m) {
+  if (h.rm_h1 <= 0) return m;
+  const int b = m / h.rm_h1, t = m - b * h.rm_h1;
+  return t < h.rm_k0 ? -1LL : (long long)b * (h.rm_h1 - h.rm_k0) + (t - h.rm_k0);
+}
+
+__global__ __launch_bounds__(512) void k_heads_tail(HeadTailBatch hb) {
+  __shared__ HeadTail s_h;
+  dr_stage_args(hb.p[blockIdx.y], s_h, threadIdx.x);
+  const Mlp2Args& a = s_h.a;
+  const GemmArgs& g = a.e;
+  const int M = dr_uni(a.M), K1 = dr_uni(a.K1), K2 = dr_uni(a.K2), N = dr_uni(g.N);
+  const int m0 = blockIdx.x * HT_ROWS;
+  if (m0 >= M) return;
+  const bool one = dr_uni(s_h.chain1) != 0;  // k_gemm_tile's accumulation order instead of k_mlp2_tail's
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r = lane & 15, q = lane >> 4;
+  constexpr int LP = MLP2_KMAX + 8;  // 8 mod 16 dwords: conflict-free ds_read_b128 fragments
+  constexpr int SP = DR_HT_NMAX + 1;
+  constexpr int HSO = HT_ROWS * (LP > SP ? LP : SP);
+  __shared__ __attribute__((aligned(16))) float ys[HT_ROWS][LP];
+  __shared__ __attribute__((aligned(16))) float hso[HSO];  // h2 rows, then (h2 is dead) the output rows
+  float(*hs)[LP] = reinterpret_cast<float(*)[LP]>(hso);
+  float(*so)[SP] = reinterpret_cast<float(*)[SP]>(hso);
+  const int k = 4 * lane;
+  const float* X = dr_uni(a.X);
+  const int ldx = dr_uni((int)a.ldx);
+  float4 xr[2 * HT_RG];
+#pragma unroll
+  for (int i = 0; i < 2 * HT_RG; ++i) {
+    const int m = m0 + wave + 8 * i;
+    const bool ok = m < M && k < K1;
+    xr[i] = dr_ld4(X, ok ? (unsigned)(m * ldx + k) : 0u);
+  }
+  const int nt3 = (K2 + 15) >> 4;
+  float4 w3[2][MLP2_KS];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int n = (wave + 8 * i) * 16 + r;
+    mlp2_wload(w3[i], a.W3, K1, n, wave + 8 * i < nt3 && n < K2, K1, q);
+  }
+  // A: y1 = SiLU(LN1(X)), four rows per wave
+  {
+    const int KP = (K1 + 15) & ~15;
+#pragma unroll
+    for (int i = 0; i < 2 * HT_RG; ++i) {
+      const int rr = wave + 8 * i, m = m0 + rr;
+      const bool ok = m < M && k < K1;
+      const float4 y = mlp2_ln_silu(xr[i], ok, K1, a.ln1_g, a.ln1_b, k);
+      if (k < KP) *reinterpret_cast<float4*>(&ys[rr][k]) = y;
+      if (a.a1_out && ok) dr_st4(a.a1_out, (unsigned)(m * a.ld_a1 + k), y);
+    }
+  }
+  __syncthreads();
+  // B: h2 = y1 W3^T + b3 (16-column tiles over the 8 waves, each on both row groups)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int tj = wave + 8 * i;
+    if (tj < nt3) {
+      const int n = tj * 16 + r;
+      const float bv = (n < K2 && a.b3) ? dr_ld1(a.b3, (unsigned)n) : 0.f;
+#pragma unroll
+      for (int rg = 0; rg < HT_RG; ++rg) {
+        const f32x4 acc = one ? mlp2_tile1<LP>(ys + 16 * rg, w3[i], K1, r, q) : mlp2_tile<LP>(ys + 16 * rg, w3[i], K1, r, q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int ml = 16 * rg + 4 * q + e, m = m0 + ml;
+          const float v = (n < K2) ? acc[e] + bv : 0.f;
+          hs[ml][n] = v;
+          if (a.pre2 && m < M && n < K2) dr_g(a.pre2)[(long long)m * a.ld_pre2 + n] = v;
+        }
+      }
+    }
+  }
+  // the last Linear's fragments of this wave's (up to) two 16-column tiles: in flight across the LayerNorm
+  const int ntd = (N + 15) >> 4;
+  float4 w6[2][MLP2_KS];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int n = (wave + 8 * i) * 16 + r;
+    mlp2_wload(w6[i], dr_uni(g.W), dr_uni((int)g.ldb), n, wave + 8 * i < ntd && n < N, K2, q);
+  }
+  __syncthreads();
+  // C: y2 = SiLU(LN4(h2)), back into ys
+  {
+    const int KP = (K2 + 15) & ~15;
+    for (int rr = wave; rr < HT_ROWS; rr += 8) {
+      const int m = m0 + rr;
+      const bool ok = k < K2;
+      float4 x = ok ? *reinterpret_cast<const float4*>(&hs[rr][k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 y = mlp2_ln_silu(x, ok, K2, a.ln4_g, a.ln4_b, k);
+      if (m >= M) y = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k < KP) *reinterpret_cast<float4*>(&ys[rr][k]) = y;
+      if (a.a2_out && ok && m < M) dr_st4(a.a2_out, (unsigned)(m * a.ld_a2 + k), y);
+    }
+  }
+  __syncthreads();
+  // D: out = y2 W6^T + b6, every column of the head
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int tj = wave + 8 * i;
+    if (tj < ntd) {
+      const int n = tj * 16 + r;
+      const float bv = (n < N && g.bias) ? dr_ld1(g.bias, (unsigned)n) : 0.f;
+#pragma unroll
+      for (int rg = 0; rg < HT_RG; ++rg) {
+        const f32x4 acc = one ? mlp2_tile1<LP>(ys + 16 * rg, w6[i], K2, r, q) : mlp2_tile<LP>(ys + 16 * rg, w6[i], K2, r, q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) so[16 * rg + 4 * q + e][n] = acc[e] + bv;
+      }
+    }
+  }
+  __syncthreads();
+  // E: the stores
+  if (g.Y) {
+    for (int x = tid; x < HT_ROWS * N; x += 512) {
+      const int ml = x / N, nl = x - ml * N, m = m0 + ml;
+      if (m >= M) continue;
+      const long long o = ht_row(s_h, m);
+      if (o >= 0) dr_g(g.Y)[o * g.ldy + nl] = epi_act(g, so[ml][nl]);
+    }
+  }
+  if (s_h.buckets) {  // k_bucket_value on the row in LDS, one wave per row
+    const float* bk = dr_uni(s_h.buckets);
+    for (int rr = wave; rr < HT_ROWS; rr += 8) {
+      const int m = m0 + rr;
+      if (m >= M) break;
+      const float* l = so[rr];
+      float mx = -INFINITY;
+      for (int c = lane; c < N; c += 64) mx = fmaxf(mx, l[c]);
+      mx = wave_max(mx);
+      float se = 0.f;
+      for (int c = lane; c < N; c += 64) se += expf(l[c] - mx);
+      se = wave_sum(se);
+      float acc = 0.f;
+      for (int c = lane; c < N; c += 64) acc += (expf(l[c] - mx) / se) * dr_g(bk)[c];
+      acc = wave_sum(acc);
+      const long long o = ht_row(s_h, m);
+      if (lane == 0 && o >= 0) dr_g(s_h.val)[o] = dr_symexp(acc);
+    }
+  }
+}
+
+bool heads_tail_ok(const HeadTail& h) {
+  const Mlp2Args& a = h.a;
+  const GemmArgs& g = a.e;
+  const bool al = !(((uintptr_t)a.X | (uintptr_t)a.W3 | (uintptr_t)g.W | (uintptr_t)a.ln1_g | (uintptr_t)a.ln1_b |
+                     (uintptr_t)a.ln4_g | (uintptr_t)a.ln4_b | (uintptr_t)a.a1_out | (uintptr_t)a.a2_out) & 15);
+  return al && mlp2_widths_ok(a.K1, a.K2) && a.M >= 1 && a.X && a.W3 && g.W && a.ln1_g && a.ln1_b && a.ln4_g &&
+         a.ln4_b && a.ldx % 4 == 0 && a.ldx >= a.K1 && (long long)a.M * a.ldx < (1LL << 31) && g.ldb % 4 == 0 &&
+         g.ldb >= a.K2 && a.ld_a1 % 4 == 0 && a.ld_a2 % 4 == 0 && (long long)a.M * a.ld_a1 < (1LL << 31) &&
+         (long long)a.M * a.ld_a2 < (1LL << 31) && g.K == a.K2 && g.N >= 1 && g.N <= DR_HT_NMAX &&
+         g.epi == EPI_NONE && !g.accumulate && !g.addend && g.alpha == 1.0f && (g.Y || h.buckets) &&
+         (!h.buckets || h.val) && h.rm_h1 >= 0 && h.rm_k0 >= 0 && (h.rm_h1 == 0 || h.rm_k0 < h.rm_h1);
+}
+
+int heads_tail_launch(const HeadTail* heads, int count, hipStream_t s) {
+  if (count < 1 || count > DR_HT_HEADS) {
+    dr_set_error("heads_tail_launch: bad head count %d", count);
+    return DR_E_INVALID;
+  }
+  HeadTailBatch hb;
+  int M = 0;
+  for (int i = 0; i < count; ++i) {
+    if (!heads_tail_ok(heads[i])) {
+      const Mlp2Args& a = heads[i].a;
+      dr_set_error("heads_tail_launch: unsupported head %d (M=%d K1=%d K2=%d N=%d)", i, a.M, a.K1, a.K2, a.e.N);
+      return DR_E_INVALID;
+    }
+    hb.p[i] = heads[i];
+    M = std::max(M, heads[i].a.M);
+  }
+  hipLaunchKernelGGL(k_heads_tail, dim3(dr_cdiv(M, HT_ROWS), count), dim3(512), 0, s, hb);
+  return dr_check_launch("heads_tail");
 }
 
 

@@ -145,6 +145,12 @@ class ImaginationEngine:
         # the online critic's forward / loss backward run on a side stream
         # beside the target critic and the BPTT (run_many): own workspace
         self.ws_cr2 = hip.workspace(dev).get("e_cr2", L.query("dr_critic_workspace_bytes", d, B, H))
+        # the four heads over the imagined states in one pass (dr_heads_fwd) where the library takes the shape;
+        # heads_done: imagine() ran them, so returns() / the update skip their own critic forwards
+        self.heads_fused = bool(L.query("dr_heads_supported", d, B, H))
+        self.heads_done = False
+        if self.heads_fused:
+            self.ws_heads = hip.workspace(dev).get("e_heads", L.query("dr_heads_workspace_bytes", d, B, H))
         self.rng = hip.rng(dev)
         if self.explorer is not None:  # own scratch, not the grow-only named one: the phase graphs keep its address
             ex = self.explorer
@@ -182,10 +188,21 @@ class ImaginationEngine:
             nz = hip.explicit_noise(q=q, eps=eps, device=self.dev)
         else:
             nz = L.dr_noise(None, None, self.rng.state.data_ptr(), self.rank * self.B, DREAM_STREAM)
+        fused = self.heads_fused
         L.call("dr_imagine_fwd", d, self.dr.world_model.packed(), self.dr.agent.actor_struct(), self.B, self.H,
                L.ptr(z0), L.ptr(h0), nz, int(deterministic), L.ptr(self.latents), L.ptr(self.hiddens),
-               L.ptr(self.actions), L.ptr(self.rewards), L.ptr(self.continues), L.ptr(self.mus),
-               L.ptr(self.sigmas), L.ptr(self.tape), L.ptr(self.ws_im), self.ws_im.numel(), hip.stream())
+               L.ptr(self.actions), None if fused else L.ptr(self.rewards), None if fused else L.ptr(self.continues),
+               L.ptr(self.mus), L.ptr(self.sigmas), L.ptr(self.tape), L.ptr(self.ws_im), self.ws_im.numel(),
+               hip.stream())
+        if fused:
+            # reward, continue, target critic (V_t) and online critic (V_c, tape) on one pass over [h | z]
+            ag = self.dr.agent
+            L.call("dr_heads_fwd", d, self.dr.world_model.packed(), ag.critic_struct(target=True), ag.critic_struct(),
+                   self.B, self.H, L.ptr(self.latents), L.ptr(self.hiddens), L.ptr(self.rewards),
+                   L.ptr(self.continues), L.ptr(self.V_t), L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_im),
+                   self.ws_im.numel(), L.ptr(self.ws_cr), self.ws_cr.numel(), L.ptr(self.ws_heads),
+                   self.ws_heads.numel(), hip.stream())
+        self.heads_done = fused
 
     def returns(self):
         """target-critic values and lambda returns (Agent.py:156-172); with exploration on, the intrinsic reward
@@ -207,8 +224,9 @@ class ImaginationEngine:
             L.call("dr_state_entropy_fwd", d.hidden, dr.explore_knn, M, L.ptr(self.hiddens), d.hidden, g, M,
                    L.ptr(self.hiddens), d.hidden, g, None, None, None, L.ptr(self.rewards), self.H + 1, 1, self.H, 1,
                    dr.explore_extrinsic, dr.explore_scale, L.ptr(self.ws_knn), self.ws_knn.numel(), st)
-        L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(self.hiddens), d.hidden,
-               L.ptr(self.latents), L_, None, L.ptr(self.V_t), None, L.ptr(self.ws_cr), self.ws_cr.numel(), st)
+        if not self.heads_done:
+            L.call("dr_critic_fwd", d, ag.critic_struct(target=True), M, L.ptr(self.hiddens), d.hidden,
+                   L.ptr(self.latents), L_, None, L.ptr(self.V_t), None, L.ptr(self.ws_cr), self.ws_cr.numel(), st)
         L.call("dr_lambda_returns", self.B, self.H, L.ptr(self.rewards), L.ptr(self.continues), L.ptr(self.V_t),
                ag.gamma, ag.lambda_, L.ptr(self.R), st)
 
@@ -223,8 +241,9 @@ class ImaginationEngine:
         M = B * (H + 1)
         L_ = d.rows * d.cols
         scale = 1.0 / float(B * self.wsize * H)
-        L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents), L_,
-               None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(), st)
+        if not self.heads_done:
+            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents), L_,
+                   None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(), st)
         critic_args = (d, ag.critic_struct(), B, H, L.ptr(self.hiddens), L.ptr(self.latents), L.ptr(self.R),
                        L.ptr(self.ctape), scale, L.ptr(ag.loss_slot(1)), ag.critic_struct(grad=True),
                        L.ptr(self.ws_cr), self.ws_cr.numel())
@@ -250,9 +269,10 @@ class ImaginationEngine:
         upstream-gradient / transposed-weight prep."""
         ag, d, st = self.dr.agent, self.d, hip.stream()
         M = self.B * (self.H + 1)
-        L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
-               d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr2), self.ws_cr2.numel(),
-               st)
+        if not self.heads_done:
+            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
+                   d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr2),
+                   self.ws_cr2.numel(), st)
         L.call("dr_imagine_bwd_prep", d, self.dr.world_model.packed(), ag.actor_struct(), self.B, self.H, None,
                None, None, L.ptr(self.ws_im), self.ws_im.numel(), st)
 
@@ -417,8 +437,10 @@ class ImaginationEngine:
         B, H = self.B, self.H
         M = B * (H + 1)
         scale = 1.0 / float(B * self.wsize * H)
-        L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
-               d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(), st)
+        if not self.heads_done:
+            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
+                   d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(),
+                   st)
         self._actor_loss()
         L.call("dr_critic_loss_bwd", d, ag.critic_struct(), B, H, L.ptr(self.hiddens), L.ptr(self.latents),
                L.ptr(self.R), L.ptr(self.ctape), scale, L.ptr(ag.loss_slot(1)), ag.critic_struct(grad=True),

@@ -410,6 +410,26 @@ size_t dr_critic_workspace_bytes(const dr_dims* d, int B, int H);
 int dr_critic_fwd(const dr_dims* d, const dr_critic* c, int M, const float* h, long long ldh, const float* z,
                   long long ldz, float* logits, float* values, void* tape, void* ws, size_t ws_bytes,
                   hipStream_t stream);
+/* The four heads that read the B*(H+1) imagined states in one pass: the reward
+ * and continue heads (dr_imagine_fwd's, rewards / continues [B][H]) and the
+ * target and online critics' values V_t, V_c [B][H+1] with the online critic's
+ * tape (dr_critic_tape_bytes(d, B*(H+1))), from dr_imagine_fwd's latents /
+ * hiddens.  The four first Linears over [h | z] run as one grouped product;
+ * every output holds the bits that dr_imagine_fwd's heads and dr_critic_fwd
+ * (target: values only, its workspace; online: values and tape) give on the
+ * same inputs.  ws_im / ws_cr: the dr_imagine_fwd / dr_critic_fwd workspaces
+ * (scratch of the tails), ws: dr_heads_workspace_bytes.  dr_imagine_fwd skips
+ * its own heads when rewards and continues are both NULL.
+ * dr_heads_supported: 1 in fp32 mode with B*(H+1) >= 1024 and head widths that
+ * are multiples of 4 (<= 208 for the reward / continue heads); otherwise
+ * dr_heads_fwd returns DR_E_UNSUPPORTED with nothing launched and nothing
+ * written, and dr_heads_workspace_bytes returns 0. */
+int dr_heads_supported(const dr_dims* d, int B, int H);
+size_t dr_heads_workspace_bytes(const dr_dims* d, int B, int H);
+int dr_heads_fwd(const dr_dims* d, const dr_world_model* wm, const dr_critic* target, const dr_critic* online,
+                 int B, int H, const float* latents, const float* hiddens, float* rewards, float* continues,
+                 float* V_t, float* V_c, void* ctape, void* ws_im, size_t ws_im_bytes, void* ws_cr,
+                 size_t ws_cr_bytes, void* ws, size_t ws_bytes, hipStream_t stream);
 /* lambda returns (Agent.py:156-172): V [B][H+1] target values */
 int dr_lambda_returns(int B, int H, const float* r, const float* c, const float* V, float gamma, float lam,
                       float* R, hipStream_t stream);
