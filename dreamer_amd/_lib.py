@@ -171,7 +171,11 @@ _SIGS = {
     "dr_replay_sample": (_i, [_ll, _ll, _ll, _i, _i, fp, _d, fp, fp, _i, fp, fp, fp, _sz, fp]),
     "dr_replay_probabilities": (_i, [_ll, _ll, _ll, _i, fp, _d, fp, fp, _sz, fp]),
     "dr_replay_priority_update": (_i, [_ll, _i, fp, fp, _d, _d, _d, _d, _d, fp, fp, fp]),
-    "dr_wm_window_scores": (_i, [_P(dr_dims), _i, _i, dr_wm_loss_cfg, fp, _sz, fp, fp]),
+    "dr_replay_spans_workspace_bytes": (_sz, [_ll]),
+    "dr_replay_spans": (_i, [_ll, _ll, _ll, fp, fp, _i, fp, fp, fp, _sz, fp]),
+    "dr_replay_sample_spans": (_i, [_ll, _ll, _ll, _i, _i, fp, _d, fp, fp, fp, _i, fp, fp, fp, _sz, fp]),
+    "dr_replay_probabilities_spans": (_i, [_ll, _ll, _ll, _i, fp, _d, fp, fp, fp, _sz, fp]),
+    "dr_wm_window_scores":(_i, [_P(dr_dims), _i, _i, dr_wm_loss_cfg, fp, _sz, fp, fp]),
     "dr_disag_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dr_disag_fwd": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, fp, fp, _i, _i, _ll, _ll, _f, _f, fp, _sz, fp]),
     "dr_disag_train_grads": (_i, [_P(dr_ensemble), _i, _i, _i, fp, _ll, fp, _ll, _P(dr_ensemble), fp, fp, _sz, fp]),

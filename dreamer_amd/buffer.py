@@ -13,7 +13,13 @@ sampling on the device: one priority (f32) and one visit count (i32) per ring
 slot beside the mirror, sample_start_indices_device / update_priorities /
 sampling_probabilities on libdreamer_hip (include/dreamer_hip.h has the
 semantics).  sample_start_indices and everything else of the uniform path are
-untouched, and in uniform mode no priority tensor is ever allocated."""
+untouched, and in uniform mode no priority tensor is ever allocated.
+
+replay_episodes = "respect"  keeps the device sampler inside one
+stream of data: a per-slot `first` flag (u8) beside the ring, the window spans
+(dr_replay_spans, recomputed when the mirror takes in new slots) and draws
+masked by span >= sequence_length, with the priorities of curious mode or with
+none (replay = "uniform").  With "ignore" (the default) none of it exists."""
 import numpy as np
 import torch
 
@@ -23,6 +29,7 @@ from .utils import symlog_np
 
 
 REPLAY_MODES = ("uniform", "curious")
+EPISODE_MODES = ("ignore", "respect")
 REPLAY_DEFAULTS = dict(replay_c=1e4, replay_beta=0.7, replay_alpha=0.7, replay_eps=0.01, replay_p_new=1e5)
 
 
@@ -35,6 +42,11 @@ def check_replay(replay, c, beta, alpha, eps, p_new):
                         ("replay_p_new", p_new, p_new > 0.0)):
         if not ok:  # a NaN fails every comparison
             raise ValueError(f"{name} = {v!r} is out of range (beta in (0, 1], alpha > 0, eps > 0, c >= 0, p_new > 0)")
+
+
+def check_replay_episodes(mode):
+    if mode not in EPISODE_MODES:
+        raise ValueError(f"replay_episodes must be one of {EPISODE_MODES}, got {mode!r}")
 
 
 def valid_starts(size, capacity, next_idx, seq_len):
@@ -79,10 +91,19 @@ class Buffer:
         self.replay = "uniform"
         self.replay_c, self.replay_beta, self.replay_alpha, self.replay_eps, self.replay_p_new = (
             REPLAY_DEFAULTS[k] for k in ("replay_c", "replay_beta", "replay_alpha", "replay_eps", "replay_p_new"))
+        # episode-aware replay (set by Dreamer from the config): first_buffer[j] != 0 says that slot j begins a
+        # new stream; only "respect" ever looks at it
+        self.replay_episodes = "ignore"
+        self.first_buffer = np.zeros(buffer_size, dtype=np.uint8)
+        self._span_key = None  # (size, next_idx) the device spans were computed for
+        self._n_valid = 0
 
     # ---- host side (Buffer.py:19-30) -----------------------------------------
-    def add_to_buffer(self, observation, action, reward, continue_):
+    def add_to_buffer(self, observation, action, reward, continue_, first=False):
+        """first=True: this transition begins a new stream of data (replay_episodes = "respect" then draws no
+        window that runs from the slot before into this one)."""
         i = self.next_idx
+        self.first_buffer[i] = 1 if first else 0
         self.observation_buffer[i] = np.array(observation, dtype=self.observation_buffer.dtype)
         self.action_buffer[i] = np.array(action, dtype=np.float32)
         self.continue_buffer[i] = np.array(continue_, dtype=np.float32)
@@ -92,14 +113,15 @@ class Buffer:
         if self.size < self.capacity:
             self.size += 1
 
-    def load_arrays(self, frames, actions, rewards_symlog, continues):
-        """Bulk fill (benchmarks / fixtures): rewards already symlog'ed."""
+    def load_arrays(self, frames, actions, rewards_symlog, continues, first=None):
+        """Bulk fill (benchmarks / fixtures): rewards already symlog'ed; first: the per-slot flags (None: 0)."""
         n = len(frames)
         assert n <= self.capacity
         self.observation_buffer[:n] = frames
         self.action_buffer[:n] = actions.reshape(n, -1)
         self.reward_buffer[:n] = rewards_symlog.reshape(n, 1)
         self.continue_buffer[:n] = continues.reshape(n, 1)
+        self.first_buffer[:n] = 0 if first is None else np.asarray(first).reshape(n) != 0
         self.size = max(self.size, n)
         self.next_idx = n % self.capacity
         self._dirty = list(range(n))
@@ -137,6 +159,12 @@ class Buffer:
             # every slot starts as new; a slot never written is not a valid start
             self._dev["priority"] = torch.full((self.capacity,), float(self.replay_p_new), device=self.device)
             self._dev["visits"] = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        respect = self.replay_episodes != "ignore"
+        if respect and "first" not in self._dev:
+            self._dev["first"] = torch.from_numpy(self.first_buffer).to(self.device)
+            self._dev["span"] = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+            self._dev["n_valid"] = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._span_key = None
         if self._dirty:
             idx = np.unique(np.asarray(self._dirty, dtype=np.int64))
             runs = np.split(idx, np.where(np.diff(idx) != 1)[0] + 1)
@@ -145,24 +173,74 @@ class Buffer:
                 for k, host in (("frames", self.observation_buffer), ("actions", self.action_buffer),
                                 ("rewards", self.reward_buffer), ("continues", self.continue_buffer)):
                     self._dev[k][a:b].copy_(torch.from_numpy(host[a:b]), non_blocking=False)
+                if respect:
+                    self._dev["first"][a:b].copy_(torch.from_numpy(self.first_buffer[a:b]), non_blocking=False)
                 if curious:  # a written slot is a new window; windows that merely contain it keep theirs
                     self._dev["priority"][a:b] = float(self.replay_p_new)
                     self._dev["visits"][a:b] = 0
             self._dirty = []
+            self._span_key = None
+        if respect and self._span_key != (self.size, self.next_idx):
+            # one span pass per refresh (new slots, or a moved write head), and one read-back of the count: the
+            # draws themselves neither rescan nor sync
+            m = self._dev
+            ws = hip.workspace(self.device).get("replay_spans", L.query("dr_replay_spans_workspace_bytes",
+                                                                        self.capacity))
+            L.call("dr_replay_spans", self.capacity, self.size, self.next_idx, L.ptr(m["continues"]),
+                   L.ptr(m["first"]), self.sequence_length, L.ptr(m["span"]), L.ptr(m["n_valid"]), L.ptr(ws),
+                   ws.numel(), hip.stream())
+            self._n_valid = int(m["n_valid"].item())
+            self._span_key = (self.size, self.next_idx)
         return self._dev
 
     # ---- prioritised replay (replay = "curious") -----------------------------
     def _curious(self):
         if self.replay == "uniform":
             raise RuntimeError("dreamer_amd: prioritised sampling needs replay = 'curious'")
+        return self._sampler()
+
+    def _sampler(self):
+        """(mirror, workspace) of the device sampler: replay = "curious", replay_episodes = "respect" or both."""
+        respect = self.replay_episodes != "ignore"
+        if self.replay == "uniform" and not respect:
+            raise RuntimeError("dreamer_amd: device sampling needs replay = 'curious' or replay_episodes = 'respect'")
         check_replay(self.replay, self.replay_c, self.replay_beta, self.replay_alpha, self.replay_eps,
                      self.replay_p_new)
+        check_replay_episodes(self.replay_episodes)
         self._require_gpu()
         if not valid_window_exists(self.size, self.capacity, self.next_idx, self.sequence_length):
             raise ValueError("Not enough data in buffer to sample a full sequence")
         m = self._mirror()
+        if respect and self._n_valid == 0:  # data enough for a window, but every window holds a break
+            raise ValueError("Not enough data in buffer to sample a full sequence")
         ws = hip.workspace(self.device).get("replay", L.query("dr_replay_sample_workspace_bytes", self.capacity))
         return m, ws
+
+    def _respecting(self):
+        if self.replay_episodes == "ignore":
+            raise RuntimeError("dreamer_amd: window spans need replay_episodes = 'respect'")
+        check_replay_episodes(self.replay_episodes)
+        self._require_gpu()
+        return self._mirror()
+
+    def window_spans(self):
+        """int32 device tensor (capacity,): span[i] slots from i on lie in one stream of data (0 for an unwritten
+        slot); slot i is a valid start iff span[i] >= sequence_length (include/dreamer_hip.h).  The mirror's own
+        tensor: read it, do not write it."""
+        return self._respecting()["span"]
+
+    def valid_start_count(self):
+        """How many slots are valid starts (read back when the mirror last took in new data: no sync here)."""
+        self._respecting()
+        return self._n_valid
+
+    def sample_eval_starts(self, batch_size):
+        """Window starts for evaluation: the data distribution, whatever `replay` says.  replay_episodes =
+        "ignore": exactly sample_start_indices (np.random).  "respect": an unweighted device draw among the valid
+        starts from the ad-hoc generator (int64 device tensor)."""
+        if self.replay_episodes == "ignore":
+            return self.sample_start_indices(batch_size)
+        return self._draw(batch_size, None, prioritised=False)[0]
 
     def p_floor(self):
         """What a stored priority that is non-finite or <= 0 counts as."""
@@ -173,8 +251,13 @@ class Buffer:
         prob f32 (B,)), both device tensors; prob[b] = w / W of the start drawn.
         No np.random call and no sync: the uniforms are Philox draws on a
         stream id of the ad-hoc generator (u: explicit float64 uniforms (B,)
-        on the device, for parity tests)."""
-        m, ws = self._curious()
+        on the device, for parity tests).  replay_episodes = "respect": only
+        starts with span >= sequence_length are drawn, with the priorities of
+        curious mode or, in uniform mode, every valid start alike."""
+        return self._draw(batch_size, u, prioritised=self.replay != "uniform")
+
+    def _draw(self, batch_size, u, prioritised):
+        m, ws = self._sampler()
         B = int(batch_size)
         starts = torch.empty(B, dtype=torch.int64, device=self.device)
         prob = torch.empty(B, device=self.device)
@@ -186,9 +269,14 @@ class Buffer:
         else:
             nz = hip.adhoc(self.device).noise()
             rng, sid = nz.rng, nz.stream
-        L.call("dr_replay_sample", self.capacity, self.size, self.next_idx, self.sequence_length, B,
-               L.ptr(m["priority"]), self.p_floor(), L.ptr(u), rng, sid, L.ptr(starts), L.ptr(prob), L.ptr(ws),
-               ws.numel(), hip.stream())
+        if self.replay_episodes == "ignore":
+            L.call("dr_replay_sample", self.capacity, self.size, self.next_idx, self.sequence_length, B,
+                   L.ptr(m["priority"]), self.p_floor(), L.ptr(u), rng, sid, L.ptr(starts), L.ptr(prob), L.ptr(ws),
+                   ws.numel(), hip.stream())
+        else:
+            L.call("dr_replay_sample_spans", self.capacity, self.size, self.next_idx, self.sequence_length, B,
+                   L.ptr(m["priority"]) if prioritised else None, self.p_floor(), L.ptr(m["span"]), L.ptr(u), rng,
+                   sid, L.ptr(starts), L.ptr(prob), L.ptr(ws), ws.numel(), hip.stream())
         return starts, prob
 
     def update_priorities(self, starts_dev, scores_dev):
@@ -206,10 +294,15 @@ class Buffer:
     def sampling_probabilities(self):
         """f32 device tensor (capacity,): the probability that a draw of
         sample_start_indices_device returns each slot (0 for an invalid start)."""
-        m, ws = self._curious()
+        m, ws = self._sampler()
         prob = torch.empty(self.capacity, device=self.device)
-        L.call("dr_replay_probabilities", self.capacity, self.size, self.next_idx, self.sequence_length,
-               L.ptr(m["priority"]), self.p_floor(), L.ptr(prob), L.ptr(ws), ws.numel(), hip.stream())
+        if self.replay_episodes == "ignore":
+            L.call("dr_replay_probabilities", self.capacity, self.size, self.next_idx, self.sequence_length,
+                   L.ptr(m["priority"]), self.p_floor(), L.ptr(prob), L.ptr(ws), ws.numel(), hip.stream())
+        else:
+            L.call("dr_replay_probabilities_spans", self.capacity, self.size, self.next_idx, self.sequence_length,
+                   L.ptr(m["priority"]) if self.replay != "uniform" else None, self.p_floor(), L.ptr(m["span"]),
+                   L.ptr(prob), L.ptr(ws), ws.numel(), hip.stream())
         return prob
 
     def device_key(self):

@@ -9,6 +9,12 @@
 // sums are summed per lane over a contiguous run of chunks and scanned the
 // same way.  No float atomics anywhere; the LDS integer min / max below pick
 // an index, which does not depend on the order they arrive in.
+//
+// Episode-aware replay (replay_episodes = "respect") adds the
+// span pass at the end of the file: span[i] = how many slots from i on belong
+// to one stream, a reverse segmented scan over the ring in the same chunks.
+// With a span array the weight of slot i is masked by span[i] >= S instead of
+// rp_valid; without one (the entry points of 5n) nothing here changes.
 #include "common.h"
 
 #define RP_THREADS 256
@@ -19,8 +25,9 @@ static inline int rp_chunks(long long cap) { return (int)((cap + RP_CHUNK - 1) /
 // what a kernel needs to weigh a slot
 struct RpRing {
   long long cap, size, next_idx, S;
-  const float* priority;
+  const float* priority;  // NULL (only with span): every valid start weighs 1
   double p_floor;
+  const int* span;  // NULL: rp_valid; else slot i is a valid start iff span[i] >= S
 };
 
 // valid start (Buffer.py:33-48 with the straddle made exact)
@@ -29,8 +36,9 @@ __device__ __forceinline__ bool rp_valid(const RpRing& r, long long i) {
   return !(r.size == r.cap && i < r.next_idx && r.next_idx < i + r.S);
 }
 // w_i: the stored priority (non-finite or <= 0: p_floor) of a valid start, else 0
-__device__ __forceinline__ double rp_weight(const RpRing& r, long long i, float p) {
-  if (!rp_valid(r, i)) return 0.0;
+__device__ __forceinline__ double rp_weight(const RpRing& r, long long i, float p, int span) {
+  if (r.span ? (long long)span < r.S : !rp_valid(r, i)) return 0.0;
+  if (!r.priority) return 1.0;
   const bool ok = (__float_as_uint(p) & 0x7f800000u) != 0x7f800000u && p > 0.0f;
   return ok ? (double)p : r.p_floor;
 }
@@ -38,14 +46,24 @@ __device__ __forceinline__ double rp_weight(const RpRing& r, long long i, float 
 __device__ __forceinline__ void rp_load4(const RpRing& r, int c, int tid, long long& i0, double w[4]) {
   i0 = (long long)c * RP_CHUNK + 4 * tid;
   float p[4] = {0.f, 0.f, 0.f, 0.f};
+  int sp[4] = {0, 0, 0, 0};
   if (i0 + 3 < r.cap) {
-    const float4 v = *reinterpret_cast<const float4*>(r.priority + i0);
-    p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    if (r.priority) {
+      const float4 v = *reinterpret_cast<const float4*>(r.priority + i0);
+      p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    }
+    if (r.span) {
+      const int4 v = *reinterpret_cast<const int4*>(r.span + i0);
+      sp[0] = v.x; sp[1] = v.y; sp[2] = v.z; sp[3] = v.w;
+    }
   } else {
     for (int k = 0; k < 4; ++k)
-      if (i0 + k < r.cap) p[k] = r.priority[i0 + k];
+      if (i0 + k < r.cap) {
+        if (r.priority) p[k] = r.priority[i0 + k];
+        if (r.span) sp[k] = r.span[i0 + k];
+      }
   }
-  for (int k = 0; k < 4; ++k) w[k] = i0 + k < r.cap ? rp_weight(r, i0 + k, p[k]) : 0.0;
+  for (int k = 0; k < 4; ++k) w[k] = i0 + k < r.cap ? rp_weight(r, i0 + k, p[k], sp[k]) : 0.0;
 }
 
 // inclusive scan of one double per lane over the 256 lanes (fixed order);
@@ -210,8 +228,7 @@ extern "C" size_t dr_replay_sample_workspace_bytes(long long cap) {
   return (size_t)rp_chunks(cap) * sizeof(double);
 }
 
-static int rp_stage1(const char* fn, long long cap, long long size, long long next_idx, int S, const float* priority,
-                     double p_floor, void* ws, size_t ws_bytes, hipStream_t s, RpRing* out) {
+static int rp_check_ring(const char* fn, long long cap, long long size, long long next_idx, int S) {
   if (!(cap > 0 && size >= 0 && size <= cap && next_idx >= 0 && next_idx < cap && S >= 1)) {
     dr_set_error("%s: need cap > 0, 0 <= size <= cap, 0 <= next_idx < cap and S >= 1", fn);
     return DR_E_INVALID;
@@ -220,7 +237,22 @@ static int rp_stage1(const char* fn, long long cap, long long size, long long ne
     dr_set_error("%s: cap over 2^30 slots", fn);
     return DR_E_UNSUPPORTED;
   }
-  if (!priority || !ws || ((uintptr_t)priority & 15) || ((uintptr_t)ws & 7)) {
+  return DR_OK;
+}
+
+// span == NULL: the entry points of 5n (priority required).  With a span
+// array the priority may be NULL.
+static int rp_stage1(const char* fn, long long cap, long long size, long long next_idx, int S, const float* priority,
+                     double p_floor, const int* span, bool masked, void* ws, size_t ws_bytes, hipStream_t s,
+                     RpRing* out) {
+  DR_TRY(rp_check_ring(fn, cap, size, next_idx, S));
+  if (masked) {
+    if (!span || !ws || ((uintptr_t)span & 15) || ((uintptr_t)priority & 15) || ((uintptr_t)ws & 7)) {
+      dr_set_error("%s: span (16-byte aligned) and ws (8-byte aligned) are required; priority, if given, 16-byte aligned",
+                   fn);
+      return DR_E_INVALID;
+    }
+  } else if (!priority || !ws || ((uintptr_t)priority & 15) || ((uintptr_t)ws & 7)) {
     dr_set_error("%s: priority (16-byte aligned) and ws (8-byte aligned) are required", fn);
     return DR_E_INVALID;
   }
@@ -232,36 +264,65 @@ static int rp_stage1(const char* fn, long long cap, long long size, long long ne
     dr_set_error("%s: workspace too small (%zu < %zu)", fn, ws_bytes, dr_replay_sample_workspace_bytes(cap));
     return DR_E_WORKSPACE;
   }
-  const RpRing r = {cap, size, next_idx, (long long)S, priority, p_floor};
+  const RpRing r = {cap, size, next_idx, (long long)S, priority, p_floor, masked ? span : nullptr};
   hipLaunchKernelGGL(k_replay_chunk_sums, dim3(rp_chunks(cap)), dim3(RP_THREADS), 0, s, r, (double*)ws);
   *out = r;
   return dr_check_launch("replay_chunk_sums");
 }
 
-extern "C" int dr_replay_sample(long long cap, long long size, long long next_idx, int S, int B,
-                                const float* priority, double p_floor, const double* u,
-                                const unsigned long long* rng, int stream_id, long long* starts_out, float* prob_out,
-                                void* ws, size_t ws_bytes, hipStream_t s) {
+static int rp_sample(const char* fn, long long cap, long long size, long long next_idx, int S, int B,
+                     const float* priority, double p_floor, const int* span, bool masked, const double* u,
+                     const unsigned long long* rng, int stream_id, long long* starts_out, float* prob_out, void* ws,
+                     size_t ws_bytes, hipStream_t s) {
   DR_REQUIRE(B >= 0 && starts_out, "need B >= 0 and starts_out");
   DR_REQUIRE(u || rng, "no uniforms (u or rng)");
   if (B == 0) return DR_OK;
   RpRing r;
-  DR_TRY(rp_stage1(__func__, cap, size, next_idx, S, priority, p_floor, ws, ws_bytes, s, &r));
+  DR_TRY(rp_stage1(fn, cap, size, next_idx, S, priority, p_floor, span, masked, ws, ws_bytes, s, &r));
   const int n = rp_chunks(cap), per = (n + RP_THREADS - 1) / RP_THREADS;
   hipLaunchKernelGGL(k_replay_draw, dim3(B), dim3(RP_THREADS), 0, s, r, n, per, (const double*)ws, u, rng, stream_id,
                      starts_out, prob_out);
   return dr_check_launch("replay_draw");
 }
 
-extern "C" int dr_replay_probabilities(long long cap, long long size, long long next_idx, int S,
-                                       const float* priority, double p_floor, float* prob_out, void* ws,
-                                       size_t ws_bytes, hipStream_t s) {
+static int rp_probabilities(const char* fn, long long cap, long long size, long long next_idx, int S,
+                            const float* priority, double p_floor, const int* span, bool masked, float* prob_out,
+                            void* ws, size_t ws_bytes, hipStream_t s) {
   DR_REQUIRE(prob_out, "prob_out is required");
   RpRing r;
-  DR_TRY(rp_stage1(__func__, cap, size, next_idx, S, priority, p_floor, ws, ws_bytes, s, &r));
+  DR_TRY(rp_stage1(fn, cap, size, next_idx, S, priority, p_floor, span, masked, ws, ws_bytes, s, &r));
   const int n = rp_chunks(cap), per = (n + RP_THREADS - 1) / RP_THREADS;
   hipLaunchKernelGGL(k_replay_normalise, dim3(n), dim3(RP_THREADS), 0, s, r, n, per, (const double*)ws, prob_out);
   return dr_check_launch("replay_normalise");
+}
+
+extern "C" int dr_replay_sample(long long cap, long long size, long long next_idx, int S, int B,
+                                const float* priority, double p_floor, const double* u,
+                                const unsigned long long* rng, int stream_id, long long* starts_out, float* prob_out,
+                                void* ws, size_t ws_bytes, hipStream_t s) {
+  return rp_sample(__func__, cap, size, next_idx, S, B, priority, p_floor, nullptr, false, u, rng, stream_id,
+                   starts_out, prob_out, ws, ws_bytes, s);
+}
+
+extern "C" int dr_replay_probabilities(long long cap, long long size, long long next_idx, int S,
+                                       const float* priority, double p_floor, float* prob_out, void* ws,
+                                       size_t ws_bytes, hipStream_t s) {
+  return rp_probabilities(__func__, cap, size, next_idx, S, priority, p_floor, nullptr, false, prob_out, ws, ws_bytes,
+                          s);
+}
+
+extern "C" int dr_replay_sample_spans(long long cap, long long size, long long next_idx, int S, int B,
+                                      const float* priority, double p_floor, const int* span, const double* u,
+                                      const unsigned long long* rng, int stream_id, long long* starts_out,
+                                      float* prob_out, void* ws, size_t ws_bytes, hipStream_t s) {
+  return rp_sample(__func__, cap, size, next_idx, S, B, priority, p_floor, span, true, u, rng, stream_id, starts_out,
+                   prob_out, ws, ws_bytes, s);
+}
+
+extern "C" int dr_replay_probabilities_spans(long long cap, long long size, long long next_idx, int S,
+                                             const float* priority, double p_floor, const int* span,
+                                             float* prob_out, void* ws, size_t ws_bytes, hipStream_t s) {
+  return rp_probabilities(__func__, cap, size, next_idx, S, priority, p_floor, span, true, prob_out, ws, ws_bytes, s);
 }
 
 // Priority update.  One lane per row b; the batch's starts and scores pass
@@ -316,4 +377,165 @@ extern "C" int dr_replay_priority_update(long long cap, int B, const long long* 
   hipLaunchKernelGGL(k_replay_priority_update, dim3((B + RP_THREADS - 1) / RP_THREADS), dim3(RP_THREADS), 0, s, cap, B,
                      starts, scores, c, beta, alpha, eps, (float)p_new, priority, visits);
   return dr_check_launch("replay_priority_update");
+}
+
+// ---- episode-aware replay: the window spans ------------------
+// span[i] = j* - i + 1 for i < size, j* the least stop >= i (the semantics are
+// in include/dreamer_hip.h); 0 for i >= size.  A reverse segmented scan in the
+// chunks of the sampler: stage 1 leaves each chunk's least stop, stage 2 takes
+// the least stop behind its chunk from those and finishes inside the chunk by a
+// suffix minimum over the lanes in LDS.  Everything is an integer minimum or an
+// integer sum in a fixed order: the same inputs give the same bits.
+#define RP_NO_STOP 0x7fffffff
+
+struct RpStops {
+  long long cap, size, newest;  // newest: the slot written last (-1: none)
+  const float* continues;
+  const unsigned char* first;  // NULL: all 0
+};
+
+// Bit k of the result: slot i0 + k (lane `tid` of chunk `c`) is a stop.  One
+// float4 of continues and one 4-byte word of first flags per lane.  first[j + 1]
+// ends slot j, so the lane's own four bytes end slots i0 - 1 .. i0 + 2; the
+// byte that ends i0 + 3 is the next lane's first one (through sh_f), for the
+// last lane the first byte of the next chunk.
+__device__ __forceinline__ unsigned rp_stops4(const RpStops& r, int c, int tid, unsigned char* sh_f, long long& i0) {
+  i0 = (long long)c * RP_CHUNK + 4 * tid;
+  float ct[4] = {1.f, 1.f, 1.f, 1.f};
+  unsigned fb = 0;  // first[i0 + k] in byte k
+  if (i0 + 3 < r.cap) {
+    const float4 v = *reinterpret_cast<const float4*>(r.continues + i0);
+    ct[0] = v.x; ct[1] = v.y; ct[2] = v.z; ct[3] = v.w;
+    if (r.first) fb = *reinterpret_cast<const unsigned*>(r.first + i0);
+  } else {
+    for (int k = 0; k < 4; ++k)
+      if (i0 + k < r.cap) {
+        ct[k] = r.continues[i0 + k];
+        if (r.first) fb |= (unsigned)r.first[i0 + k] << (8 * k);
+      }
+  }
+  sh_f[tid] = (fb & 0xffu) != 0;
+  __syncthreads();
+  bool next_first;
+  if (tid + 1 < RP_THREADS) next_first = sh_f[tid + 1] != 0;
+  else next_first = r.first && i0 + 4 < r.cap && r.first[i0 + 4] != 0;
+  __syncthreads();
+  unsigned m = 0;
+  for (int k = 0; k < 4; ++k) {
+    const long long j = i0 + k;
+    if (j >= r.cap) break;
+    const bool f = k < 3 ? ((fb >> (8 * (k + 1))) & 0xffu) != 0 : next_first;
+    if (!(ct[k] >= 0.5f) || f || j == r.cap - 1 || j == r.newest) m |= 1u << k;  // (a NaN continue is a stop)
+  }
+  return m;
+}
+
+// stage 1: mins[c] = the least stop of chunk c (RP_NO_STOP: none)
+__global__ __launch_bounds__(RP_THREADS) void k_replay_chunk_stops(RpStops r, int* __restrict__ mins) {
+  __shared__ unsigned char sh_f[RP_THREADS];
+  __shared__ int s_min;
+  if (threadIdx.x == 0) s_min = RP_NO_STOP;
+  long long i0;
+  const unsigned m = rp_stops4(r, blockIdx.x, threadIdx.x, sh_f, i0);  // (its barriers also publish s_min)
+  if (m) atomicMin(&s_min, (int)i0 + __ffs(m) - 1);
+  __syncthreads();
+  if (threadIdx.x == 0) mins[blockIdx.x] = s_min;
+}
+
+// stage 2: the spans of chunk c, and counts[c] = how many of them are >= S
+__global__ __launch_bounds__(RP_THREADS) void k_replay_spans(RpStops r, int S, int nchunks,
+                                                             const int* __restrict__ mins, int* __restrict__ span,
+                                                             int* __restrict__ counts) {
+  __shared__ unsigned char sh_f[RP_THREADS];
+  __shared__ int sh[RP_THREADS];
+  __shared__ int s_after;
+  const int tid = threadIdx.x, c = blockIdx.x;
+  if (tid == 0) s_after = RP_NO_STOP;
+  long long i0;
+  const unsigned m = rp_stops4(r, c, tid, sh_f, i0);  // (its barriers also publish s_after)
+  // the least stop behind this chunk (the last slot of the ring is one, so only the last chunk has none)
+  int after = RP_NO_STOP;
+  for (int k = c + 1 + tid; k < nchunks; k += RP_THREADS) after = min(after, mins[k]);
+  if (after != RP_NO_STOP) atomicMin(&s_after, after);
+  // inclusive suffix minimum of the lanes' least stops
+  sh[tid] = m ? (int)i0 + __ffs(m) - 1 : RP_NO_STOP;
+  __syncthreads();
+  for (int o = 1; o < RP_THREADS; o <<= 1) {
+    const int a = tid + o < RP_THREADS ? sh[tid + o] : RP_NO_STOP;
+    __syncthreads();
+    sh[tid] = min(sh[tid], a);
+    __syncthreads();
+  }
+  int nxt = min(tid + 1 < RP_THREADS ? sh[tid + 1] : RP_NO_STOP, s_after);  // the least stop behind the lane's slots
+  __syncthreads();
+  int out[4] = {0, 0, 0, 0}, cnt = 0;
+  for (int k = 3; k >= 0; --k) {
+    const long long j = i0 + k;
+    if (j >= r.cap) continue;
+    if ((m >> k) & 1u) nxt = (int)j;
+    out[k] = j < r.size ? nxt - (int)j + 1 : 0;  // nxt >= j: slot cap - 1 is a stop
+    cnt += out[k] >= S;
+  }
+  if (i0 + 3 < r.cap) {
+    *reinterpret_cast<int4*>(span + i0) = make_int4(out[0], out[1], out[2], out[3]);
+  } else {
+    for (int k = 0; k < 4; ++k)
+      if (i0 + k < r.cap) span[i0 + k] = out[k];
+  }
+  sh[tid] = cnt;
+  __syncthreads();
+  for (int o = RP_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) counts[c] = sh[0];
+}
+
+// stage 3 (one workgroup): n_valid = the sum of the chunks' counts
+__global__ __launch_bounds__(RP_THREADS) void k_replay_span_count(int nchunks, const int* __restrict__ counts,
+                                                                  long long* __restrict__ n_valid) {
+  __shared__ long long sh[RP_THREADS];
+  const int tid = threadIdx.x;
+  long long s = 0;
+  for (int k = tid; k < nchunks; k += RP_THREADS) s += counts[k];
+  sh[tid] = s;
+  __syncthreads();
+  for (int o = RP_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) *n_valid = sh[0];
+}
+
+extern "C" size_t dr_replay_spans_workspace_bytes(long long cap) {
+  if (cap <= 0) return 0;
+  return ((size_t)rp_chunks(cap) * 2 * sizeof(int) + 7) & ~(size_t)7;  // the chunks' least stops, then their counts
+}
+
+extern "C" int dr_replay_spans(long long cap, long long size, long long next_idx, const float* continues,
+                               const unsigned char* first, int S, int* span_out, long long* n_valid_out, void* ws,
+                               size_t ws_bytes, hipStream_t s) {
+  DR_TRY(rp_check_ring(__func__, cap, size, next_idx, S));
+  if (!continues || !span_out || !ws || ((uintptr_t)continues & 15) || ((uintptr_t)span_out & 15) ||
+      ((uintptr_t)first & 3) || ((uintptr_t)ws & 7) || ((uintptr_t)n_valid_out & 7)) {
+    dr_set_error("%s: continues and span_out (16-byte aligned) and ws (8-byte aligned) are required; first, if given, "
+                 "4-byte aligned", __func__);
+    return DR_E_INVALID;
+  }
+  if (ws_bytes < dr_replay_spans_workspace_bytes(cap)) {
+    dr_set_error("%s: workspace too small (%zu < %zu)", __func__, ws_bytes, dr_replay_spans_workspace_bytes(cap));
+    return DR_E_WORKSPACE;
+  }
+  const long long newest = size == 0 ? -1 : size < cap ? size - 1 : (next_idx - 1 + cap) % cap;
+  const RpStops r = {cap, size, newest, continues, first};
+  const int n = rp_chunks(cap);
+  int* mins = (int*)ws;
+  int* counts = mins + n;
+  hipLaunchKernelGGL(k_replay_chunk_stops, dim3(n), dim3(RP_THREADS), 0, s, r, mins);
+  DR_TRY(dr_check_launch("replay_chunk_stops"));
+  hipLaunchKernelGGL(k_replay_spans, dim3(n), dim3(RP_THREADS), 0, s, r, S, n, (const int*)mins, span_out, counts);
+  DR_TRY(dr_check_launch("replay_spans"));
+  if (!n_valid_out) return DR_OK;
+  hipLaunchKernelGGL(k_replay_span_count, dim3(1), dim3(RP_THREADS), 0, s, n, (const int*)counts, n_valid_out);
+  return dr_check_launch("replay_span_count");
 }

@@ -308,7 +308,7 @@ def evaluate_dreams(dr, batches=1, batch_size=None, context=None, horizon=None, 
             return dr.dream_trace(batch_size=batch_size, context=context, horizon=horizon, samples=samples,
                                   decode=False)
         # the same starts for both, both filters at the posterior's mode: the same states
-        starts = dr.buffer.sample_start_indices(batch_size or dr.batch_size)
+        starts = dr.buffer.sample_eval_starts(batch_size or dr.batch_size)
         r = dr.dream_trace(starts=starts, context=context, horizon=horizon, samples=samples, sample=False,
                            decode=False)
         tr = dr.agent_trace(starts=starts, length=S, sample=False)

@@ -14,7 +14,7 @@ from tqdm import tqdm
 from . import _lib as L
 from . import hip
 from .agent import Agent
-from .buffer import REPLAY_DEFAULTS, Buffer, check_replay
+from .buffer import REPLAY_DEFAULTS, Buffer, check_replay, check_replay_episodes
 from .utils import _sanitize_for_save
 from .world_model import WorldModel
 
@@ -112,6 +112,11 @@ class Dreamer(nn.Module):
         for k, v in REPLAY_DEFAULTS.items():
             setattr(buf, k, float(c.get(k, v)))
         check_replay(buf.replay, buf.replay_c, buf.replay_beta, buf.replay_alpha, buf.replay_eps, buf.replay_p_new)
+        # extra config key: replay_episodes = "ignore" (default: windows may run across the
+        # end of an episode, as the reference's do) or "respect" -- the device sampler draws only windows that
+        # lie inside one stream of data, in either replay mode
+        buf.replay_episodes = c.get("replay_episodes", "ignore")
+        check_replay_episodes(buf.replay_episodes)
         # extra config keys: explore = "none" (default: nothing below exists) or
         # "disagreement" -- Plan2Explore's ensemble; its disagreement on imagined states is added to the
         # reward train_Agent learns from (engine.returns); Agent.train_step, the reference-API path, is left alone
@@ -484,11 +489,12 @@ class Dreamer(nn.Module):
     def train_Agent(self):
         """Dreamer.train_Agent (Dreamer.py:264-287): AC_epochs fused epochs.
         replay = "curious": the starts come from the device sampler (the
-        sequential epoch loop; priorities and visits are not touched).
+        sequential epoch loop; priorities and visits are not touched), and so
+        they do with replay_episodes = "respect" in either replay mode.
         explore = "disagreement": the epochs learn from explore_extrinsic * reward +
         explore_scale * disagreement (engine.returns)."""
         self._exploring()  # (ValueError under data parallelism)
-        if self._curious():
+        if self._device_starts():  # replay = "curious" or replay_episodes = "respect"
             return self._train_agent_curious()
         if self.AC_epochs > 1 and self.pipeline_epochs and not self.engine.persistent_chain():
             # config key pipeline_epochs (default on): the epochs' window
@@ -529,6 +535,16 @@ class Dreamer(nn.Module):
             raise ValueError("replay = 'curious' is not supported under data parallelism")
         return True
 
+    def _device_starts(self):
+        """True where the window starts come from the device sampler: replay = "curious" or replay_episodes =
+        "respect" (ValueError under data parallelism for either)."""
+        curious = self._curious()
+        if self.buffer.replay_episodes == "ignore":
+            return curious
+        if self.world is not None or self.world_model._dp is not None:
+            raise ValueError("replay_episodes = 'respect' is not supported under data parallelism")
+        return True
+
     def _train_agent_curious(self):
         la, lc = [], []
         for _ in tqdm(range(self.AC_epochs), desc="Training Agent in Dreams", leave=False):
@@ -561,12 +577,15 @@ class Dreamer(nn.Module):
         out = []
         explore = self._exploring()
         trace = {} if explore else None
-        if self._curious():
+        if self._device_starts():
             # per epoch: device sample -> step with per-window scores -> priority update; no host round trip
+            # (replay_episodes = "respect" in uniform mode: the device sample and the step alone)
+            curious = self._curious()
             for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
                 starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
-                out.append(self.world_model.train_step_ring(self.buffer, starts, scores=True, outputs=trace))
-                self.buffer.update_priorities(starts, self.world_model.last_window_scores)
+                out.append(self.world_model.train_step_ring(self.buffer, starts, scores=curious, outputs=trace))
+                if curious:
+                    self.buffer.update_priorities(starts, self.world_model.last_window_scores)
                 if explore:
                     self._train_explorer(trace)
             return out
@@ -629,6 +648,8 @@ class Dreamer(nn.Module):
         if buf.replay != "uniform":  # prioritised replay: the per-slot state (uniform mode: exactly the keys above)
             m = buf._mirror()
             st["buffer"].update(priority=cpu(m["priority"]), visits=cpu(m["visits"]))
+        if buf.replay_episodes != "ignore":  # episode-aware replay: the per-slot flags (ignore mode: no such key)
+            st["buffer"]["first"] = torch.from_numpy(buf.first_buffer.copy())
         if self.explore == "disagreement":  # the ensemble's AdamW state (its weights are in "model"); absent otherwise
             self.explorer._ensure_flat()
             st["opt_explorer"] = opt(self.explorer.optimiser)
@@ -643,6 +664,8 @@ class Dreamer(nn.Module):
             raise ValueError(f"not a {self.TRAINING_STATE_FORMAT} file: {st.get('format')!r}")
         if self.explore == "disagreement" and "opt_explorer" not in st:
             raise ValueError("the training state was saved without exploration: it has no ensemble optimiser state")
+        if self.buffer.replay_episodes != "ignore" and "first" not in st["buffer"]:
+            raise ValueError("the training state was saved with replay_episodes = 'ignore': it has no first flags")
         self.load_state_dict({k: v.to(self.device) for k, v in st["model"].items()})
         ag, wm, buf = self.agent, self.world_model, self.buffer
         ag._ensure_flat()
@@ -671,6 +694,7 @@ class Dreamer(nn.Module):
         buf.reward_buffer[...] = b["rew"].numpy()
         buf.continue_buffer[...] = b["cont"].numpy()
         buf.next_idx, buf.size = int(b["next_idx"]), int(b["size"])
+        buf.first_buffer[...] = b["first"].numpy() if "first" in b else 0
         buf._dirty = list(range(buf.capacity))  # the device mirror re-uploads on next use
         if buf.replay != "uniform":
             if "priority" not in b:
@@ -1034,7 +1058,9 @@ class Dreamer(nn.Module):
         add_to_buffer as N consecutive blocks of S -- env 0's steps, then env
         1's, ... -- so every block is one env's contiguous stream.  A sampled
         window that crosses a block boundary joins two envs' streams, the same
-        way the reference's windows already join two episodes across a done."""
+        way the reference's windows already join two episodes across a done.
+        With N > 1 the first transition of each block goes in with first=True,
+        so replay_episodes = "respect" draws no such window."""
         N = len(envs)
         with torch.no_grad():
             if self.vec_obs is None or len(self.vec_obs) != N:
@@ -1067,8 +1093,8 @@ class Dreamer(nn.Module):
                 action, _, _, self.vec_latent, self.vec_hidden = self.act_step_batch(
                     np.stack(frames), (self.vec_latent, self.vec_hidden, action), first)
             for block in blocks:
-                for transition in block:
-                    self.buffer.add_to_buffer(*transition)
+                for t, transition in enumerate(block):
+                    self.buffer.add_to_buffer(*transition, first=N > 1 and t == 0)
 
     def evaluate_agent_vec(self, envs, eval_episodes):
         """evaluate_agent with len(envs) episodes in flight: eval_episodes

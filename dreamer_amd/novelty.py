@@ -44,7 +44,7 @@ def evaluate_novelty(dr, batches=1, batch_size=None, length=None):
     with preserved_rng(dr.device):
         for _ in range(int(batches)):
             # each batch draws fresh windows and fresh posterior samples; novelty() alone would put both back
-            starts = dr.buffer.sample_start_indices(batch_size or dr.batch_size)
+            starts = dr.buffer.sample_eval_starts(batch_size or dr.batch_size)
             cur = novelty(dr, starts=starts, length=length).mean(0)
             hip.adhoc(dr.device).noise()  # advance the ad-hoc stream id for the next batch
             acc = cur if acc is None else acc + cur

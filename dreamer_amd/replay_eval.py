@@ -80,16 +80,17 @@ def window_prologue(dr, starts, batch_size, T, draws, mark, check=None):
     dr.batch_size) of them.  check(B), if given, runs before the sampling and
     on the final B.  draws(B, dev) resolves the call's noise (resolve_noise)
     once B is known, before the gather.  Marks "gather" and "encoder".
-    The sampled starts are uniform (buffer.sample_start_indices) also with
+    The sampled starts are uniform (buffer.sample_eval_starts) also with
     replay = "curious": evaluation sees the data distribution, not the
-    training distribution."""
+    training distribution.  With replay_episodes = "respect" they are an
+    unweighted device draw among the windows that lie inside one stream."""
     buf, wmod = dr.buffer, dr.world_model
     dev = buf.device
     if starts is None:
         n_win = batch_size or dr.batch_size
         if check is not None:
             check(int(n_win))
-        starts = buf.sample_start_indices(n_win)
+        starts = buf.sample_eval_starts(n_win)
     st = starts.to(dev, torch.int64) if isinstance(starts, torch.Tensor) else \
         torch.as_tensor(np.asarray(starts), dtype=torch.int64).to(dev)
     B = int(st.numel())

@@ -969,6 +969,51 @@ int dr_replay_priority_update(long long cap, int B, const long long* starts, con
                               double beta, double alpha, double eps, double p_new, float* priority, int* visits,
                               hipStream_t stream);
 
+/* ---- episode-aware replay: only windows inside one stream are drawn --------
+ * (config key replay_episodes = "respect", DESIGN.md 5q.  No reference
+ * definition: the reference's windows run across the end of an episode.)
+ * Per-slot inputs, on the device beside the ring mirror: continues f32 [cap]
+ * (what the ring stores) and first u8 [cap]; first[j] != 0 says that slot j
+ * begins a new stream (a new episode, or a block of another environment).
+ * Stops: slot j is a stop iff any of
+ *   !(continues[j] >= 0.5f)              (a NaN is therefore a stop),
+ *   j + 1 < cap and first[j + 1] != 0,
+ *   j == cap - 1                         (windows never wrap the physical end),
+ *   j is the newest written slot: size - 1 when size < cap, else
+ *                                        (next_idx - 1 + cap) % cap.
+ * Span: span[i] = 0 for i >= size; otherwise span[i] = j* - i + 1 with j* the
+ * least stop >= i.  Slot i is a valid start iff span[i] >= S.  A window may
+ * end on a terminal step (the continue head still sees terminals) and never
+ * holds one before its last position.  Where the data has no break,
+ * span[i] >= S is exactly the valid-start rule of prioritised replay above;
+ * with breaks it is a subset of it.  span is an integer suffix minimum over
+ * stop indices: no order of evaluation changes it.
+ * dr_replay_spans writes span_out int32 [cap] and, if n_valid_out (a device
+ * int64) is given, the number of slots with span >= S, a fixed-order integer
+ * sum.  first may be NULL (all 0).  Three plain launches (the least stop of
+ * each 1024-slot chunk; the suffix minimum over those and inside the chunk;
+ * the count), capturable, no host sync, no allocation.  continues and
+ * span_out must be 16-byte aligned, first 4-byte aligned; cap <= 2^30. */
+size_t dr_replay_spans_workspace_bytes(long long cap);
+int dr_replay_spans(long long cap, long long size, long long next_idx, const float* continues,
+                    const unsigned char* first, int S, int* span_out, long long* n_valid_out, void* ws,
+                    size_t ws_bytes, hipStream_t stream);
+/* dr_replay_sample / dr_replay_probabilities with the valid starts taken from
+ * span (int32 [cap], 16-byte aligned): w_i = priority[i] (floored as above) if
+ * span[i] >= S, else 0.  priority may be NULL: every valid start weighs 1.0,
+ * the float64 sums are then exact integers and the start is exactly the least
+ * valid i with C_i > u n (n the number of valid starts), with no rounding
+ * margin; prob = 1 / n.  A draw never returns a slot with span < S; where no
+ * slot is valid the draw answers start 0, prob 0 (the host refuses first).
+ * Same workspace as dr_replay_sample. */
+int dr_replay_sample_spans(long long cap, long long size, long long next_idx, int S, int B, const float* priority,
+                           double p_floor, const int* span, const double* u, const unsigned long long* rng,
+                           int stream_id, long long* starts_out, float* prob_out, void* ws, size_t ws_bytes,
+                           hipStream_t stream);
+int dr_replay_probabilities_spans(long long cap, long long size, long long next_idx, int S, const float* priority,
+                                  double p_floor, const int* span, float* prob_out, void* ws, size_t ws_bytes,
+                                  hipStream_t stream);
+
 /* ---- latent-disagreement ensemble (Plan2Explore, Sekar et al. 2020, in the
  *      form of DreamerV3's expl.Disag; config key explore = "disagreement",
  *      DESIGN.md 5o).  No reference definition: the reference learns from the
