@@ -494,9 +494,9 @@ class Dreamer(nn.Module):
         explore = "disagreement": the epochs learn from explore_extrinsic * reward +
         explore_scale * disagreement (engine.returns)."""
         self._exploring()  # (ValueError under data parallelism)
-        if self._device_starts():  # replay = "curious" or replay_episodes = "respect"
-            return self._train_agent_curious()
-        if self.AC_epochs > 1 and self.pipeline_epochs and not self.engine.persistent_chain():
+        host = not self._device_starts()  # replay = "curious" or replay_episodes = "respect": device starts
+        B = self.batch_size if self.world is None else self.engine.B
+        if self.AC_epochs > 1 and host and self.pipeline_epochs and not self.engine.persistent_chain():
             # config key pipeline_epochs (default on): the epochs' window
             # starts are drawn up front (same np.random order); the warm start
             # of epoch e+1 then overlaps epoch e's update (engine.run_many),
@@ -505,33 +505,45 @@ class Dreamer(nn.Module):
             # epochs below are faster (a persistent kernel needs every CU, so
             # it cannot share the chip with an overlapped warm start; measured
             # in bench.py's configs1_B64_ac_epochs2)
-            B = self.batch_size if self.world is None else self.engine.B
-            starts = [self.buffer.sample_start_indices(B) for _ in range(self.AC_epochs)]
-            losses = self.engine.run_many(starts)
+            losses = self.engine.run_many([self._window_starts(B) for _ in range(self.AC_epochs)])
             return losses[:, 0].mean(dim=0), losses[:, 1].mean(dim=0)
         if self.AC_epochs == 1:
             # one epoch: one copy of the two loss slots (the loop below costs
             # clone + cat + mean per loss, six small launches outside the
             # captured graphs, each behind a dispatch gap); the mean of one
             # value is that value, bit for bit
-            starts = self.buffer.sample_start_indices(self.batch_size if self.world is None else self.engine.B)
+            starts = self._window_starts(B)
             self.engine.run(starts)
             losses = self.agent.loss_buffer[0:2].clone()
             return losses[0], losses[1]
         la, lc = [], []
         for _ in tqdm(range(self.AC_epochs), desc="Training Agent in Dreams", leave=False):
-            starts = self.buffer.sample_start_indices(self.batch_size if self.world is None else self.engine.B)
+            starts = self._window_starts(B)
             a, c = self.engine.run(starts)
             la.append(a.clone())
             lc.append(c.clone())
         return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
+
+    def _window_starts(self, B):
+        """One epoch's B window starts: a device tensor from the device sampler (no np.random draw) where
+        _device_starts(), else the reference's host draw.  Invariant of the callers: with device starts the first
+        draw comes before the first look at self.engine -- the first device draw seeds the ad-hoc generator and the
+        first engine the engine's, both from torch's CPU generator, in that order.  train_Agent keeps it because
+        device starts exclude data parallelism (so B is not read from the engine) and its pipelining condition tests
+        `host` before it touches self.engine."""
+        if self._device_starts():
+            return self.buffer.sample_start_indices_device(B)[0]
+        return self.buffer.sample_start_indices(B)
+
+    def _data_parallel(self):
+        return self.world is not None or self.world_model._dp is not None
 
     def _curious(self):
         """True in prioritised-replay mode (ValueError under data parallelism:
         per-rank priorities need a design of their own)."""
         if self.buffer.replay == "uniform":
             return False
-        if self.world is not None or self.world_model._dp is not None:
+        if self._data_parallel():
             raise ValueError("replay = 'curious' is not supported under data parallelism")
         return True
 
@@ -541,25 +553,16 @@ class Dreamer(nn.Module):
         curious = self._curious()
         if self.buffer.replay_episodes == "ignore":
             return curious
-        if self.world is not None or self.world_model._dp is not None:
+        if self._data_parallel():
             raise ValueError("replay_episodes = 'respect' is not supported under data parallelism")
         return True
-
-    def _train_agent_curious(self):
-        la, lc = [], []
-        for _ in tqdm(range(self.AC_epochs), desc="Training Agent in Dreams", leave=False):
-            starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
-            a, c = self.engine.run(starts)
-            la.append(a.clone())
-            lc.append(c.clone())
-        return torch.cat(la).mean(dim=0), torch.cat(lc).mean(dim=0)
 
     def _exploring(self):
         """True with explore = "disagreement" (ValueError under data parallelism in either exploring mode: the
         ensemble's gradients have no all-reduce, the entropy's bank would be one rank's states)."""
         if self.explore == "none":
             return False
-        if self.world is not None or self.world_model._dp is not None:
+        if self._data_parallel():
             raise ValueError(f"explore = {self.explore!r} is not supported under data parallelism")
         return self.explore == "disagreement"
 
@@ -577,23 +580,17 @@ class Dreamer(nn.Module):
         out = []
         explore = self._exploring()
         trace = {} if explore else None
-        if self._device_starts():
-            # per epoch: device sample -> step with per-window scores -> priority update; no host round trip
-            # (replay_episodes = "respect" in uniform mode: the device sample and the step alone)
-            curious = self._curious()
-            for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
-                starts, _ = self.buffer.sample_start_indices_device(self.batch_size)
+        device, curious = self._device_starts(), self._curious()
+        for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
+            if device or self.device.type == "cuda":
+                # the step fed from the replay ring (frames stay u8 in HBM).  Host starts: the same np.random draws
+                # as sample_sequences.  Device starts: no host round trip; in curious mode the step also leaves the
+                # per-window scores, which update the priorities (replay_episodes = "respect" in uniform mode: the
+                # device sample and the step alone)
+                starts = self._window_starts(self.batch_size)
                 out.append(self.world_model.train_step_ring(self.buffer, starts, scores=curious, outputs=trace))
                 if curious:
                     self.buffer.update_priorities(starts, self.world_model.last_window_scores)
-                if explore:
-                    self._train_explorer(trace)
-            return out
-        for _ in tqdm(range(self.WM_epochs), desc="Training World Model On Buffer Data", leave=False):
-            if self.device.type == "cuda":
-                # same np.random draws as sample_sequences; frames stay u8 in HBM
-                starts = self.buffer.sample_start_indices(self.batch_size)
-                out.append(self.world_model.train_step_ring(self.buffer, starts, outputs=trace))
                 if explore:
                     self._train_explorer(trace)
             else:

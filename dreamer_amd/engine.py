@@ -20,7 +20,9 @@ Each phase is captured once into a HIP graph and replayed; collectives run
 between the phase graphs.
 """
 import contextlib
+import ctypes
 import gc
+import os
 
 import numpy as np
 
@@ -78,15 +80,14 @@ class ImaginationEngine:
         self.use_graph = use_graph
         self.graph = None
         self.graph_key = None
-        # Second stream: the conv encoder of the warm start (one chunk, the
-        # scan waits on it) and the critic backward beside the actor BPTT in
+        # Second stream: the conv encoder of the warm start (the scan waits on
+        # it) and the critic backward beside the actor BPTT in
         # losses_and_grads(fork=True).  Measured and dropped:
         # time-chunked encoding under the posterior scan (r01 and r04:
         # slower, every later phase of the epoch 3-4x slower when fenced,
         # profiles/r04l_overlap_phase_probe.txt) and a forked critic backward
         # inside the epoch graph (~6 % slower replays, r01_ab_overlap.txt).
         self.side = torch.cuda.Stream(self.dev)
-        self.chunks = [(0, self.T)]
         # explore = "disagreement" (DESIGN.md 5o): the ensemble whose disagreement returns() adds to the rewards
         mode = getattr(dreamer, "explore", "none")
         self.explorer = dreamer.explorer if mode == "disagreement" else None
@@ -98,12 +99,6 @@ class ImaginationEngine:
             self.explorer._ensure_flat()  # (before the first capture: the graphs hold the flat buffer's addresses)
         self._alloc()
     # ------------------------------------------------------------------ setup
-    @staticmethod
-    def warm_chunks(T, size=8):
-        """Time chunks [t0, t1) of the warm-start window: conv chunk c+1 runs
-        while the posterior scan consumes chunk c."""
-        return [(t0, min(T, t0 + size)) for t0 in range(0, T, size)]
-
     def dims(self):
         return self.dr.world_model.dims(self.dr.agent)
 
@@ -113,6 +108,7 @@ class ImaginationEngine:
         B, H, T = self.B, self.H, self.T
         L_ = d.rows * d.cols
         dev = self.dev
+        self.scale = 1.0 / float(B * self.wsize * H)  # of both losses: the mean over the global batch and the horizon
         f = lambda *s: torch.zeros(*s, device=dev)
         self.starts = torch.zeros(B, dtype=torch.int64, device=dev)
         # two pinned staging buffers; an event guards reuse (a graph replay
@@ -142,8 +138,8 @@ class ImaginationEngine:
         self.ws_im = hip.workspace(dev).get("e_im", L.query("dr_imagine_workspace_bytes", d, B, H))
         self.ctape = torch.zeros(L.query("dr_critic_tape_bytes", d, M), dtype=torch.uint8, device=dev)
         self.ws_cr = hip.workspace(dev).get("e_cr", L.query("dr_critic_workspace_bytes", d, B, H))
-        # the online critic's forward / loss backward run on a side stream
-        # beside the target critic and the BPTT (run_many): own workspace
+        # a second critic workspace, not used by the epoch: for a caller's own dr_critic_fwd over the imagined states
+        # beside the engine's (tests/test_gpu_heads_fused.py)
         self.ws_cr2 = hip.workspace(dev).get("e_cr2", L.query("dr_critic_workspace_bytes", d, B, H))
         # the four heads over the imagined states in one pass (dr_heads_fwd) where the library takes the shape;
         # heads_done: imagine() ran them, so returns() / the update skip their own critic forwards
@@ -166,17 +162,9 @@ class ImaginationEngine:
     def encode_and_warm(self, frames, noise_q=None):
         """a3 + a2: frames is a dr_frames over (B, T) windows; actions come from
         self.act_win [B][S][A].  Writes self.z0, self.h0."""
-        d, st = self.d, hip.stream()
-        wm = self.dr.world_model.packed()
-        L.call("dr_encoder_features", d, wm, frames, self.B, self.T, L.ptr(self.feat), L.ptr(self.ws_enc),
-               self.ws_enc.numel(), st)
-        if noise_q is not None:
-            nz = hip.explicit_noise(q=noise_q, device=self.dev)
-        else:
-            nz = L.dr_noise(None, None, self.rng.state.data_ptr(), self.rank * self.B, WARM_STREAM)
-        A = d.action
-        L.call("dr_observe_scan", d, wm, self.B, self.T, L.ptr(self.feat), L.ptr(self.act_win), self.S * A, A, None,
-               None, nz, L.ptr(self.z0), L.ptr(self.h0), None, L.ptr(self.ws_obs), self.ws_obs.numel(), st)
+        st = hip.stream()
+        self._encode_chunk(0, self.T, st, frames=frames)
+        self._scan_chunk(0, self.T, st, q=noise_q)
 
     def imagine(self, eps=None, q=None, deterministic=False, z0=None, h0=None, d=None):
         """a7: unroll H steps from (self.z0, self.h0) (or the given slot);
@@ -234,132 +222,135 @@ class ImaginationEngine:
         """update_S, actor loss + BPTT, critic CE backward (Agent.py:96-145).
         With fork=True the critic backward runs on the side stream beside the
         actor's BPTT (they share only read-only inputs)."""
-        ag, d = self.dr.agent, self.d
         main = torch.cuda.current_stream(self.dev)
-        st = main.cuda_stream
-        B, H = self.B, self.H
-        M = B * (H + 1)
-        L_ = d.rows * d.cols
-        scale = 1.0 / float(B * self.wsize * H)
-        if not self.heads_done:
-            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents), L_,
-                   None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(), st)
-        critic_args = (d, ag.critic_struct(), B, H, L.ptr(self.hiddens), L.ptr(self.latents), L.ptr(self.R),
-                       L.ptr(self.ctape), scale, L.ptr(ag.loss_slot(1)), ag.critic_struct(grad=True),
-                       L.ptr(self.ws_cr), self.ws_cr.numel())
+        self._critic_fwd()
         if fork:
             self.side.wait_stream(main)
-            L.call("dr_critic_loss_bwd", *critic_args, self.side.cuda_stream)
-        L.call("dr_update_S", self.R_all.numel(), L.ptr(self.R_all), L.ptr(ag.S_dev), L.ptr(self.norm), None, 0, st)
-        L.call("dr_actor_loss_grad", B, H, d.action, L.ptr(self.mus), L.ptr(self.sigmas), L.ptr(self.actions),
-               L.ptr(self.R), L.ptr(self.V_c), L.ptr(self.norm), ag.nu, scale, L.ptr(self.loss_a), L.ptr(self.g_mu),
-               L.ptr(self.g_sig), st)
+            self._critic_bwd(self.side.cuda_stream)
+        self._actor_loss()
         if not fork:
-            L.call("dr_critic_loss_bwd", *critic_args, st)
-        L.call("dr_imagine_bwd", d, self.dr.world_model.packed(), ag.actor_struct(), B, H, L.ptr(self.latents),
-               L.ptr(self.hiddens), L.ptr(self.actions), L.ptr(self.g_mu), L.ptr(self.g_sig), None, None, None,
-               L.ptr(self.tape), ag.actor_struct(grad=True), L.ptr(self.ws_im), self.ws_im.numel(), st)
-        ag.loss_slot(0).copy_(self.loss_a[0:1])
+            self._critic_bwd()
+        self._bptt()
+        self._actor_loss_slot()
         if fork:
             main.wait_stream(self.side)
 
-    # pieces of losses_and_grads for the two-stream update of run_many
+    # The launches of the update, each written once; losses_and_grads, the two
+    # data-parallel phases (_ph_critic, _bptt) and the pipelined graphs
+    # (_pipe_capture) are compositions of them.
+    def _critic_fwd(self):
+        """Online critic forward (Agent.py:105): V_c and the critic's tape; dr_heads_fwd did it where imagine() ran
+        the grouped heads.  Like every launch method, on the current stream of the current device, which self.dev
+        must be."""
+        if self.heads_done:
+            return
+        ag, d = self.dr.agent, self.d
+        L.call("dr_critic_fwd", d, ag.critic_struct(), self.B * (self.H + 1), L.ptr(self.hiddens), d.hidden,
+               L.ptr(self.latents), d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr),
+               self.ws_cr.numel(), hip.stream())
+
     def _x_critic_fwd_and_prep(self):
-        """side stream: online critic forward (Agent.py:105) and the BPTT's
+        """Pipelined epochs: online critic forward and the BPTT's
         upstream-gradient / transposed-weight prep."""
-        ag, d, st = self.dr.agent, self.d, hip.stream()
-        M = self.B * (self.H + 1)
-        if not self.heads_done:
-            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
-                   d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr2),
-                   self.ws_cr2.numel(), st)
-        L.call("dr_imagine_bwd_prep", d, self.dr.world_model.packed(), ag.actor_struct(), self.B, self.H, None,
-               None, None, L.ptr(self.ws_im), self.ws_im.numel(), st)
+        self._critic_fwd()
+        L.call("dr_imagine_bwd_prep", self.d, self.dr.world_model.packed(), self.dr.agent.actor_struct(), self.B,
+               self.H, None, None, None, L.ptr(self.ws_im), self.ws_im.numel(), hip.stream())
 
     def _actor_loss(self):
         """update_S and the actor loss / its gradient w.r.t. mu, sigma (Agent.py:78-125)."""
         ag, d, st = self.dr.agent, self.d, hip.stream()
         B, H = self.B, self.H
-        scale = 1.0 / float(B * self.wsize * H)
         L.call("dr_update_S", self.R_all.numel(), L.ptr(self.R_all), L.ptr(ag.S_dev), L.ptr(self.norm), None, 0, st)
         L.call("dr_actor_loss_grad", B, H, d.action, L.ptr(self.mus), L.ptr(self.sigmas), L.ptr(self.actions),
-               L.ptr(self.R), L.ptr(self.V_c), L.ptr(self.norm), ag.nu, scale, L.ptr(self.loss_a), L.ptr(self.g_mu),
-               L.ptr(self.g_sig), st)
+               L.ptr(self.R), L.ptr(self.V_c), L.ptr(self.norm), ag.nu, self.scale, L.ptr(self.loss_a),
+               L.ptr(self.g_mu), L.ptr(self.g_sig), st)
 
-    def _x_critic_bwd(self):
-        """side stream: two-hot CE of the critic and its backward (Agent.py:127-145)."""
-        ag, d = self.dr.agent, self.d
-        B, H = self.B, self.H
-        scale = 1.0 / float(B * self.wsize * H)
-        L.call("dr_critic_loss_bwd", d, ag.critic_struct(), B, H, L.ptr(self.hiddens), L.ptr(self.latents),
-               L.ptr(self.R), L.ptr(self.ctape), scale, L.ptr(ag.loss_slot(1)), ag.critic_struct(grad=True),
-               L.ptr(self.ws_cr2), self.ws_cr2.numel(), hip.stream())
+    def _critic_bwd(self, stream_ptr=None):
+        """Two-hot CE of the critic and its backward (Agent.py:127-145), on the current stream (of the current device
+        = self.dev) unless given one."""
+        ag = self.dr.agent
+        L.call("dr_critic_loss_bwd", self.d, ag.critic_struct(), self.B, self.H, L.ptr(self.hiddens),
+               L.ptr(self.latents), L.ptr(self.R), L.ptr(self.ctape), self.scale, L.ptr(ag.loss_slot(1)),
+               ag.critic_struct(grad=True), L.ptr(self.ws_cr), self.ws_cr.numel(),
+               hip.stream() if stream_ptr is None else stream_ptr)
 
-    def _bptt(self, d=None):
-        ag, d = self.dr.agent, (self.d if d is None else d)
-        L.call("dr_imagine_bwd_main", d, self.dr.world_model.packed(), ag.actor_struct(), self.B, self.H,
-               L.ptr(self.latents), L.ptr(self.hiddens), L.ptr(self.actions), L.ptr(self.g_mu), L.ptr(self.g_sig),
-               0, L.ptr(self.tape), ag.actor_struct(grad=True), L.ptr(self.ws_im), self.ws_im.numel(), hip.stream())
-        ag.loss_slot(0).copy_(self.loss_a[0:1])
+    def _bptt(self, d=None, prepared=False):
+        """The actor's BPTT through the unroll: dr_imagine_bwd, or with prepared=True (dr_imagine_bwd_prep ran, the
+        pipelined epochs) its main part alone; d: dims override (launch_form = 1 there)."""
+        ag = self.dr.agent
+        head = (self.d if d is None else d, self.dr.world_model.packed(), ag.actor_struct(), self.B, self.H,
+                L.ptr(self.latents), L.ptr(self.hiddens), L.ptr(self.actions), L.ptr(self.g_mu), L.ptr(self.g_sig))
+        tail = (L.ptr(self.tape), ag.actor_struct(grad=True), L.ptr(self.ws_im), self.ws_im.numel(), hip.stream())
+        if prepared:
+            L.call("dr_imagine_bwd_main", *head, 0, *tail)
+        else:
+            L.call("dr_imagine_bwd", *head, None, None, None, *tail)
+
+    def _actor_loss_slot(self):
+        self.dr.agent.loss_slot(0).copy_(self.loss_a[0:1])
 
     def optimise(self):
         """non-finite skip, clip_grad_norm_(100) x2, AdamW x2, soft target (Agent.py:137-153)."""
         self.dr.agent.fused_optimiser_step(self.sq, self.skip)
 
     # phases of one epoch; collectives (world > 1) run between phases
-    def _encode_chunk(self, t0, t1, stream_ptr):
+    def _encode_chunk(self, t0, t1, stream_ptr, frames=None):
+        """Conv encoder over window steps [t0, t1) of all B windows into self.feat; frames: a dr_frames to read
+        instead of the replay ring at self.starts (encode_and_warm)."""
         d = self.d
-        fr = self.dr.buffer.frames_struct(self.starts)
-        fr.t0 = t0
+        if frames is None:
+            frames = self.dr.buffer.frames_struct(self.starts)
+            frames.t0 = t0
         off = t0 * self.B * d.enc_hidden * 4
-        L.call("dr_encoder_features", d, self.dr.world_model.packed(), fr, self.B, t1 - t0,
+        L.call("dr_encoder_features", d, self.dr.world_model.packed(), frames, self.B, t1 - t0,
                L.ptr(self.feat) + off, L.ptr(self.ws_enc), self.ws_enc.numel(), stream_ptr)
 
-    def _scan_chunk(self, t0, t1, stream_ptr):
+    def _scan_chunk(self, t0, t1, stream_ptr, q=None, rng=None, d=None, out=None):
         """Posterior scan over window steps [t0, t1) (Dreamer.py:244-262).  A
-        chunk after the first continues from (self.z0, self.h0): its first
-        step runs GRU(z_{t0-1}, a_{t0-1}, h) and the sampler's Philox stream
-        is offset by t0, so the draws equal the unchunked scan's."""
-        d, A = self.d, self.d.action
-        nz = L.dr_noise(None, None, self.rng.state.data_ptr(), self.rank * self.B, WARM_STREAM + t0)
+        chunk after the first continues from (z0, h0): its first step runs
+        GRU(z_{t0-1}, a_{t0-1}, h) and the sampler's Philox stream is offset
+        by t0, so the draws equal the unchunked scan's.  q: explicit sampler
+        noise (parity); rng: a Philox state other than the engine's and d: a
+        dims override (the pipelined warm starts: their own copy of the state,
+        launch_form = 1); out: the (z0, h0) to write instead of self's."""
+        d, A = (self.d if d is None else d), self.d.action
+        z0, h0 = (self.z0, self.h0) if out is None else out
+        if q is not None:
+            nz = hip.explicit_noise(q=q, device=self.dev)
+        else:
+            state = self.rng.state if rng is None else rng
+            nz = L.dr_noise(None, None, state.data_ptr(), self.rank * self.B, WARM_STREAM + t0)
         feat = L.ptr(self.feat) + t0 * self.B * d.enc_hidden * 4
         if t0 == 0:
             acts, zi, hi = L.ptr(self.act_win), None, None
         else:
-            acts, zi, hi = L.ptr(self.act_win) + (t0 - 1) * A * 4, L.ptr(self.z0), L.ptr(self.h0)
+            acts, zi, hi = L.ptr(self.act_win) + (t0 - 1) * A * 4, L.ptr(z0), L.ptr(h0)
         L.call("dr_observe_scan", d, self.dr.world_model.packed(), self.B, t1 - t0, feat, acts, self.S * A, A,
-               hi, zi, nz, L.ptr(self.z0), L.ptr(self.h0), None, L.ptr(self.ws_obs), self.ws_obs.numel(),
-               stream_ptr)
+               hi, zi, nz, L.ptr(z0), L.ptr(h0), None, L.ptr(self.ws_obs), self.ws_obs.numel(), stream_ptr)
 
     def _ph_encwarm(self):
-        """a3 + a2, pipelined: the conv encoder runs chunk by chunk on the side
-        stream; the scan of chunk c waits only for chunk c's features."""
+        """a3 + a2: the conv encoder on the side stream, the scan behind it on
+        the main one."""
         main = torch.cuda.current_stream(self.dev)
         self.dr.buffer.gather_actions(self.starts, self.act_win)
         self.side.wait_stream(main)
-        done = []
         with torch.cuda.stream(self.side):
-            for t0, t1 in self.chunks:
-                self._encode_chunk(t0, t1, self.side.cuda_stream)
-                ev = torch.cuda.Event()
-                ev.record(self.side)
-                done.append(ev)
-        for (t0, t1), ev in zip(self.chunks, done):
-            main.wait_event(ev)
-            self._scan_chunk(t0, t1, main.cuda_stream)
+            self._encode_chunk(0, self.T, self.side.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+        main.wait_event(ev)
+        self._scan_chunk(0, self.T, main.cuda_stream)
 
     def time_encoder(self, reps=5):
-        """Average ms of the conv encoder (all chunks, back to back on one
-        stream, no overlap): the dominant kernel group's live duration for the
-        bench's roofline line."""
+        """Average ms of the conv encoder (back to back on one stream, no
+        overlap): the dominant kernel group's live duration for the bench's
+        roofline line."""
         st = torch.cuda.current_stream(self.dev)
-        for t0, t1 in self.chunks:
-            self._encode_chunk(t0, t1, st.cuda_stream)
+        self._encode_chunk(0, self.T, st.cuda_stream)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(st)
         for _ in range(reps):
-            for t0, t1 in self.chunks:
-                self._encode_chunk(t0, t1, st.cuda_stream)
+            self._encode_chunk(0, self.T, st.cuda_stream)
         b.record(st)
         b.synchronize()
         return a.elapsed_time(b) / reps
@@ -387,7 +378,7 @@ class ImaginationEngine:
             # holding CUs beside k_pbptt (one workgroup on every CU) could push
             # its waits past their bound
             ph[3:4] = [("critic", self._ph_critic, self._allreduce_critic_async),
-                       ("actor", self._ph_actor, self._allreduce_actor)]
+                       ("actor", self._bptt, self._allreduce_actor)]
         return ph
 
     def persistent_chain(self):
@@ -432,28 +423,12 @@ class ImaginationEngine:
     def _ph_critic(self):
         """DP update, part 1: online critic forward, update_S, the actor loss
         and its dL/dmu / dL/dsigma, the critic's CE backward, both loss slots
-        (the kernel order of losses_and_grads(fork=False) without the BPTT)."""
-        ag, d, st = self.dr.agent, self.d, hip.stream()
-        B, H = self.B, self.H
-        M = B * (H + 1)
-        scale = 1.0 / float(B * self.wsize * H)
-        if not self.heads_done:
-            L.call("dr_critic_fwd", d, ag.critic_struct(), M, L.ptr(self.hiddens), d.hidden, L.ptr(self.latents),
-                   d.rows * d.cols, None, L.ptr(self.V_c), L.ptr(self.ctape), L.ptr(self.ws_cr), self.ws_cr.numel(),
-                   st)
+        (the kernel order of losses_and_grads(fork=False) without the BPTT,
+        which is part 2: tests/test_gpu_engine_launches.py)."""
+        self._critic_fwd()
         self._actor_loss()
-        L.call("dr_critic_loss_bwd", d, ag.critic_struct(), B, H, L.ptr(self.hiddens), L.ptr(self.latents),
-               L.ptr(self.R), L.ptr(self.ctape), scale, L.ptr(ag.loss_slot(1)), ag.critic_struct(grad=True),
-               L.ptr(self.ws_cr), self.ws_cr.numel(), st)
-        ag.loss_slot(0).copy_(self.loss_a[0:1])
-
-    def _ph_actor(self):
-        """DP update, part 2: the actor's BPTT (dr_imagine_bwd)."""
-        ag, d = self.dr.agent, self.d
-        L.call("dr_imagine_bwd", d, self.dr.world_model.packed(), ag.actor_struct(), self.B, self.H,
-               L.ptr(self.latents), L.ptr(self.hiddens), L.ptr(self.actions), L.ptr(self.g_mu), L.ptr(self.g_sig),
-               None, None, None, L.ptr(self.tape), ag.actor_struct(grad=True), L.ptr(self.ws_im), self.ws_im.numel(),
-               hip.stream())
+        self._critic_bwd()
+        self._actor_loss_slot()
 
     def epoch_body(self):
         for _, body, coll in self.phases():
@@ -572,8 +547,6 @@ class ImaginationEngine:
         chain at high priority 5.86 ms per epoch against 6.33 unfenced and
         6.87 sequential; fenced at normal priority 8.58, tools/pipe_probe.py,
         profiles/r04i_pipe_probe.txt)"""
-        import ctypes
-        import os
         if cu_fraction is None:
             cu_fraction = float(os.environ.get("DREAMER_WARM_CUS", "0.875"))
         if not 0.0 < cu_fraction < 1.0:
@@ -595,10 +568,10 @@ class ImaginationEngine:
         return torch.cuda.ExternalStream(h.value, device=self.dev)
 
     def _pipe_capture(self, key):
-        dev, B, H = self.dev, self.B, self.H
+        dev = self.dev
         if getattr(self, "_pipe", None) is None:
             self._pipe = dict(
-                stream=self.warm_stream(), side=torch.cuda.Stream(dev),
+                stream=self.warm_stream(),
                 rng=torch.zeros(2, dtype=torch.int64, device=dev),
                 z0=[self.z0, torch.zeros_like(self.z0)],
                 h0=[self.h0, torch.zeros_like(self.h0)],
@@ -606,55 +579,39 @@ class ImaginationEngine:
         P = self._pipe
         if P["key"] == key:
             return P
-        d, A = self.d, self.d.action
         # the warm graphs are captured here and replayed on the CU-masked warm
         # stream, the imagination and the BPTT beside them: all in launch form (a
         # persistent kernel needs every workgroup resident, which neither the
         # capture stream nor a chain sharing the CUs with the warm start can
         # vouch for)
-        dw = L.dr_dims.from_buffer_copy(d)
+        dw = L.dr_dims.from_buffer_copy(self.d)
         dw.launch_form = 1
 
         def warm(s):
-            st = torch.cuda.current_stream(dev).cuda_stream
+            st = hip.stream()
             self.dr.buffer.gather_actions(self.starts, self.act_win)
             self._encode_chunk(0, self.T, st)
-            nz = L.dr_noise(None, None, P["rng"].data_ptr(), self.rank * B, WARM_STREAM)
-            L.call("dr_observe_scan", dw, self.dr.world_model.packed(), B, self.T, L.ptr(self.feat),
-                   L.ptr(self.act_win), self.S * A, A, None, None, nz, L.ptr(P["z0"][s]), L.ptr(P["h0"][s]), None,
-                   L.ptr(self.ws_obs), self.ws_obs.numel(), st)
+            self._scan_chunk(0, self.T, st, rng=P["rng"], d=dw, out=(P["z0"][s], P["h0"][s]))
             L.call("dr_rng_advance", P["rng"].data_ptr(), 1, st)
 
-        cs = torch.cuda.Stream(dev)
-        cs.wait_stream(torch.cuda.current_stream(dev))
-        graphs = {}
-        with _no_gc(), torch.cuda.stream(cs):
-            for s in (0, 1):
-                for name, body in (("warm", lambda s=s: warm(s)),
-                                   ("imagine", lambda s=s: self.imagine(z0=P["z0"][s], h0=P["h0"][s], d=dw))):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=cs):
-                        body()
-                    graphs[(name, s)] = g
-            for name, body in (("returns", self.returns), ("xfwd", self._x_critic_fwd_and_prep),
-                               ("actor_loss", self._actor_loss), ("xbwd", self._x_critic_bwd),
-                               ("bptt", lambda: self._bptt(d=dw)), ("optim", self._ph_optim)):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=cs):
-                    body()
-                graphs[name] = g
-        torch.cuda.current_stream(dev).wait_stream(cs)
-        P["graphs"], P["key"] = graphs, key
+        def bptt():
+            self._bptt(d=dw, prepared=True)
+            self._actor_loss_slot()
+
+        bodies = {}
+        for s in (0, 1):
+            bodies[("warm", s)] = lambda s=s: warm(s)
+            bodies[("imagine", s)] = lambda s=s: self.imagine(z0=P["z0"][s], h0=P["h0"][s], d=dw)
+        bodies.update(returns=self.returns, xfwd=self._x_critic_fwd_and_prep, actor_loss=self._actor_loss,
+                      xbwd=self._critic_bwd, bptt=bptt, optim=self._ph_optim)
+        P["graphs"], P["key"] = dict(zip(bodies, self._record(bodies.values()))), key
         return P
 
     def run_many(self, starts_list):
         """len(starts_list) consecutive train_Agent epochs, pipelined (see
         above).  Returns a [K, 2] device tensor of (actor, critic) losses."""
         self.check_faults(wait=False)
-        ag = self.dr.agent
-        key = self._graph_key()
-        P = self._pipe_capture(key)
-        G = P["graphs"]
+        P = self._pipe_capture(self._graph_key())
         outer = torch.cuda.current_stream(self.dev)
         # DREAMER_CHAIN_PRIORITY (torch stream priority, -1 = high): the
         # imagination / update chain on a stream of that priority, so that its
@@ -663,7 +620,6 @@ class ImaginationEngine:
         # chain beside an unfenced warm stream measured 13.1 ms per epoch
         # against 6.9 sequential after sequential epochs in the same process,
         # profiles/r04n_pipe_after.txt)
-        import os
         fenced = 0.0 < float(os.environ.get("DREAMER_WARM_CUS", "0.875")) < 1.0
         prio = int(os.environ.get("DREAMER_CHAIN_PRIORITY", "-1" if fenced else "0"))
         if prio != 0:
@@ -671,16 +627,15 @@ class ImaginationEngine:
                 P["chain"], P["chain_prio"] = torch.cuda.Stream(self.dev, priority=prio), prio
             P["chain"].wait_stream(outer)
             with torch.cuda.stream(P["chain"]):
-                losses = self._run_many(P, G, starts_list, P["chain"])
+                losses = self._run_many(P, starts_list, P["chain"])
             outer.wait_stream(P["chain"])
         else:
-            losses = self._run_many(P, G, starts_list, outer)
+            losses = self._run_many(P, starts_list, outer)
         return losses
 
-    def _run_many(self, P, G, starts_list, main):
-        import os
+    def _run_many(self, P, starts_list, main):
         K = len(starts_list)
-        ag = self.dr.agent
+        ag, G = self.dr.agent, P["graphs"]
         ws = P["stream"]
         host = torch.from_numpy(np.stack([np.asarray(x, dtype=np.int64) for x in starts_list])).pin_memory()
         losses = torch.empty(K, 2, device=self.dev)
@@ -708,72 +663,53 @@ class ImaginationEngine:
                 ev_w[e] = torch.cuda.Event()
                 ev_w[e].record(s)
 
-        xs = P["side"]
-        import os
-        # Which update pieces run on a third stream: the online critic forward
-        # + BPTT prep ("fwd", beside the target critic) and/or the critic
-        # loss backward ("bwd", beside the BPTT).  Measured at B = 64
-        # (bench, 30 epochs): none 242.3k, bwd 235.4k, both 228.7k, fwd
-        # 224.3k steps/s -- a third stream of latency-bound launches slows
-        # the critical chain more than it hides, so the default is "none".
-        side = os.environ.get("DREAMER_SIDE", "none")
-
-        def record(stream):
-            ev = torch.cuda.Event()
-            ev.record(stream)
-            return ev
-
+        # The whole chain of an epoch runs on the one stream.  Measured and
+        # dropped: the online critic forward + BPTT prep beside the target
+        # critic and / or the critic loss backward beside the BPTT on a third
+        # stream (B = 64, bench, 30 epochs: 242.3k steps/s on one stream,
+        # 235.4k with the backward aside, 224.3k with the forward aside, 228.7k
+        # with both) -- a third stream of latency-bound launches slows the
+        # critical chain more than it hides.
         issue_warm(0)
         for e in range(K):
             if e + 1 < K:
                 issue_warm(e + 1)
             main.wait_event(ev_w[e])
             G[("imagine", e & 1)].replay()
-            ev_i[e] = record(main)
-            # side stream: online critic forward + BPTT prep beside the target
-            # critic / lambda returns; later the critic loss backward beside
-            # the actor's BPTT (they share only read-only inputs)
-            s1 = xs if side in ("both", "fwd") else main
-            s2 = xs if side in ("both", "bwd") else main
-            if s1 is xs:
-                xs.wait_event(ev_i[e])
-            with torch.cuda.stream(s1):
-                G["xfwd"].replay()
-            ev_x1 = record(s1)
+            ev_i[e] = torch.cuda.Event()
+            ev_i[e].record(main)
+            G["xfwd"].replay()
             G["returns"].replay()
             if self.dp:
                 self._allgather_R()
-            ev_r = record(main)
-            main.wait_event(ev_x1)
             G["actor_loss"].replay()
-            if s2 is xs:
-                xs.wait_event(record(main) if s1 is main else ev_r)
-            with torch.cuda.stream(s2):
-                G["xbwd"].replay()
-            ev_x2 = record(s2)
+            G["xbwd"].replay()
             G["bptt"].replay()
-            main.wait_event(ev_x2)
             if self.dp:
                 self._allreduce_grads()
             G["optim"].replay()
             losses[e].copy_(ag.loss_buffer[0:2])
         main.wait_stream(ws)
-        main.wait_stream(xs)
         self.epochs += K
         self._pipe_host = host  # keep the pinned source alive until the H2D copy ran
         return losses
 
-    def _capture(self, key):
-        """Record each phase into its own HIP graph (capture does not execute;
-        run() replays right after).  Collectives stay outside the graphs."""
-        s = torch.cuda.Stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
+    def _record(self, bodies):
+        """Each body into a HIP graph of its own, in order, on one capture
+        stream (capture does not execute; the caller replays)."""
+        cur = torch.cuda.current_stream(self.dev)
+        cs = torch.cuda.Stream(self.dev)
+        cs.wait_stream(cur)
         graphs = []
-        with _no_gc(), torch.cuda.stream(s):
-            for _, body, _ in self.phases():
+        with _no_gc(), torch.cuda.stream(cs):
+            for body in bodies:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=s):
+                with torch.cuda.graph(g, stream=cs):
                     body()
                 graphs.append(g)
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        self.graph, self.graph_key = graphs, key
+        cur.wait_stream(cs)
+        return graphs
+
+    def _capture(self, key):
+        """The phases of run(), one graph each.  Collectives stay outside the graphs."""
+        self.graph, self.graph_key = self._record([body for _, body, _ in self.phases()]), key

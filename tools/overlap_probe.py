@@ -103,8 +103,9 @@ def main():
         ge = torch.cuda.CUDAGraph()
         with torch.cuda.stream(cap):
             with torch.cuda.graph(ge, stream=cap):
-                for t0, t1 in eng.warm_chunks(eng.T, (eng.T + nch - 1) // nch):
-                    eng._encode_chunk(t0, t1, cap.cuda_stream)
+                size = (eng.T + nch - 1) // nch  # time chunks [t0, t1) of the warm-start window
+                for t0 in range(0, eng.T, size):
+                    eng._encode_chunk(t0, min(eng.T, t0 + size), cap.cuda_stream)
         torch.cuda.synchronize()
         warm = lambda: (ge.replay(), gscan.replay())
         out[f"chunks{nch} enc"] = timed(lambda: [ge.replay() for _ in range(N)])
